@@ -8,7 +8,12 @@ bytes of SURVEY.md §8(d): 8·D + 10·K per client (read x, write dense output, 
 5-byte/entry wire).  At N GPUs each rank owns its own client delta (weak scaling), no collective in
 the timed region; ``value`` = N x per-client bytes / max-over-ranks step time.
 
-Also reported (``configs``): configs[1] (8-bit dithering of 10 cnn_femmist_tiny deltas batched),
+A plain run does only that: set-up, W warm-up steps, K timed steps, the result line (``roofline``,
+``cpu_baseline`` and ``parity`` null, ``extra`` empty).  ``--dump-outputs DIR`` also writes what the last
+timed step computed (see ``dump_outputs``); the inputs are seeded, so two builds run with the same
+arguments can be compared array for array.
+
+With ``--full`` also reported (``configs``): configs[1] (8-bit dithering of 10 cnn_femmist_tiny deltas batched),
 configs[2] (top-k 1 % of a 25M delta), and at N > 1 configs[3] (codec + fused weighted
 decode-accumulate + RCCL reduce of a 25M delta per client).  ``roofline`` is the dominant kernel
 (stacked_encode: the fused filter + select + compaction kernel) — its algorithmic bytes over its live
@@ -17,7 +22,8 @@ HIP-event duration, timed in a separate short run so no event sits inside the ti
 the decode kernel's figure.  ``cpu_baseline`` times the CPU-PyTorch path of the same workload on this
 host (all threads on the full delta, one thread on a 64 MiB sample) and, labelled apart, the numpy oracle.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--skip-extra] [--skip-cpu]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                       [--full [--skip-extra] [--skip-cpu] [--probe KERNEL]]
 """
 
 from __future__ import annotations
@@ -182,6 +188,47 @@ def timed(fn, steps, warmup, world, probe=None):
         _lib.call("flc_probe_set", None)
         probe_ms = tot.value / max(cnt.value, 1)
     return (t1 - t0) * 1e3 / steps, probe_ms
+
+
+DUMP_SAMPLE = 1_000_000  # positions of the dense output kept beside the entries the wire names
+DUMP_SAMPLE_SEED = 4321
+
+
+def dump_outputs(dirname: str, pkt, out: torch.Tensor, world: int = 1, rank: int = 0) -> dict:
+    """Write what one step returned — the packet and the dense decoded vector — as ``dirname/<name>.npy``
+    (``<name>_rank<r>.npy`` at N > 1), float32 or float64, 57 MB at the headline shape (the limit is 64 MB):
+
+    wire_idx (float64; indices are below 2^53, exact), wire_codes, wire_norm, wire_tiles (float64) — the packet;
+    decoded_at_kept — the dense output at the packet's indices; decoded_sample — the dense output at
+    ``DUMP_SAMPLE`` fixed positions (a CPU generator seeded with ``DUMP_SAMPLE_SEED``, ascending; the whole
+    output when it is no longer than that); decoded_sample_pos (float64) — those positions; decoded_nnz
+    (float64) — the count of non-zeros of the whole output.  Returns {name: array}."""
+    os.makedirs(dirname, exist_ok=True)
+    k, n = pkt.idx.numel(), out.numel()
+    if n > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        pos = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+    else:
+        pos = torch.arange(n)
+    arrays = {
+        "wire_idx": pkt.idx.to(torch.float64),
+        "wire_codes": pkt.codes[:k].to(torch.float32),
+        "wire_norm": pkt.norm.to(torch.float32),
+        "decoded_at_kept": out[pkt.idx.long()],
+        "decoded_sample": out[pos.to(out.device)],
+        "decoded_sample_pos": pos.to(torch.float64),
+        "decoded_nnz": torch.count_nonzero(out).reshape(1).to(torch.float64),
+    }
+    if pkt.tiles is not None:
+        arrays["wire_tiles"] = pkt.tiles.to(torch.float64)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    res = {name: t.cpu().numpy() for name, t in arrays.items()}
+    nbytes = sum(a.nbytes for a in res.values())
+    if nbytes > 64_000_000:
+        raise ValueError(f"--dump-outputs would write {nbytes} bytes, more than 64 MB")
+    for name in res:
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), res[name])
+    return res
 
 
 def cpu_model() -> str:
@@ -551,9 +598,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20)  # the first ~15 steps of a fresh process run ~3 % slow
-    ap.add_argument("--skip-extra", action="store_true")
-    ap.add_argument("--skip-cpu", action="store_true")
-    ap.add_argument("--probe", default="stacked_encode", help="kernel timed live for the roofline entry")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the per-kernel and roofline runs, the other "
+                         "configs and placements, the aggregation half, the parity self-check, the CPU baselines")
+    ap.add_argument("--skip-extra", action="store_true", help="with --full: leave out the other configs")
+    ap.add_argument("--skip-cpu", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--probe", default="stacked_encode",
+                    help="with --full: kernel timed live for the roofline entry")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="process-group backend; gloo only with --launch-check (CPU rehearsal of the launcher)")
     ap.add_argument("--launch-check", action="store_true",
@@ -561,6 +614,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.backend != "nccl" and not args.launch_check:
         ap.error("the benchmark itself runs on RCCL; --backend gloo is for --launch-check only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -579,15 +634,22 @@ def main():
     out = torch.empty(D, dtype=torch.float32, device=dev)
     settle_gpu(out)
     ctr = [0]
+    last = [None]  # the newest step's packet (its dense output is `out`), for --dump-outputs
 
     def step():
         ctr[0] += 1
         pkt = codec.stacked_encode(x, K, LEVELS, seed=rank, counter=ctr[0])
         codec.stacked_decode(pkt, out=out)
+        last[0] = pkt
 
     ms, _ = timed(step, args.steps, args.warmup, world)  # no probe events inside the timed steps
     ms = max_over_ranks(ms, world)
-    _, probe_ms = timed(step, 5, 1, world, probe=args.probe)  # the roofline kernel, timed on its own run
+    if args.dump_outputs:  # before any further step overwrites `out`
+        dump_outputs(args.dump_outputs, last[0], out, world, rank)
+    last[0] = None
+    probe_ms = None
+    if args.full:
+        _, probe_ms = timed(step, 5, 1, world, probe=args.probe)  # the roofline kernel, timed on its own run
     value = world * stacked_bytes(D, K) / (ms * 1e-3) / 1e9
 
     # dominant-kernel roofline: algorithmic bytes per launch / live average duration
@@ -643,7 +705,7 @@ def main():
                 "traffic": (traffic_from_profiles().get("stacked_decode") or {}).get("bytes"),
                 "algorithmic_bytes": kernel_bytes["stacked_decode"],
             }
-    if not args.skip_extra:
+    if args.full and not args.skip_extra:
         # SURVEY §8(d)'s "realistic" variant of the headline input: 5 % exact zeros (the dithering's zero path,
         # zeros among the candidates); same step, same bytes formula
         xz = x.clone()
@@ -749,7 +811,7 @@ def main():
     del x, out
     torch.cuda.empty_cache()
 
-    if not args.skip_extra:
+    if args.full and not args.skip_extra:
         # configs[1]: 8-bit dithering, 10 clients x cnn_femmist_tiny (417,482 params), one batched launch
         d2, b2 = 417_482, 10
         X = torch.randn(b2, d2, generator=gen, device=dev) * 1e-3
@@ -1020,7 +1082,7 @@ def main():
     topk_err = int(max_over_ranks(float(topk_err), world))
 
     cpu = None
-    if rank == 0 and not args.skip_cpu:  # after the GPU work, at every N (rank 0's host cores)
+    if rank == 0 and args.full and not args.skip_cpu:  # after the GPU work, at every N (rank 0's host cores)
         cpu = cpu_baseline()
         for key, ck in (("config0_fedavg_10x417482", "aggregation_config0_fedavg_10x417482"),
                         ("config0_fedavg_10x417482", "aggregation_config0_host_server"),
