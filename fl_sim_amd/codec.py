@@ -464,12 +464,40 @@ def stacked_encode(x: torch.Tensor, k: int, levels: int = 127, seed: int = 0, co
     return StackedPacket(idx, codes, norm, n, levels, tiles)
 
 
+def _round_args(C: int, dev, counter: int, counters, counts):
+    """The per-client Philox counters and count destinations of a round encode (flc_stacked_encode[_delta]_round) as
+    ctypes arrays: ``counters`` (None: ``counter`` for every client) and ``counts`` (None: no counts) — a contiguous
+    device int64 tensor of C elements, or a sequence of C one-element device int64 tensors."""
+    import ctypes
+
+    ctr = [int(counter)] * C if counters is None else [int(t) for t in counters]
+    if len(ctr) != C:
+        raise ValueError("one counter per client")
+    cp = None
+    if counts is not None:
+        if isinstance(counts, torch.Tensor):
+            if counts.dtype != torch.int64 or counts.numel() != C or not counts.is_contiguous() or counts.device != dev:
+                raise ValueError(f"counts must be a contiguous int64 tensor of {C} elements on {dev}")
+            ptrs = [counts.data_ptr() + 8 * c for c in range(C)]
+        else:
+            counts = list(counts)
+            if len(counts) != C or any(t.dtype != torch.int64 or t.numel() != 1 or t.device != dev for t in counts):
+                raise ValueError(f"counts must be {C} one-element int64 tensors on {dev}")
+            ptrs = [t.data_ptr() for t in counts]
+        cp = (ctypes.c_void_p * C)(*ptrs)
+    return (ctypes.c_uint64 * C)(*ctr), cp
+
+
 def stacked_encode_batch(xs: Sequence[torch.Tensor], k: int, levels: int = 127, seeds: Sequence[int] = (),
-                         counter: int = 0, with_tiles: bool = True, wires=None) -> Optional[Sequence[StackedPacket]]:
+                         counter: int = 0, with_tiles: bool = True, wires=None, counters: Optional[Sequence[int]] = None,
+                         counts=None) -> Optional[Sequence[StackedPacket]]:
     """The stacked encode of many clients' flat deltas (all of one size) in one launch (flc_stacked_encode_batch):
     packet c equals ``stacked_encode(xs[c], k, levels, seeds[c], counter)`` bit for bit.  ``wires``: the packed wire
     records to write into — a ``[clients, >= stride]`` uint8 tensor (then nothing is returned: the records are the
-    output) or a list of one record per client (the packets returned are views of them)."""
+    output) or a list of one record per client (the packets returned are views of them).  ``counters``: one Philox
+    counter per client in place of ``counter``; ``counts``: a device int64 tensor ``[clients]`` (or a list of
+    one-element ones) that receives each packet's number of kept entries with a nonzero (or NaN) value — either keyword
+    takes the call through flc_stacked_encode_round, whose encode makes the counts itself."""
     import ctypes
 
     C = len(xs)
@@ -518,19 +546,26 @@ def stacked_encode_batch(xs: Sequence[torch.Tensor], k: int, levels: int = 127, 
                    "tiles": P(*[tiles.data_ptr() + 4 * ntl * c for c in range(C)]) if with_tiles else None}
     ws = workspace(dev, _ws_size(dev, "flc_stacked_encode_batch_workspace_size", n, k, C), "topk_batch")
     vp = lambda a: None if a is None else ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
-    call("flc_stacked_encode_batch", vp(P(*xp)), C, n, k, levels,
-         vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), counter, vp(ptr["idx"]), vp(ptr["codes"]),
-         vp(ptr["norm"]), vp(ptr["tiles"]), _p(ws), ws.numel(), _stream(dev))
+    if counters is None and counts is None:
+        call("flc_stacked_encode_batch", vp(P(*xp)), C, n, k, levels,
+             vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), counter, vp(ptr["idx"]), vp(ptr["codes"]),
+             vp(ptr["norm"]), vp(ptr["tiles"]), _p(ws), ws.numel(), _stream(dev))
+    else:
+        ctr, cp = _round_args(C, dev, counter, counters, counts)
+        call("flc_stacked_encode_round", vp(P(*xp)), C, n, k, levels,
+             vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), vp(ctr), vp(ptr["idx"]), vp(ptr["codes"]),
+             vp(ptr["norm"]), vp(ptr["tiles"]), vp(cp), _p(ws), ws.numel(), _stream(dev))
     _after_encode(dev)
     return pks
 
 
 def stacked_encode_delta_batch(local_params: Sequence[Sequence[torch.Tensor]], global_params: Sequence[torch.Tensor],
-                               k: int, levels: int = 127, seeds: Sequence[int] = (),
-                               counter: int = 0) -> "PacketBatch":
+                               k: int, levels: int = 127, seeds: Sequence[int] = (), counter: int = 0,
+                               counters: Optional[Sequence[int]] = None, counts=None) -> "PacketBatch":
     """The delta-fused stacked encode of a round's clients in one launch (flc_stacked_encode_delta_batch): client c's
     delta ``cat([l - g for l, g in zip(local_params[c], global_params)])`` (the global model shared by every client),
-    packet c equal to ``stacked_encode_delta(local_params[c], global_params, k, levels, seeds[c], counter)``."""
+    packet c equal to ``stacked_encode_delta(local_params[c], global_params, k, levels, seeds[c], counter)``.
+    ``counters`` / ``counts``: as in :func:`stacked_encode_batch` (flc_stacked_encode_delta_round)."""
     import ctypes
 
     C = len(local_params)
@@ -560,13 +595,18 @@ def stacked_encode_delta_batch(local_params: Sequence[Sequence[torch.Tensor]], g
     P = ctypes.c_void_p
     vp = lambda a: ctypes.cast(a, P)  # noqa: E731
     ws = workspace(dev, _ws_size(dev, "flc_stacked_encode_delta_batch_workspace_size", n, k, C, m), "topk_batch")
-    call("flc_stacked_encode_delta_batch", vp((P * (C * m))(*[t.data_ptr() for lp in ls for t in lp])),
+    if counters is None and counts is None:
+        name, ctr, cnt = "flc_stacked_encode_delta_batch", (counter,), ()
+    else:
+        ca, cp = _round_args(C, dev, counter, counters, counts)
+        name, ctr, cnt = "flc_stacked_encode_delta_round", (vp(ca),), (None if cp is None else vp(cp),)
+    call(name, vp((P * (C * m))(*[t.data_ptr() for lp in ls for t in lp])),
          vp((P * m)(*[t.data_ptr() for t in gs])), vp((ctypes.c_int64 * m)(*[t.numel() for t in gs])), m, C, k,
-         levels, vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), counter,
+         levels, vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), *ctr,
          vp((P * C)(*[idx.data_ptr() + 4 * k * c for c in range(C)])),
          vp((P * C)(*[codes.data_ptr() + kc * c for c in range(C)])),
          vp((P * C)(*[norm.data_ptr() + 4 * c for c in range(C)])),
-         vp((P * C)(*[tiles.data_ptr() + 4 * ntl * c for c in range(C)])), _p(ws), ws.numel(), _stream(dev))
+         vp((P * C)(*[tiles.data_ptr() + 4 * ntl * c for c in range(C)])), *cnt, _p(ws), ws.numel(), _stream(dev))
     _after_encode(dev)
     return PacketBatch(idx, codes, norm, tiles, n, levels)
 
@@ -875,6 +915,22 @@ def _pybatch():
         except (ImportError, AttributeError):
             _PYBATCH.append(None)
     return _PYBATCH[0]
+
+
+_PYROUND: list = []
+
+
+def _pyround():
+    """fl_sim_amd._flcfold.stacked_records_round (the round's stacked encode into a record block, one Philox counter
+    per message, the send counts made by the encode; one C call) when built, else None."""
+    if not _PYROUND:
+        try:
+            from . import _flcfold
+
+            _PYROUND.append(_flcfold.stacked_records_round)
+        except (ImportError, AttributeError):
+            _PYROUND.append(None)
+    return _PYROUND[0]
 
 
 def _pydelta():

@@ -223,21 +223,36 @@ def compress_delta(local: Sequence[torch.Tensor], cached: Sequence[torch.Tensor]
 # it the persistent select's grid exchanges — so a round's messages are encoded together: `communicate` flattens the
 # client's delta (a snapshot: the model may change before the encode runs) and fixes its Philox (seed, counter) and
 # send-count slot, and the first access to any of the round's records — or to a statistic of their compressors —
-# encodes them all in one launch (flc_stacked_encode_batch: each client's select on its share of the CUs, records
-# bit-identical to the per-message encodes) and counts their dithering stages' nonzero inputs in one more
-# (flc_count_nonzero_at_batch).  FLC_DEFER_ENCODE=0 encodes every message when it is made (the one-C-call form).
+# encodes them all in one launch chain (flc_stacked_encode_round: each client's select on its share of the CUs with
+# the message's own (seed, counter) — sampled clients' compressors have advanced differently, so a round's counters
+# differ — records bit-identical to the per-message encodes; the select also counts the dithering stage's nonzero
+# inputs into the message's slot, so no count launch follows).  FLC_DEFER_ENCODE=0 encodes every message when it is
+# made (the one-C-call form).  deferred_stats() counts the batched encodes run and their messages.
 DEFER_ENCODE = os.environ.get("FLC_DEFER_ENCODE", "1") != "0"
 _DEFER_MAX_N = 1 << 24
 _DEFER_MAX_PENDING = 64
 _DEFER_MAX_BATCHES = 16
 
 
+_STATS = {"batches": 0, "messages": 0}
+
+
+def deferred_stats(reset: bool = False) -> dict:
+    """``{"batches": batched encodes run, "messages": messages they encoded}`` since import or since the last
+    ``deferred_stats(reset=True)`` (which returns the figures up to then)."""
+    out = dict(_STATS)
+    if reset:
+        _STATS.update(batches=0, messages=0)
+    return out
+
+
 class _Batch:
-    """The waiting messages of one (device, n, k, levels, counter)."""
+    """The waiting messages of one (device, n, k, levels)."""
 
     def __init__(self, key):
         self.key = key
-        self.items = []  # (CompressedDelta, flat delta, seed, count slot, dithering compressor, stream, its handle)
+        # (CompressedDelta, flat delta, seed, count slot, dithering compressor, stream, its handle, counter)
+        self.items = []
 
     def run(self) -> None:
         if _PENDING.get(self.key) is self:
@@ -253,31 +268,29 @@ class _Batch:
             raise
 
     def _encode(self, items) -> None:
-        di, n, k, levels, counter = self.key
+        di, n, k, levels = self.key
         dev = torch.device("cuda", di)
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
             ch = cur.cuda_stream
             for st in {it[6]: it[5] for it in items if it[6] != ch}.values():  # (deltas flattened on other streams)
                 cur.wait_stream(st)
-            stride, off = codec.stacked_wire_layout(n, k)
+            stride, _ = codec.stacked_wire_layout(n, k)
             C = len(items)
             recs = torch.empty(C, stride, dtype=torch.uint8, device=dev)
             flats = [it[1] for it in items]
-            fast = codec._pybatch()
-            if fast is not None:  # both launches in one C call
+            seeds, ctrs, cnts = [it[2] for it in items], [it[7] for it in items], [it[3] for it in items]
+            fast = codec._pyround()
+            if fast is not None:  # one C call: the encode's launch chain fills the count slots too
                 ws = codec.workspace(dev, codec._ws_size(dev, "flc_stacked_encode_batch_workspace_size", n, k, C),
                                      "topk_batch")
-                fast(flats, [it[2] for it in items], counter, k, levels, recs, [it[3] for it in items], ws)
+                fast(flats, seeds, ctrs, k, levels, recs, cnts, ws)
             else:
-                codec.stacked_encode_batch(flats, k, levels, seeds=[it[2] for it in items], counter=counter,
-                                           wires=recs)
-                P = ctypes.c_void_p * C
-                _lib.call("flc_count_nonzero_at_batch", P(*[f.data_ptr() for f in flats]),
-                          P(*[recs[c].data_ptr() + off["idx"] for c in range(C)]), C, n, k,
-                          P(*[it[3].data_ptr() for it in items]), codec._stream(dev))
+                codec.stacked_encode_batch(flats, k, levels, seeds=seeds, counters=ctrs, counts=cnts, wires=recs)
             codec._after_encode(dev)
-            for (d, flat, _, _, sd, _, sh), r in zip(items, recs.unbind(0)):
+            _STATS["batches"] += 1
+            _STATS["messages"] += C
+            for (d, flat, _, _, sd, _, sh, _), r in zip(items, recs.unbind(0)):
                 if sh != ch:
                     flat.record_stream(cur)
                     sd._note_slab_stream(cur)  # (the count was written on this stream, not the slot's own)
@@ -307,12 +320,12 @@ def _deferred(local, cached, shapes, n: int, K: int, s: int, tk: Compressor, sd:
         return None
     st = torch.cuda.current_stream(dev)
     cnt = sd._count_slot(dev, st)  # (before the batch is looked up: a full slab is read back, running the batches)
-    key = (dev.index, n, K, s, seed_ctr[1])
+    key = (dev.index, n, K, s)
     b = _PENDING.get(key)
     if b is None:
         b = _PENDING[key] = _Batch(key)
     d = CompressedDelta(shapes, dev, n, k=K, levels=s, batch=b)
-    b.items.append((d, flat, seed_ctr[0], cnt, sd, st, st.cuda_stream))
+    b.items.append((d, flat, seed_ctr[0], cnt, sd, st, st.cuda_stream, seed_ctr[1]))
     tk._finish(n, tk.K)
     base = _norm_stage_send(sd, None)
     sd._finish_pending(n, cnt, base, (1.0 + np.ceil(math.log2(sd.s))) / 32.0)  # compressors.py:365

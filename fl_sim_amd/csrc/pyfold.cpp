@@ -538,12 +538,18 @@ PyObject* delta_flat(PyObject*, PyObject* args) {
 // stacked_records_batch(flats, seeds, counter, k, levels, records, counts, ws): the deferred messages of a round in
 // one C call — flc_stacked_encode_batch of the flat deltas into rows of the [C, >= stride] record block (row c equals
 // client c's one-message record), then flc_count_nonzero_at_batch of each delta at its kept indices into counts[c].
-PyObject* stacked_records_batch(PyObject*, PyObject* args) {
-  PyObject *flats, *seeds, *recs, *counts, *wso;
-  unsigned long long counter;
+//
+// stacked_records_round(flats, seeds, counters, k, levels, records, counts, ws): the same with one Philox counter per
+// message (a sequence), in one C call and one encode launch chain — flc_stacked_encode_round, whose select writes
+// counts[c] itself (no count launches).
+PyObject* stacked_records(PyObject* args, const bool round) {
+  PyObject *flats, *seeds, *recs, *counts, *wso, *ctrs = nullptr;
+  unsigned long long counter = 0;
   long long k;
   int levels;
-  if (!PyArg_ParseTuple(args, "OOKLiOOO", &flats, &seeds, &counter, &k, &levels, &recs, &counts, &wso)) return nullptr;
+  if (round ? !PyArg_ParseTuple(args, "OOOLiOOO", &flats, &seeds, &ctrs, &k, &levels, &recs, &counts, &wso)
+            : !PyArg_ParseTuple(args, "OOKLiOOO", &flats, &seeds, &counter, &k, &levels, &recs, &counts, &wso))
+    return nullptr;
   std::vector<PyObject*> keep;
   auto done = [&](PyObject* r) {
     for (PyObject* o : keep) Py_XDECREF(o);
@@ -559,6 +565,18 @@ PyObject* stacked_records_batch(PyObject*, PyObject* args) {
   const Py_ssize_t C = PySequence_Fast_GET_SIZE(f[0]);
   if (C < 1 || PySequence_Fast_GET_SIZE(f[1]) != C || PySequence_Fast_GET_SIZE(f[2]) != C)
     return done(value_error("one seed and one count per client, at least one client"));
+  std::vector<uint64_t> ct64;
+  if (round) {
+    PyObject* fc = PySequence_Fast(ctrs, "stacked_records_round takes a sequence of counters");
+    if (!fc) return done(nullptr);
+    keep.push_back(fc);
+    if (PySequence_Fast_GET_SIZE(fc) != C) return done(value_error("one counter per client"));
+    ct64.resize(C);
+    for (Py_ssize_t c = 0; c < C; ++c) {
+      ct64[c] = (uint64_t)PyLong_AsUnsignedLongLongMask(PySequence_Fast_ITEMS(fc)[c]);
+      if (PyErr_Occurred()) return done(nullptr);
+    }
+  }
   int dev = -1;
   int64_t n = -1;
   std::vector<const float*> xp(C);
@@ -607,16 +625,21 @@ PyObject* stacked_records_batch(PyObject*, PyObject* args) {
   }
   void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
   int rc = FLC_OK;
-  const char* what = "flc_stacked_encode_batch";
+  const char* what = round ? "flc_stacked_encode_round" : "flc_stacked_encode_batch";
   Py_BEGIN_ALLOW_THREADS
   int cur = -1;
   (void)hipGetDevice(&cur);
   if (cur != dev) (void)hipSetDevice(dev);
-  rc = flc_stacked_encode_batch(xp.data(), (int)C, n, k, levels, sd.data(), counter, ip.data(), kp.data(), np.data(),
-                                tp.data(), ws->data_ptr(), (size_t)ws->numel(), st);
-  if (rc == FLC_OK) {
-    what = "flc_count_nonzero_at_batch";
-    rc = flc_count_nonzero_at_batch(xp.data(), cip.data(), (int)C, n, k, cp.data(), st);
+  if (round) {
+    rc = flc_stacked_encode_round(xp.data(), (int)C, n, k, levels, sd.data(), ct64.data(), ip.data(), kp.data(),
+                                  np.data(), tp.data(), cp.data(), ws->data_ptr(), (size_t)ws->numel(), st);
+  } else {
+    rc = flc_stacked_encode_batch(xp.data(), (int)C, n, k, levels, sd.data(), counter, ip.data(), kp.data(), np.data(),
+                                  tp.data(), ws->data_ptr(), (size_t)ws->numel(), st);
+    if (rc == FLC_OK) {
+      what = "flc_count_nonzero_at_batch";
+      rc = flc_count_nonzero_at_batch(xp.data(), cip.data(), (int)C, n, k, cp.data(), st);
+    }
   }
   if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
   Py_END_ALLOW_THREADS
@@ -626,6 +649,8 @@ PyObject* stacked_records_batch(PyObject*, PyObject* args) {
   }
   return done((Py_INCREF(Py_None), Py_None));
 }
+PyObject* stacked_records_batch(PyObject*, PyObject* args) { return stacked_records(args, false); }
+PyObject* stacked_records_round(PyObject*, PyObject* args) { return stacked_records(args, true); }
 
 // fold_records(records, weights, n, k, levels, delta, theta, v, beta0, opt, lr, beta2, tau): the server update of a
 // round of stacked records (flc_fedopt_fold_records) on Python lists.  TypeError (nothing launched) when a tensor is
@@ -760,6 +785,9 @@ PyMethodDef kMethods[] = {
      "flc_fedopt_fold_records on Python lists"},
     {"delta_flat", delta_flat, METH_VARARGS,
      "delta_flat(local, global): a new flat fp32 tensor cat(local - global) (flc_delta_flatten) on the tensors' device"},
+    {"stacked_records_round", stacked_records_round, METH_VARARGS,
+     "stacked_records_round(flats, seeds, counters, k, levels, records, counts, ws): flc_stacked_encode_round into the "
+     "rows of a record block, one Philox counter per message, the send counts written by the encode itself"},
     {"stacked_records_batch", stacked_records_batch, METH_VARARGS,
      "stacked_records_batch(flats, seeds, counter, k, levels, records, counts, ws): flc_stacked_encode_batch into the "
      "rows of a record block, then flc_count_nonzero_at_batch into counts"},

@@ -1095,9 +1095,10 @@ __global__ __launch_bounds__(256) void topk_sample_kernel(Src x, int64_t n, int 
 #endif
 }
 
-// one client of a batched call (flc_stacked_encode_batch[_delta]): its input, Philox seed and outputs.  `x` is the
-// client's flat delta, or (delta batch) its table of local parameter pointers; the kernel's source argument is the
-// prototype (the delta batch: offsets and global pointers shared by every client)
+// one client of a batched call (flc_stacked_encode_batch[_delta], flc_stacked_encode[_delta]_round): its input, Philox
+// (seed, counter) and outputs.  `x` is the client's flat delta, or (delta batch) its table of local parameter
+// pointers; the kernel's source argument is the prototype (the delta batch: offsets and global pointers shared by
+// every client)
 struct BatchEntry {
   const void* x;
   uint64_t seed;
@@ -1106,13 +1107,23 @@ struct BatchEntry {
   float* norm;
   unsigned* tiles;
   float* val;  // plain top-k batch (flc_topk_encode_batch): the kept values
+  uint64_t counter;           // the message's Philox counter (the *_batch entries: one value for every client)
+  unsigned long long* count;  // stacked, optional: the kept entries with !(value == 0) (the dithering stage's send count)
 };
 
 // batched: every client's header state, flags and histograms ([0, kOffBlk) of each kOffStage header) zeroed in one
 // launch at the start of a call (grid: blocks per header x headers) — except header 0's error word (EncState::err,
 // the one every client ORs into and flc_topk_status reads), which stays sticky across calls until a reset
 static_assert(offsetof(EncState, call) == 0 && offsetof(EncState, err) == 8, "the error word is bytes 8-15");
-__global__ __launch_bounds__(256) void zero_headers_kernel(char* base, int n_words16) {
+// (tab: every client's count destination — the take-all case has no sample launch to zero them — client c by header
+// c % gridDim.y's first thread)
+__global__ __launch_bounds__(256) void zero_headers_kernel(char* base, int n_words16,
+                                                           const BatchEntry* __restrict__ tab, int n_clients) {
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    for (int c = (int)blockIdx.y; c < n_clients; c += (int)gridDim.y) {
+      unsigned long long* const cnt = tab[c].count;
+      if (cnt) *cnt = 0ull;
+    }
   uint4* p = reinterpret_cast<uint4*>(base + (size_t)blockIdx.y * kOffStage);
   for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < n_words16; i += (int)gridDim.x * 256) {
     if (i == 0 && blockIdx.y == 0) {
@@ -1135,7 +1146,7 @@ __device__ __forceinline__ DeltaSrc batch_src(const DeltaSrc& proto, const Batch
 
 // batched: `per` blocks sample each client into its own header (and zero the client's header for its select: the
 // state, the flags of its nb blocks, the histograms and accumulators — the `per` blocks of a client each take a
-// slice; the sample keys lie past kOffBlk)
+// slice; the sample keys lie past kOffBlk — and the client's send count, which its select's blocks add to)
 template <class Src>
 __global__ __launch_bounds__(256) void topk_sample_batch_kernel(Src proto, const BatchEntry* __restrict__ tab,
                                                                 int64_t n, int S, EncWs w, int per) {
@@ -1155,7 +1166,9 @@ __global__ __launch_bounds__(256) void topk_sample_batch_kernel(Src proto, const
       p[q] = make_uint4(0u, 0u, 0u, 0u);
     }
   }
-  (void)sample_one(batch_src(proto, tab[g]), n, S, w, sub * 256 + (int)threadIdx.x);
+  const BatchEntry& e = tab[g];
+  if (sub == 0 && threadIdx.x == 0 && e.count) *e.count = 0ull;
+  (void)sample_one(batch_src(proto, e), n, S, w, sub * 256 + (int)threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1375,7 +1388,9 @@ __global__ __launch_bounds__(kET) void topk_filter_kernel(Src x, int64_t n, EncW
 // FUSED: the filter phase runs first in the same kernel (one exchange after it): the candidates stay in
 // LDS, so the staging round trip through HBM and a kernel boundary are gone
 // BATCH (stacked, fused, flat input only): blocks [g * w.nb, (g + 1) * w.nb) run client g's select with its own
-// header, staging area, input, seed and outputs (tab[g]); the selects never exchange with each other
+// header, staging area, input, Philox (seed, counter) and outputs (tab[g]); the selects never exchange with each
+// other.  With a count destination (stacked) every block adds its kept entries with !(value == 0) to it: the send
+// count of the dithering stage (compressors.py:339-365), zeroed by the launch ahead of the select
 template <bool STACKED, bool FUSED, class Src, bool BATCH = false>
 __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long long k, EncWs w,
                                                           int* __restrict__ idx_out, float* __restrict__ val_out,
@@ -1384,6 +1399,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
                                                           unsigned* __restrict__ tile_out, int S, long long rank_lo,
                                                           long long rank_hi, int take_all,
                                                           const BatchEntry* __restrict__ tab = nullptr) {
+  unsigned long long* cnt_out = nullptr;
   if constexpr (BATCH) {
     static_assert(FUSED, "batched selects are the fused encode");
     const int g = (int)blockIdx.x / w.nb;  // (w.nb: blocks per client, set by the host)
@@ -1393,6 +1409,8 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
     const BatchEntry e = tab[g];
     x = batch_src(x, e);
     seed = e.seed;
+    counter = e.counter;
+    cnt_out = e.count;
     idx_out = e.idx;
     code_out = e.codes;
     val_out = e.val;
@@ -1988,6 +2006,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
     }
   };
   const unsigned plast = q1 > 0u ? q1 - 1u : 0u;
+  unsigned nzc = 0;  // (batched stacked) this wave's kept entries with !(value == 0): wave-uniform
   if (!src.xmode && !src.gmode) {
     // LDS candidates: pass 2 touches no memory but LDS and the Philox words.  Kept entries are staged in
     // place, wave range order (a kept entry's slot q0 + (kept before it in the range) <= its own index, and
@@ -2046,6 +2065,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
           st_cw[slot] = STACKED ? code_of(c_raw, c_id, have, rw) : c_raw;
         }
         nk += (unsigned)__popcll(km);
+        if constexpr (BATCH && STACKED) nzc += (unsigned)__popcll(__ballot(keep && !(__uint_as_float(c_raw) == 0.0f)));
         s_before += __popcll(ms);
         t_before += __popcll(mt);
         c_raw = n_raw;
@@ -2094,6 +2114,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
         else val_out[pos] = __uint_as_float(raw);
       }
       if (tile_owner) tiles_of(in, id, pos);  // (pos of a dropped candidate: the kept entries before it)
+      if constexpr (BATCH && STACKED) nzc += (unsigned)__popcll(__ballot(keep && !(__uint_as_float(raw) == 0.0f)));
       s_before += __popcll(ms);
       t_before += __popcll(mt);
     };
@@ -2114,6 +2135,17 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
     const long long nxt = s_before + (t_before > skip ? t_before - skip : 0);
     for (int64_t t = (tile_prev >> kTileLog) + 1 + lane; t <= (tile_hi >> kTileLog); t += kWave) tile_out[t] = (unsigned)nxt;
     if (w.bid == w.nb - 1 && q1 >= ncand && lane == 0) tile_out[cdiv_dev(n, kTile)] = (unsigned)k;
+  }
+  if constexpr (BATCH && STACKED) {
+    if (cnt_out) {  // (block-uniform) the block's count: one memory-side add (s_red: last read before the compaction)
+      if (lane == 0) s_red[wid] = nzc;
+      __syncthreads();
+      if (tid == 0) {
+        unsigned long long nz = 0;
+        for (int i = 0; i < kENW; ++i) nz += s_red[i];
+        if (nz) (void)__hip_atomic_fetch_add(cnt_out, nz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
   }
   STAMP(15);
   BLKT(3);
@@ -2358,16 +2390,16 @@ int copy_table(int dev, void* dst, const void* src, size_t bytes, hipStream_t st
 // the batched launches over the clients in chunks of bg.chunk (tab: the entry table, device-readable)
 template <class Src, bool STACKED>
 int launch_topk_batch_chunks(const Src& proto, const BatchEntry* tab, int C, const BatchGeom& bg, int64_t n, int64_t k,
-                             int levels, uint64_t counter, char* base, hipStream_t st, int dev) {
+                             int levels, char* base, hipStream_t st, int dev) {
   // each call starts its headers from zero (state, flags, histograms): no history is carried between calls, so the
   // header / staging split may move with the client count
   const SampleSetup ss = sample_setup(n, k, batch_sample_cap(n));
   const double step = levels > 0 ? 1.0 / (double)levels : 0.0;
   static_assert(kOffBlk % 16 == 0 && kOffStage % 16 == 0 && kOffFlags % 16 == 0 && kOffHist % 16 == 0,
                 "16-B zeroing of the headers");
-  if (ss.take_all)  // (otherwise every chunk's sample launch zeroes its clients' headers)
+  if (ss.take_all)  // (otherwise every chunk's sample launch zeroes its clients' headers and send counts)
     FLC_LAUNCH("zero_headers", zero_headers_kernel, dim3(8, (unsigned)bg.chunk), dim3(256), 0, st, base,
-               (int)(kOffBlk / 16));
+               (int)(kOffBlk / 16), tab, C);
   EncWs w;
   w.base = base;
   w.var = base + (size_t)bg.chunk * kOffStage;
@@ -2392,7 +2424,7 @@ int launch_topk_batch_chunks(const Src& proto, const BatchEntry* tab, int C, con
     FLC_LAUNCH_CO(co, STACKED ? "stacked_encode_batch" : "topk_encode_batch", (topk_select_kernel<STACKED, true, Src, true>),
                dim3((unsigned)(cn * bg.g.G)),
                dim3(kET), 0, st, proto, n, (long long)k, w, nullptr, nullptr, nullptr, nullptr, levels, step, 0ull,
-               counter, nullptr, ss.S, ss.rank_lo, ss.rank_hi, ss.take_all, t);
+               0ull, nullptr, ss.S, ss.rank_lo, ss.rank_hi, ss.take_all, t);
   }
   return co.finish();
 }
@@ -2401,8 +2433,7 @@ int launch_topk_batch_chunks(const Src& proto, const BatchEntry* tab, int C, con
 // workspace) both copied into the workspace in one copy
 template <class Src, bool STACKED = true>
 int launch_topk_batch(const Src& proto, const std::vector<BatchEntry>& ents, const std::vector<char>& extra, int64_t n,
-                      int64_t k, int levels, uint64_t counter, void* ws, size_t ws_bytes, hipStream_t st,
-                      const char* who) {
+                      int64_t k, int levels, void* ws, size_t ws_bytes, hipStream_t st, const char* who) {
   int dev = 0;
   const int cus = stream_cus(st, &dev);
   const int C = (int)ents.size();
@@ -2425,7 +2456,7 @@ int launch_topk_batch(const Src& proto, const std::vector<BatchEntry>& ents, con
     std::memcpy(host.data() + (bg.extra_off - bg.table_off), extra.data(), extra.size());
     if (const int rc = copy_table(dev, base + bg.table_off, host.data(), host.size(), st)) return rc;
   }
-  const int rc = launch_topk_batch_chunks<Src, STACKED>(proto, tab, C, bg, n, k, levels, counter, base, st, dev);
+  const int rc = launch_topk_batch_chunks<Src, STACKED>(proto, tab, C, bg, n, k, levels, base, st, dev);
   if (slot >= 0) {
     const int rc2 = table_done(dev, slot, st);
     if (rc == FLC_OK) return rc2;
@@ -2540,19 +2571,46 @@ size_t flc_stacked_encode_batch_workspace_size(int64_t n, int64_t k, int n_clien
   return batch_geometry(n < 1 ? 1 : n, k < 1 ? 1 : k, n_clients < 1 ? 1 : n_clients, current_cus(nullptr)).need;
 }
 
-int flc_stacked_encode_batch(const float* const* xs, int n_clients, int64_t n, int64_t k, int levels,
-                             const uint64_t* seeds, uint64_t counter, int32_t* const* idx, uint8_t* const* codes,
-                             float* const* norm, uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "flc_stacked_encode_batch";
+}  // extern "C"
+
+namespace {
+// the flat batched stacked encode: client c's Philox counter is counters[c] (null: `counter` for every client), its
+// send count goes to counts[c] (counts null: none)
+int stacked_encode_flat_batch(const char* who, const float* const* xs, int n_clients, int64_t n, int64_t k, int levels,
+                              const uint64_t* seeds, const uint64_t* counters, uint64_t counter, int32_t* const* idx,
+                              uint8_t* const* codes, float* const* norm, uint32_t* const* tiles,
+                              int64_t* const* counts, void* ws, size_t ws_bytes, void* stream) {
   if (n_clients <= 0 || !xs || !seeds || !idx || !codes || !norm) return fail(FLC_EINVAL, "%s: bad arguments", who);
   if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "%s: levels must be in [1, 127]", who);
   std::vector<BatchEntry> ents((size_t)n_clients);
   for (int c = 0; c < n_clients; ++c) {
     if (int rc = check_topk(xs[c], n, k, who)) return rc;
     if (!idx[c] || !codes[c] || !norm[c]) return fail(FLC_EINVAL, "%s: null output of client %d", who, c);
-    ents[c] = BatchEntry{xs[c], seeds[c], idx[c], codes[c], norm[c], tiles ? tiles[c] : nullptr, nullptr};
+    if (counts && !counts[c]) return fail(FLC_EINVAL, "%s: null count of client %d", who, c);
+    ents[c] = BatchEntry{xs[c], seeds[c], idx[c], codes[c], norm[c], tiles ? tiles[c] : nullptr, nullptr,
+                         counters ? counters[c] : counter,
+                         counts ? reinterpret_cast<unsigned long long*>(counts[c]) : nullptr};
   }
-  return launch_topk_batch(FlatSrc{nullptr}, ents, {}, n, k, levels, counter, ws, ws_bytes, as_stream(stream), who);
+  return launch_topk_batch(FlatSrc{nullptr}, ents, {}, n, k, levels, ws, ws_bytes, as_stream(stream), who);
+}
+}  // namespace
+
+extern "C" {
+
+int flc_stacked_encode_batch(const float* const* xs, int n_clients, int64_t n, int64_t k, int levels,
+                             const uint64_t* seeds, uint64_t counter, int32_t* const* idx, uint8_t* const* codes,
+                             float* const* norm, uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream) {
+  return stacked_encode_flat_batch("flc_stacked_encode_batch", xs, n_clients, n, k, levels, seeds, nullptr, counter, idx,
+                                   codes, norm, tiles, nullptr, ws, ws_bytes, stream);
+}
+
+int flc_stacked_encode_round(const float* const* xs, int n_clients, int64_t n, int64_t k, int levels,
+                             const uint64_t* seeds, const uint64_t* counters, int32_t* const* idx,
+                             uint8_t* const* codes, float* const* norm, uint32_t* const* tiles, int64_t* const* counts,
+                             void* ws, size_t ws_bytes, void* stream) {
+  if (!counters) return fail(FLC_EINVAL, "flc_stacked_encode_round: null counters");
+  return stacked_encode_flat_batch("flc_stacked_encode_round", xs, n_clients, n, k, levels, seeds, counters, 0, idx,
+                                   codes, norm, tiles, counts, ws, ws_bytes, stream);
 }
 
 size_t flc_topk_encode_batch_workspace_size(int64_t n, int64_t k, int n_clients) {
@@ -2567,10 +2625,9 @@ int flc_topk_encode_batch(const float* const* xs, int n_clients, int64_t n, int6
   for (int c = 0; c < n_clients; ++c) {
     if (int rc = check_topk(xs[c], n, k, who)) return rc;
     if (!idx[c] || !val[c]) return fail(FLC_EINVAL, "%s: null output of client %d", who, c);
-    ents[c] = BatchEntry{xs[c], 0, idx[c], nullptr, nullptr, tiles ? tiles[c] : nullptr, val[c]};
+    ents[c] = BatchEntry{xs[c], 0, idx[c], nullptr, nullptr, tiles ? tiles[c] : nullptr, val[c], 0, nullptr};
   }
-  return launch_topk_batch<FlatSrc, false>(FlatSrc{nullptr}, ents, {}, n, k, 0, 0, ws, ws_bytes, as_stream(stream),
-                                           who);
+  return launch_topk_batch<FlatSrc, false>(FlatSrc{nullptr}, ents, {}, n, k, 0, ws, ws_bytes, as_stream(stream), who);
 }
 
 // the delta batch's tables: off[n_tensors + 1] (int64), the global pointers, then each client's local pointers
@@ -2585,11 +2642,15 @@ size_t flc_stacked_encode_delta_batch_workspace_size(int64_t n, int64_t k, int n
                         delta_batch_extra_bytes(n_tensors, n_clients)).need;
 }
 
-int flc_stacked_encode_delta_batch(const float* const* local, const float* const* global, const int64_t* sizes,
-                                   int n_tensors, int n_clients, int64_t k, int levels, const uint64_t* seeds,
-                                   uint64_t counter, int32_t* const* idx, uint8_t* const* codes, float* const* norm,
-                                   uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "flc_stacked_encode_delta_batch";
+}  // extern "C"
+
+namespace {
+// the delta batched stacked encode; counters / counter / counts as stacked_encode_flat_batch
+int stacked_encode_delta_batch(const char* who, const float* const* local, const float* const* global,
+                               const int64_t* sizes, int n_tensors, int n_clients, int64_t k, int levels,
+                               const uint64_t* seeds, const uint64_t* counters, uint64_t counter, int32_t* const* idx,
+                               uint8_t* const* codes, float* const* norm, uint32_t* const* tiles,
+                               int64_t* const* counts, void* ws, size_t ws_bytes, void* stream) {
   if (n_tensors <= 0 || n_clients <= 0 || !local || !global || !sizes || !seeds || !idx || !codes || !norm)
     return fail(FLC_EINVAL, "%s: bad arguments", who);
   if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "%s: levels must be in [1, 127]", who);
@@ -2608,8 +2669,10 @@ int flc_stacked_encode_delta_batch(const float* const* local, const float* const
   const int64_t n = off[n_tensors];
   if (n >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n must be < 2^31", who);
   if (k <= 0 || k >= n) return fail(FLC_EINVAL, "%s: need 0 < k < n (got k=%lld, n=%lld)", who, (long long)k, (long long)n);
-  for (int c = 0; c < n_clients; ++c)
+  for (int c = 0; c < n_clients; ++c) {
     if (!idx[c] || !codes[c] || !norm[c]) return fail(FLC_EINVAL, "%s: null output of client %d", who, c);
+    if (counts && !counts[c]) return fail(FLC_EINVAL, "%s: null count of client %d", who, c);
+  }
   const BatchGeom bg = batch_geometry(n, k, n_clients, current_cus(nullptr),
                                       delta_batch_extra_bytes(n_tensors, n_clients));
   if (!ws || bg.need > ws_bytes) return fail(FLC_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, bg.need);
@@ -2627,8 +2690,31 @@ int flc_stacked_encode_delta_batch(const float* const* local, const float* const
   std::vector<BatchEntry> ents((size_t)n_clients);
   for (int c = 0; c < n_clients; ++c)
     ents[c] = BatchEntry{dx + o_lp + (size_t)c * n_tensors * 8, seeds[c], idx[c], codes[c], norm[c],
-                         tiles ? tiles[c] : nullptr, nullptr};
-  return launch_topk_batch(proto, ents, extra, n, k, levels, counter, ws, ws_bytes, as_stream(stream), who);
+                         tiles ? tiles[c] : nullptr, nullptr, counters ? counters[c] : counter,
+                         counts ? reinterpret_cast<unsigned long long*>(counts[c]) : nullptr};
+  return launch_topk_batch(proto, ents, extra, n, k, levels, ws, ws_bytes, as_stream(stream), who);
+}
+}  // namespace
+
+extern "C" {
+
+int flc_stacked_encode_delta_batch(const float* const* local, const float* const* global, const int64_t* sizes,
+                                   int n_tensors, int n_clients, int64_t k, int levels, const uint64_t* seeds,
+                                   uint64_t counter, int32_t* const* idx, uint8_t* const* codes, float* const* norm,
+                                   uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream) {
+  return stacked_encode_delta_batch("flc_stacked_encode_delta_batch", local, global, sizes, n_tensors, n_clients, k,
+                                    levels, seeds, nullptr, counter, idx, codes, norm, tiles, nullptr, ws, ws_bytes,
+                                    stream);
+}
+
+int flc_stacked_encode_delta_round(const float* const* local, const float* const* global, const int64_t* sizes,
+                                   int n_tensors, int n_clients, int64_t k, int levels, const uint64_t* seeds,
+                                   const uint64_t* counters, int32_t* const* idx, uint8_t* const* codes,
+                                   float* const* norm, uint32_t* const* tiles, int64_t* const* counts, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  if (!counters) return fail(FLC_EINVAL, "flc_stacked_encode_delta_round: null counters");
+  return stacked_encode_delta_batch("flc_stacked_encode_delta_round", local, global, sizes, n_tensors, n_clients, k,
+                                    levels, seeds, counters, 0, idx, codes, norm, tiles, counts, ws, ws_bytes, stream);
 }
 
 // the pinned table ring's bookkeeping on its own (no device): ops are triples (kind, slot, stream id); kind 0 stages

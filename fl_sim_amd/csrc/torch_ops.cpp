@@ -137,6 +137,53 @@ at::Tensor stacked_encode_batch_wire(at::TensorList xs_, int64_t k, int64_t leve
   return recs;
 }
 
+// a round's packed wire records with one Philox (seed, counter) per client, and the send counts the encode makes
+// (flc_stacked_encode_round): row c equals stacked_encode_wire(xs[c], k, levels, seeds[c], counters[c]), counts[c] the
+// record's kept entries with a nonzero (or NaN) value
+std::tuple<at::Tensor, at::Tensor> stacked_encode_round_wire(at::TensorList xs_, int64_t k, int64_t levels,
+                                                             at::IntArrayRef seeds, at::IntArrayRef counters) {
+  TORCH_CHECK(!xs_.empty(), "flcodec: stacked_encode_round_wire needs at least one client");
+  TORCH_CHECK(seeds.size() == xs_.size() && counters.size() == xs_.size(),
+              "flcodec: one seed and one counter per client");
+  std::vector<at::Tensor> xs;
+  for (const auto& t : xs_) xs.push_back(dev_f32(t, "xs").reshape({-1}));
+  c10::DeviceGuard g(xs[0].device());
+  const int64_t n = xs[0].numel();
+  const int C = (int)xs.size();
+  for (const auto& t : xs)
+    TORCH_CHECK(t.numel() == n && t.device() == xs[0].device(), "flcodec: clients of one size on one device");
+  int64_t off[4];
+  const size_t stride = flc_stacked_wire_layout(n, k, off);
+  TORCH_CHECK(stride > 0, "flcodec: bad wire shape n=", n, ", k=", k);
+  at::Tensor recs = at::empty({(int64_t)C, (int64_t)stride}, xs[0].options().dtype(at::kByte));
+  at::Tensor counts = at::empty({(int64_t)C}, xs[0].options().dtype(at::kLong));
+  uint8_t* r0 = recs.data_ptr<uint8_t>();
+  std::vector<const float*> xp;
+  std::vector<uint64_t> sd, ct;
+  std::vector<int32_t*> ip;
+  std::vector<uint8_t*> cp;
+  std::vector<float*> np_;
+  std::vector<uint32_t*> tp;
+  std::vector<int64_t*> np64;
+  for (int c = 0; c < C; ++c) {
+    uint8_t* r = r0 + (size_t)c * stride;
+    xp.push_back(xs[c].data_ptr<float>());
+    sd.push_back((uint64_t)seeds[c]);
+    ct.push_back((uint64_t)counters[c]);
+    ip.push_back(reinterpret_cast<int32_t*>(r + off[1]));
+    cp.push_back(r + off[2]);
+    np_.push_back(reinterpret_cast<float*>(r + off[0]));
+    tp.push_back(reinterpret_cast<uint32_t*>(r + off[3]));
+    np64.push_back(counts.data_ptr<int64_t>() + c);
+  }
+  at::Tensor ws = workspace(xs[0], flc_stacked_encode_batch_workspace_size(n, k, C), kWsTopkBatch);
+  check(flc_stacked_encode_round(xp.data(), C, n, k, (int)levels, sd.data(), ct.data(), ip.data(), cp.data(),
+                                 np_.data(), tp.data(), np64.data(), ws.data_ptr(), (size_t)ws.numel(),
+                                 stream_of(xs[0])),
+        "stacked_encode_round_wire");
+  return {recs, counts};
+}
+
 at::Tensor stacked_encode_wire(const at::Tensor& x_, int64_t k, int64_t levels, int64_t seed, int64_t counter) {
   at::Tensor x = dev_f32(x_, "x").reshape({-1});
   c10::DeviceGuard g(x.device());
@@ -578,6 +625,13 @@ at::Tensor stacked_encode_batch_wire_meta(at::TensorList xs, int64_t k, int64_t,
   return at::empty({(int64_t)xs.size(), (int64_t)flc_stacked_wire_layout(xs[0].numel(), k, nullptr)},
                    xs[0].options().dtype(at::kByte));
 }
+std::tuple<at::Tensor, at::Tensor> stacked_encode_round_wire_meta(at::TensorList xs, int64_t k, int64_t,
+                                                                  at::IntArrayRef, at::IntArrayRef) {
+  TORCH_CHECK(!xs.empty(), "flcodec: stacked_encode_round_wire needs at least one client");
+  return {at::empty({(int64_t)xs.size(), (int64_t)flc_stacked_wire_layout(xs[0].numel(), k, nullptr)},
+                    xs[0].options().dtype(at::kByte)),
+          at::empty({(int64_t)xs.size()}, xs[0].options().dtype(at::kLong))};
+}
 at::Tensor stacked_encode_wire_meta(const at::Tensor& x, int64_t k, int64_t, int64_t, int64_t) {
   return at::empty({(int64_t)flc_stacked_wire_layout(x.numel(), k, nullptr)}, x.options().dtype(at::kByte));
 }
@@ -644,6 +698,8 @@ TORCH_LIBRARY(flcodec, m) {
   m.def("adaptive_random(Tensor x, float u) -> (Tensor out, Tensor index, Tensor status)");
   m.def("stacked_encode_wire(Tensor x, int k, int levels=127, int seed=0, int counter=0) -> Tensor");
   m.def("stacked_encode_batch_wire(Tensor[] xs, int k, int levels, int[] seeds, int counter=0) -> Tensor");
+  m.def("stacked_encode_round_wire(Tensor[] xs, int k, int levels, int[] seeds, int[] counters) -> "
+        "(Tensor records, Tensor counts)");
   m.def("stacked_fold_wires(Tensor wires, int[] slots, float[] weights, int n, int k, int levels=127, "
         "Tensor? out=None, bool accumulate=False) -> Tensor");
 }
@@ -669,6 +725,7 @@ TORCH_LIBRARY_IMPL(flcodec, CUDA, m) {
   m.impl("adaptive_random", &adaptive_random);
   m.impl("stacked_encode_wire", &stacked_encode_wire);
   m.impl("stacked_encode_batch_wire", &stacked_encode_batch_wire);
+  m.impl("stacked_encode_round_wire", &stacked_encode_round_wire);
   m.impl("stacked_fold_wires", &stacked_fold_wires);
 }
 
@@ -688,5 +745,6 @@ TORCH_LIBRARY_IMPL(flcodec, Meta, m) {
   m.impl("adaptive_random", &adaptive_random_meta);
   m.impl("stacked_encode_wire", &stacked_encode_wire_meta);
   m.impl("stacked_encode_batch_wire", &stacked_encode_batch_wire_meta);
+  m.impl("stacked_encode_round_wire", &stacked_encode_round_wire_meta);
   m.impl("stacked_fold_wires", &stacked_fold_wires_meta);
 }

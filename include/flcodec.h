@@ -317,6 +317,27 @@ int flc_stacked_encode_delta_batch(const float* const* local, const float* const
                                    uint64_t counter, int32_t* const* idx, uint8_t* const* codes, float* const* norm,
                                    uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream);
 
+/* a round's messages in one batched encode, each with its own Philox (seed, counter) — sampled clients, whose
+ * compressors have advanced differently — and the send counts made by the encode itself: client c's packet is
+ * bit-identical to flc_stacked_encode_tiled(xs[c], n, k, levels, seeds[c], counters[c], ...) (the delta form: to
+ * flc_stacked_encode_delta of client c's tensors), and counts[c] (counts may be NULL: no counts; else a HOST array
+ * of n_clients device pointers, none NULL) receives what flc_count_nonzero_at_batch would write for the packet: one
+ * device int64, the kept entries with !(value == 0) (a kept NaN counts), zeroed and added to in the stream by the
+ * encode's own launches.  counters is a HOST array of n_clients entries (NULL: FLC_EINVAL).  Everything else as in
+ * flc_stacked_encode_batch / flc_stacked_encode_delta_batch, which are the all-counters-equal, no-count case of the
+ * same code; the workspace is flc_stacked_encode_batch_workspace_size(n, k, n_clients) for the flat form and
+ * flc_stacked_encode_delta_batch_workspace_size(n, k, n_clients, n_tensors) for the delta form.  The flat form may
+ * be captured into a graph (its table then travels in kernel arguments). */
+int flc_stacked_encode_round(const float* const* xs, int n_clients, int64_t n, int64_t k, int levels,
+                             const uint64_t* seeds, const uint64_t* counters, int32_t* const* idx,
+                             uint8_t* const* codes, float* const* norm, uint32_t* const* tiles, int64_t* const* counts,
+                             void* ws, size_t ws_bytes, void* stream);
+int flc_stacked_encode_delta_round(const float* const* local, const float* const* global, const int64_t* sizes,
+                                   int n_tensors, int n_clients, int64_t k, int levels, const uint64_t* seeds,
+                                   const uint64_t* counters, int32_t* const* idx, uint8_t* const* codes,
+                                   float* const* norm, uint32_t* const* tiles, int64_t* const* counts, void* ws,
+                                   size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ other compressors
  * identical (compressors.py:273-275): out = +x;  lazy (276-283): out = x / p (fp32 division);
  * rand-k (284-292): out = 0, out[idx[j]] = scale * x[idx[j]] (idx in any order, unique). */
