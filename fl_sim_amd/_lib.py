@@ -186,6 +186,8 @@ SIGNATURES = {
                                c_int, c_double, c_double, c_double, c_void_p]),
     "flc_avg_and_gradients": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                       c_int, c_float, c_void_p]),
+    "flc_avg_and_gradient_records": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                             c_int64, c_int64, c_int, c_void_p, c_int, c_float, c_void_p]),
     "flc_model_fold_server": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                       c_int, c_float, c_double, c_void_p]),
     "flc_delta_flatten": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),

@@ -166,13 +166,92 @@ def _gradients_on(dev: torch.device, messages: Sequence[Mapping]) -> List[torch.
     return gs
 
 
+def _flat_views(like: Sequence[torch.Tensor], **kw):
+    """One flat fp32 buffer and its per-tensor views shaped as ``like``."""
+    flat = torch.empty(max(sum(p.numel() for p in like), 1), dtype=torch.float32, **kw)
+    views, off = [], 0
+    for p in like:
+        views.append(flat[off:off + p.numel()].view(p.shape))
+        off += p.numel()
+    return flat, views
+
+
+def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs, wg: Sequence[float],
+                  wp: Optional[Sequence[float]] = None, inertia: float = 0.0) -> Optional[List[torch.Tensor]]:
+    """A round whose ``gradients`` are stacked records (``recs``: compressed.stacked_round(messages, "gradients")):
+    every record decoded and folded into one flat gradient buffer and, with ``wp``, the dense ``parameters`` folded
+    into the model in the same pass (flc_avg_and_gradient_records); the records are never decoded densely.  Sets
+    ``.grad`` of every parameter and returns the gradients; None (nothing launched, nothing changed) when the model
+    is not one the launch takes — the caller's dense path follows.  A host-resident model is staged: the records (and
+    the messages' parameters) in, the parameters out, the gradients out in one copy."""
+    n = len(messages)
+    psrc = [m["parameters"] for m in messages] if wp is not None else None
+    if hoststage.is_host(mps):
+        if not all(isinstance(p, torch.Tensor) and p.is_cpu and p.dtype is torch.float32 for p in mps):
+            return None
+        rmsgs = [[d.record] for d in recs]
+        host = None
+        if wp is not None:
+            with hoststage.staged([mps], [True], [True], psrc + rmsgs) as ((dps,), dm):
+                flat, dg = _flat_views(dps, device=dps[0].device)
+                if compressed.fold_gradient_records(recs, wg, dg, dps, dm[:n], wp, inertia,
+                                                    records=[r[0] for r in dm[n:]]):
+                    host = torch.empty(flat.numel(), dtype=flat.dtype, pin_memory=True)
+                    host.copy_(flat, non_blocking=True)  # one D2H copy, drained by the staging's synchronisation
+        else:
+            dev = hoststage._device_for(rmsgs)
+            with torch.cuda.device(dev):
+                flat, dg = _flat_views(mps, device=dev)
+                if compressed.fold_gradient_records(recs, wg, dg):
+                    host = torch.empty(flat.numel(), dtype=flat.dtype, pin_memory=True)
+                    host.copy_(flat, non_blocking=True)
+                    torch.cuda.current_stream(dev).synchronize()
+        if host is None:
+            return None
+        grads, off = [], 0
+        for p in mps:
+            grads.append(host[off:off + p.numel()].view(p.shape))
+            off += p.numel()
+    else:
+        fast = codec._pygrecs()
+        if fast is not None and mps and isinstance(mps[0], torch.Tensor) and mps[0].is_cuda:
+            # one C call: every tensor and record checked in place, the fold, the gradients' buffer and views, and every
+            # parameter's `.grad`; a TypeError (a tensor the launch does not take, or messages elsewhere) leaves
+            # everything untouched
+            d0 = recs[0]
+            try:
+                return fast(mps, messages if wp is not None else None, [d.record for d in recs], wp, wg, d0.n, d0.k,
+                            d0.levels, float(inertia), True)[0]
+            except TypeError:
+                pass
+        ps = _params(mps)
+        if not ps or not all(isinstance(p, torch.Tensor) and p.is_cuda and p.device == ps[0].device for p in ps):
+            return None
+        with torch.cuda.device(ps[0].device):
+            _, grads = _flat_views(ps, device=ps[0].device)
+            if not compressed.fold_gradient_records(recs, wg, grads, ps if wp is not None else None, psrc, wp, inertia):
+                return None
+    for mp, g in zip(mps, grads):
+        if isinstance(mp, torch.Tensor):
+            mp.grad = g
+    return grads
+
+
 def update_gradients(model_params: Sequence[torch.Tensor], messages: Sequence[Mapping]) -> Optional[List[torch.Tensor]]:
     """nodes.py:1165-1180: sets ``.grad`` of each model parameter to the sample-weighted gradient sum, on the model's
-    device (a host-resident model gets host gradients, as the reference's ``.to(self.device)`` gives)."""
+    device (a host-resident model gets host gradients, as the reference's ``.to(self.device)`` gives).  A round whose
+    gradients are stacked records is folded from the records (flc_avg_and_gradient_records, the parameters untouched)."""
     if len(messages) == 0:
         return None
     assert all(["gradients" in m for m in messages]), "some clients have not sent gradients yet"
     model_params = list(model_params)
+    recs = (compressed.stacked_round(messages, key="gradients")
+            if isinstance(messages[0]["gradients"], compressed.CompressedDelta) else None)
+    if recs is not None:
+        total_samples = sum([m["train_samples"] for m in messages])
+        r = _record_round(model_params, messages, recs, [m["train_samples"] / total_samples for m in messages])
+        if r is not None:
+            return r
     if hoststage.is_host(model_params):
         dev = hoststage._device_for([m["gradients"] for m in messages])
         with torch.cuda.device(dev):
@@ -254,7 +333,9 @@ def avg_parameters_and_gradients(model_params: Sequence[torch.Tensor], messages:
     in ONE launch (flc_avg_and_gradients) — the update of the variance-reduced servers (fedprox/_fedprox.py:163-167,
     fedpd/_fedpd.py:197-202, proxskip/_proxskip.py:212-216, pfedmac/_pfedmac.py:158-162).  Bit-identical to the two
     calls; a host-resident model is staged once (its messages and parameters in; the parameters and, in one copy, the
-    gradients out).  Sets ``.grad`` of each parameter as update_gradients does and returns the gradients."""
+    gradients out).  Sets ``.grad`` of each parameter as update_gradients does and returns the gradients.  A round
+    whose ``gradients`` are stacked records (compressed.CompressedGradientsClientMixin) is folded from the records in
+    the same single pass (flc_avg_and_gradient_records); a mixed or dense round takes the dense path."""
     assert 0.0 <= inertia < 1.0, "`inertia` should be in [0, 1)"
     if len(messages) == 0:
         return None
@@ -264,6 +345,12 @@ def avg_parameters_and_gradients(model_params: Sequence[torch.Tensor], messages:
     wp = [(m["train_samples"] / total if size_aware else 1 / len(messages)) * (1 - inertia) for m in messages]
     wg = [m["train_samples"] / total for m in messages]
     n = len(messages)
+    if isinstance(messages[0]["gradients"], compressed.CompressedDelta):
+        recs = compressed.stacked_round(messages, key="gradients")
+        if recs is not None:  # compressed gradients: the records folded beside the dense parameters, in the same pass
+            r = _record_round(mps, messages, recs, wg, wp, inertia)
+            if r is not None:
+                return r
     if hoststage.is_host(mps):
         with hoststage.staged([mps], [True], [True], [m["parameters"] for m in messages]
                               + [m["gradients"] for m in messages]) as ((dps,), dm):
@@ -612,7 +699,10 @@ class VRUpdateMixin:
         mps = list(self.model.parameters())
         if hoststage.is_host(mps):
             keys = ["parameters"] + (["gradients"] if self.config.vr else [])
-            _adopt([mps], [m[k] for m in self._received_messages for k in keys])
+            # (compressed gradients are placed by their record or flat vector: iterating them would decode them)
+            _adopt([mps], [[m[k].record if m[k].kind == "stacked" else m[k].flat()]
+                           if isinstance(m[k], compressed.CompressedDelta) else m[k]
+                           for m in self._received_messages for k in keys])
             mps = list(self.model.parameters())  # (the adopted tensors)
         if self.config.vr:
             avg_parameters_and_gradients(mps, self._received_messages, inertia=inertia)

@@ -892,6 +892,22 @@ def _pyrecs():
     return _PYRECS[0]
 
 
+_PYGRECS: list = []
+
+
+def _pygrecs():
+    """fl_sim_amd._flcfold.avg_and_gradient_records (flc_avg_and_gradient_records on Python lists, one C call) when
+    built, else None."""
+    if not _PYGRECS:
+        try:
+            from . import _flcfold
+
+            _PYGRECS.append(_flcfold.avg_and_gradient_records)
+        except (ImportError, AttributeError):
+            _PYGRECS.append(None)
+    return _PYGRECS[0]
+
+
 def _pyflat():
     """fl_sim_amd._flcfold.delta_flat (a new flat delta, flc_delta_flatten, one C call) when built, else None."""
     if not _PYFLAT:

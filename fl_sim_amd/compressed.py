@@ -26,6 +26,17 @@ What runs here instead:
   v) read and written once; bit-identical to decoding each record and running the reference's update.
 
 The compressors' send statistics advance as ``compressVector`` advances them (``compressors.py:406-408``), per stage.
+
+The variance-reduced algorithms (FedProx, FedPD, ProxSkip, pFedMac with ``config.vr``) send ``parameters`` and
+``gradients`` (fedprox/_fedprox.py:208-217, fedpd/_fedpd.py:252-275, proxskip/_proxskip.py:265-276,
+pfedmac/_pfedmac.py:203-212).  Their call site compresses the gradients only — the stochastic half of the message, and
+the one whose server fold starts from +0 (``tests/golden/gen_golden_vr_codec.py`` fixes the meaning the same way):
+
+* :class:`CompressedGradientsClientMixin` — runs the client's own ``communicate`` and sends the ``gradients`` of the
+  message it appended through :func:`compress_tensors` (everything :func:`compress_delta` does, nothing subtracted);
+* ``aggregation.avg_parameters_and_gradients`` / ``update_gradients`` (and the ``VRUpdateMixin`` family) recognise a
+  round of stacked records and run :func:`fold_gradient_records`: every record decoded and folded into the gradients
+  and the dense parameters folded into the model in one ``flc_avg_and_gradient_records`` pass.
 """
 
 from __future__ import annotations
@@ -180,7 +191,25 @@ def compress_delta(local: Sequence[torch.Tensor], cached: Sequence[torch.Tensor]
                    compressors: Sequence[Compressor]) -> CompressedDelta:
     """The client's compressed delta ``compressors(cat(local − cached))`` (see the module docstring); every compressor's
     RNG stream and send statistics advance as its own ``compressVector`` call would advance them."""
-    local = list(local)
+    return _compress(list(local), cached, compressors)
+
+
+def compress_tensors(tensors: Sequence[torch.Tensor], compressors: Sequence[Compressor]) -> CompressedDelta:
+    """``compressors(cat(tensors))`` — :func:`compress_delta` with nothing subtracted (a client's gradient list): the
+    stacked pipeline gives a packed record, any other compressor the decoded flat vector; the compressors' RNG streams
+    and send statistics advance alike, and in philox mode a deferred message joins the round's batched encode with the
+    flat vector as its snapshot."""
+    return _compress(list(tensors), None, compressors)
+
+
+def _flatten(ts: Sequence[torch.Tensor], dev: torch.device) -> torch.Tensor:
+    """cat(ts) as a new flat fp32 vector on ``dev`` (a snapshot: the tensors may change before a deferred encode)."""
+    return torch.cat([t.reshape(-1) for t in _fp32_on(ts, dev)])
+
+
+def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
+              compressors: Sequence[Compressor]) -> CompressedDelta:
+    """``compressors(cat(local − cached))``, or (``cached`` None) ``compressors(cat(local))``."""
     dev = local[0].device if local[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
     shapes = [t.shape for t in local]
     n = sum(t.numel() for t in local)
@@ -195,11 +224,16 @@ def compress_delta(local: Sequence[torch.Tensor], cached: Sequence[torch.Tensor]
             r = _deferred(local, cached, shapes, n, pipe[0], pipe[1], compressors[0], compressors[1], dev, seed_ctr)
             if r is not None:
                 return r
-        r = _stacked_fast(local, cached, shapes, n, pipe[0], pipe[1], compressors[0], compressors[1], dev, seed_ctr)
+        r = None if cached is None else _stacked_fast(local, cached, shapes, n, pipe[0], pipe[1], compressors[0],
+                                                      compressors[1], dev, seed_ctr)
         if r is not None:
             return r
     out = None
-    if pipe is None or not 0 < pipe[0] < n:
+    if cached is None:
+        out = _flatten(local, dev)
+        if pipe is not None and 0 < pipe[0] < n:
+            return _stacked(out, None, shapes, n, pipe[0], pipe[1], compressors[0], compressors[1], dev, seed_ctr)
+    elif pipe is None or not 0 < pipe[0] < n:
         snap = codec._pyflat()
         if snap is not None:
             try:  # the flat delta in one C call (the tensors as they are: contiguous fp32 on one device)
@@ -312,10 +346,13 @@ Compressor._before_read = staticmethod(_run_pending)
 def _deferred(local, cached, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compressor, dev,
               seed_ctr) -> Optional[CompressedDelta]:
     snap = codec._pyflat()
-    try:
-        flat = snap(local, cached) if snap is not None else codec.delta_flatten(local, cached)
-    except TypeError:  # (host-resident, non-contiguous or non-fp32 tensors: converted first)
-        flat = codec.delta_flatten(_fp32_on(local, dev), _fp32_on(cached, dev))
+    if cached is None:  # (nothing subtracted: the flat vector itself)
+        flat = _flatten(local, dev)
+    else:
+        try:
+            flat = snap(local, cached) if snap is not None else codec.delta_flatten(local, cached)
+        except TypeError:  # (host-resident, non-contiguous or non-fp32 tensors: converted first)
+            flat = codec.delta_flatten(_fp32_on(local, dev), _fp32_on(cached, dev))
     if flat.device != dev:
         return None
     st = torch.cuda.current_stream(dev)
@@ -364,6 +401,7 @@ def _identical(nc) -> bool:
 
 def _stacked(ls, gs, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compressor, dev,
              seed_ctr=None) -> CompressedDelta:
+    """The stacked message of ``cat(ls − gs)``, or (``gs`` None) of the flat vector ``ls``."""
     stride, _ = codec.stacked_wire_layout(n, K)
     rec = torch.empty(stride, dtype=torch.uint8, device=dev)
     pk = codec.wire_packet(rec, n, K, s)
@@ -371,18 +409,24 @@ def _stacked(ls, gs, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compres
     seed, ctr = seed_ctr if seed_ctr is not None else sd.philox.next()
     if sd.rng_mode == "philox":
         # the delta formed inside the encoder's read; the dithering stage's nonzero count stays on the device
-        codec.stacked_encode_delta(ls, gs, K, s, seed, ctr, wire=rec)
-        cnt = sd._count_slot(dev)
-        _lib.call("flc_delta_count_nonzero_at", _ptrs(ls), _ptrs(gs),
-                  (ctypes.c_int64 * len(ls))(*[t.numel() for t in ls]), len(ls), pk.idx.data_ptr(), K,
-                  cnt.data_ptr(), codec._stream(dev))
+        if gs is None:
+            codec.stacked_encode(ls, K, s, seed, ctr, wire=rec)
+            cnt = sd._count_slot(dev)
+            _lib.call("flc_count_nonzero_at_batch", _ptrs([ls]), _ptrs([pk.idx]), 1, n, K, _ptrs([cnt]),
+                      codec._stream(dev))
+        else:
+            codec.stacked_encode_delta(ls, gs, K, s, seed, ctr, wire=rec)
+            cnt = sd._count_slot(dev)
+            _lib.call("flc_delta_count_nonzero_at", _ptrs(ls), _ptrs(gs),
+                      (ctypes.c_int64 * len(ls))(*[t.numel() for t in ls]), len(ls), pk.idx.data_ptr(), K,
+                      cnt.data_ptr(), codec._stream(dev))
         tk._finish(n, tk.K)
         base = _norm_stage_send(sd, pk.norm)
         sd._finish_pending(n, cnt, base, per)
         return CompressedDelta(shapes, dev, n, record=rec, k=K, levels=s)
     # compat: TopK (compressors.py:293-296), then standard dithering of the K-sparse vector (327-365) whose nonzero
     # elements, in index order, are the kept values: one random.random() per consuming kept value
-    x = codec.delta_flatten(ls, gs)
+    x = ls if gs is None else codec.delta_flatten(ls, gs)
     val = torch.empty(K, dtype=torch.float32, device=dev)
     ws = codec.workspace(dev, codec._ws_size(dev, "flc_topk_workspace_size", n, K), "topk")
     st = codec._stream(dev)
@@ -458,10 +502,50 @@ def fold_records(deltas: Sequence[CompressedDelta], weights: Sequence[float], de
     return True
 
 
-def _compressors_of(node) -> List[Compressor]:
-    cs = getattr(node, "compressors", None)
+def fold_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequence[float], grads: Sequence[torch.Tensor],
+                          params: Optional[Sequence[torch.Tensor]] = None,
+                          param_srcs: Optional[Sequence[Sequence[torch.Tensor]]] = None,
+                          w_params: Optional[Sequence[float]] = None, inertia: float = 0.0,
+                          records: Optional[Sequence[torch.Tensor]] = None) -> bool:
+    """``grads = Σ_m w_grads[m]·decode(record_m)`` from +0 in message order and, with ``params``,
+    ``θ = θ·inertia + Σ_m w_params[m]·param_srcs[m]`` — one ``flc_avg_and_gradient_records`` pass (``params`` None:
+    ``update_gradients`` alone).  ``records``: the messages' records where they were staged (default: the deltas' own).
+    False (nothing launched) when a tensor is not a contiguous fp32 tensor of the gradients' HIP device holding the
+    records' element count (the caller then takes the dense path); records and parameter sources elsewhere are moved."""
+    gs = list(grads)
+    ok = lambda t, dev: (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev  # noqa: E731
+                         and t.dtype is torch.float32 and t.is_contiguous())
+    if not gs or not isinstance(gs[0], torch.Tensor) or not gs[0].is_cuda:
+        return False
+    dev = gs[0].device
+    d0 = deltas[0]
+    if not all(ok(g, dev) for g in gs) or sum(g.numel() for g in gs) != d0.n:
+        return False
+    T, m = len(gs), len(deltas)
+    ps = srcs = None
+    if params is not None:
+        ps = [p.data if isinstance(p, torch.nn.Parameter) else p for p in params]
+        if len(ps) != T or not all(ok(p, dev) and p.numel() == g.numel() for p, g in zip(ps, gs)):
+            return False
+        srcs = [[t.detach() if t.device == dev else t.detach().to(dev) for t in r] for r in param_srcs]
+        if len(srcs) != m or any(len(r) != T or not all(ok(t, dev) and t.numel() == g.numel() for t, g in zip(r, gs))
+                                 for r in srcs):
+            return False
+    recs = [d.record for d in deltas] if records is None else list(records)
+    recs = [r if r.device == dev else r.to(dev) for r in recs]
+    fl = lambda ws: (ctypes.c_float * m)(*[float(w) for w in ws])  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.call("flc_avg_and_gradient_records", _ptrs(ps) if ps is not None else None, _ptrs(gs),
+                  _ptrs([t for r in srcs for t in r]) if srcs is not None else None, _ptrs(recs),
+                  fl(w_params) if ps is not None else None, fl(w_grads), m, d0.n, d0.k, d0.levels,
+                  (ctypes.c_int64 * T)(*[g.numel() for g in gs]), T, float(inertia), codec._stream(dev))
+    return True
+
+
+def _compressors_of(node, name: str = "compressors") -> List[Compressor]:
+    cs = getattr(node, name, None)
     if cs is None:
-        cs = getattr(getattr(node, "config", None), "compressors", None)
+        cs = getattr(getattr(node, "config", None), name, None)
     if cs is None:
         return []
     return [cs] if isinstance(cs, Compressor) else list(cs)
@@ -487,3 +571,36 @@ class CompressedFedOptClientMixin:
                 }
             )
         )
+
+
+def compress_message_gradients(message, compressors: Sequence[Compressor]) -> None:
+    """Replace ``message["gradients"]`` (a list of tensors) with the :class:`CompressedDelta` made from them
+    (:func:`compress_tensors`); no compressors, no gradients or gradients already compressed: the message as it is."""
+    gs = message.get("gradients")
+    if not compressors or gs is None or isinstance(gs, CompressedDelta) or len(gs) == 0:
+        return
+    message["gradients"] = compress_tensors(list(gs), compressors)
+
+
+class CompressedGradientsClientMixin:
+    """Mix in before the reference's ``FedProxClient``, ``FedPDClient``, ``ProxSkipClient`` or ``pFedMacClient``
+    (``class C(CompressedGradientsClientMixin, FedProxClient)``): the client's own ``communicate``
+    (fedprox/_fedprox.py:208-217, fedpd/_fedpd.py:252-275, proxskip/_proxskip.py:265-276, pfedmac/_pfedmac.py:203-212)
+    runs as it is, and the ``gradients`` of every message it appended (``config.vr``) go through the client's
+    compressors (``self.gradient_compressors``, or ``self.config.gradient_compressors``: one
+    :class:`~fl_sim_amd.compressors.Compressor` or a sequence applied in order; none leaves the message unchanged).
+    A client that skips the round appends nothing, so nothing is compressed and no compressor advances; ``parameters``
+    stay as the reference sends them.  The server side is :class:`~fl_sim_amd.aggregation.VRUpdateMixin`, which folds a
+    round of stacked records and the dense parameters in one pass (or any reference server: the compressed gradients
+    read as a list of tensors)."""
+
+    def communicate(self, target) -> None:
+        received = target._received_messages
+        before = len(received)
+        super().communicate(target)
+        cs = _compressors_of(self, "gradient_compressors")
+        if not cs:
+            return
+        for m in target._received_messages[before if target._received_messages is received else 0:]:
+            if isinstance(m, dict) and "gradients" in m:
+                compress_message_gradients(m, cs)

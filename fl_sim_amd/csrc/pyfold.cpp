@@ -2,7 +2,8 @@
 // Python lists of tensors, for the per-round host path of FedOptServer.update / avg_parameters / add_parameters /
 // update_gradients (_fedopt.py:196-240, nodes.py:1116-1180); `server_fold`, the same for FedDyn's and pFedMe's server
 // updates (flc_model_fold_server); `avg_and_gradients`, the variance-reduced servers' avg_parameters + update_gradients
-// (flc_avg_and_gradients); `stacked_delta_record`, a client's compressed message (flc_stacked_encode_delta into a wire
+// (flc_avg_and_gradients), and `avg_and_gradient_records`, the same over compressed gradients
+// (flc_avg_and_gradient_records); `stacked_delta_record`, a client's compressed message (flc_stacked_encode_delta into a wire
 // record + flc_delta_count_nonzero_at).
 //
 // At configs[0] (cnn_femmist_tiny: 8 tensors, 10 clients) the kernel takes ~9 us, but going through the dispatcher
@@ -743,6 +744,139 @@ PyObject* fold_records(PyObject*, PyObject* args) {
   return done((Py_INCREF(Py_None), Py_None));
 }
 
+// avg_and_gradient_records(params, msgs, records, w_params, w_grads, n, k, levels, inertia, set_grad): a
+// variance-reduced round whose gradients are stacked records (flc_avg_and_gradient_records) on Python lists.  `params`
+// folded in place from every message's "parameters" (`msgs` None: left untouched — update_gradients alone, `w_params`
+// unused); the gradients decoded and folded into one new flat fp32 buffer on the model's device, returned as (list of
+// per-parameter views, flat buffer); with `set_grad` each parameter's `.grad` is set to its view.  TypeError (nothing
+// allocated or launched) when a tensor is not what the pass takes, as fold_records and avg_and_gradients raise it.
+PyObject* avg_and_gradient_records(PyObject*, PyObject* args) {
+  PyObject *params, *msgs, *recs, *wpar, *wgrd;
+  long long n, k;
+  int levels, set_grad = 0;
+  double inertia;
+  if (!PyArg_ParseTuple(args, "OOOOOLLid|p", &params, &msgs, &recs, &wpar, &wgrd, &n, &k, &levels, &inertia, &set_grad))
+    return nullptr;
+  std::vector<PyObject*> keep;
+  auto done = [&](PyObject* r) {
+    for (PyObject* o : keep) Py_XDECREF(o);
+    return r;
+  };
+  const bool p_on = msgs != Py_None;
+  PyObject* seqs[5] = {params, recs, wgrd, p_on ? msgs : recs, p_on ? wpar : wgrd};
+  PyObject* f[5];
+  for (int i = 0; i < 5; ++i) {
+    f[i] = PySequence_Fast(seqs[i], "avg_and_gradient_records takes sequences");
+    if (!f[i]) return done(nullptr);
+    keep.push_back(f[i]);
+  }
+  const Py_ssize_t nt = PySequence_Fast_GET_SIZE(f[0]), ns = PySequence_Fast_GET_SIZE(f[1]);
+  if (PySequence_Fast_GET_SIZE(f[2]) != ns || PySequence_Fast_GET_SIZE(f[3]) != ns || PySequence_Fast_GET_SIZE(f[4]) != ns)
+    return done(value_error("one record, one message and one weight of each kind per message"));
+  if (ns < 1 || nt < 1) return done(type_error("avg_and_gradient_records needs records and model tensors"));
+  int dev = -1;
+  std::vector<float*> pp(nt), gp(nt);
+  std::vector<int64_t> sz(nt);
+  std::vector<const at::Tensor*> pt(nt);
+  int64_t total = 0;
+  PyObject** pi = PySequence_Fast_ITEMS(f[0]);
+  for (Py_ssize_t t = 0; t < nt; ++t) {
+    const at::Tensor* a = usable(pi[t], &dev);
+    if (!a) return done(type_error("model tensors must be contiguous fp32 HIP tensors on one device"));
+    pt[t] = a;
+    pp[t] = a->data_ptr<float>();
+    sz[t] = a->numel();
+    total += sz[t];
+  }
+  if (total != n) return done(type_error("the model tensors do not hold the records' element count"));
+  int64_t off4[4];
+  const size_t stride = flc_stacked_wire_layout(n, k, off4);
+  if (stride == 0) return done(value_error("bad wire shape"));
+  std::vector<const void*> rp(ns);
+  std::vector<const float*> ps(p_on ? (size_t)ns * nt : 0);
+  std::vector<float> wp(ns), wg(ns);
+  PyObject** ri = PySequence_Fast_ITEMS(f[1]);
+  PyObject** wgi = PySequence_Fast_ITEMS(f[2]);
+  PyObject** mi = PySequence_Fast_ITEMS(f[3]);
+  PyObject** wpi = PySequence_Fast_ITEMS(f[4]);
+  static PyObject* const key = PyUnicode_InternFromString("parameters");
+  for (Py_ssize_t m = 0; m < ns; ++m) {
+    const at::Tensor* r = usable_as(ri[m], at::kByte, &dev);
+    if (!r || (size_t)r->numel() < stride || reinterpret_cast<uintptr_t>(r->data_ptr()) % 16 != 0)
+      return done(type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the model's device"));
+    rp[m] = r->data_ptr();
+    const double b = PyFloat_AsDouble(wgi[m]);
+    if (b == -1.0 && PyErr_Occurred()) return done(nullptr);
+    wg[m] = (float)b;
+    if (!p_on) continue;
+    const double a = PyFloat_AsDouble(wpi[m]);
+    if (a == -1.0 && PyErr_Occurred()) return done(nullptr);
+    wp[m] = (float)a;
+    PyObject* v = PyObject_GetItem(mi[m], key);
+    if (!v) return done(nullptr);
+    keep.push_back(v);
+    PyObject* fv = PySequence_Fast(v, "a message's parameters are a sequence of tensors");
+    if (!fv) return done(nullptr);
+    keep.push_back(fv);
+    if (PySequence_Fast_GET_SIZE(fv) != nt) return done(type_error("every message has one tensor per model tensor"));
+    PyObject** it = PySequence_Fast_ITEMS(fv);
+    for (Py_ssize_t t = 0; t < nt; ++t) {
+      const at::Tensor* s = usable(it[t], &dev);
+      if (!s || s->numel() != sz[t])
+        return done(type_error("message tensors must be contiguous fp32 HIP tensors of the model's sizes and device"));
+      ps[(size_t)m * nt + t] = s->data_ptr<float>();
+    }
+  }
+  // (every tensor checked: the gradient buffer is allocated now)
+  at::Tensor flat;
+  std::vector<at::Tensor> gv;
+  try {
+    flat = at::empty({total > 0 ? total : 1}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, dev));
+  } catch (const std::exception& e) {
+    PyErr_SetString(PyExc_RuntimeError, e.what());
+    return done(nullptr);
+  }
+  gv.reserve(nt);
+  int64_t off = 0;
+  for (Py_ssize_t t = 0; t < nt; ++t) {
+    gv.push_back(flat.narrow(0, off, sz[t]).view(pt[t]->sizes()));
+    gp[t] = flat.data_ptr<float>() + off;
+    off += sz[t];
+  }
+  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
+  int rc = FLC_OK;
+  Py_BEGIN_ALLOW_THREADS
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  if (cur != dev) (void)hipSetDevice(dev);
+  rc = flc_avg_and_gradient_records(p_on ? pp.data() : nullptr, gp.data(), p_on ? ps.data() : nullptr, rp.data(),
+                                    p_on ? wp.data() : nullptr, wg.data(), (int)ns, n, k, levels, sz.data(), (int)nt,
+                                    (float)inertia, st);
+  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
+  Py_END_ALLOW_THREADS
+  if (rc != FLC_OK) {
+    PyErr_Format(PyExc_RuntimeError, "flc_avg_and_gradient_records failed with status %d: %s", rc, flc_last_error());
+    return done(nullptr);
+  }
+  PyObject* lst = PyList_New(nt);
+  if (!lst) return done(nullptr);
+  for (Py_ssize_t t = 0; t < nt; ++t) {
+    if (set_grad) pt[t]->mutable_grad() = gv[t];  // (update_gradients' `mp.grad = ...`: same device, dtype, sizes)
+    PyObject* w = THPVariable_Wrap(gv[t]);
+    if (!w) {
+      Py_DECREF(lst);
+      return done(nullptr);
+    }
+    PyList_SET_ITEM(lst, t, w);
+  }
+  PyObject* fl = THPVariable_Wrap(flat);
+  if (!fl) {
+    Py_DECREF(lst);
+    return done(nullptr);
+  }
+  return done(Py_BuildValue("(NN)", lst, fl));
+}
+
 void release_storage(void* ctx) { delete static_cast<c10::Storage*>(ctx); }
 
 // alias(host_tensor, device_index) -> tensor on cuda:device_index over the same bytes (see the header)
@@ -783,6 +917,9 @@ PyMethodDef kMethods[] = {
     {"fold_records", fold_records, METH_VARARGS,
      "fold_records(records, weights, n, k, levels, delta, theta, v, beta0, opt, lr, beta2, tau): "
      "flc_fedopt_fold_records on Python lists"},
+    {"avg_and_gradient_records", avg_and_gradient_records, METH_VARARGS,
+     "avg_and_gradient_records(params, msgs, records, w_params, w_grads, n, k, levels, inertia[, set_grad]): "
+     "flc_avg_and_gradient_records on Python lists (messages: mappings with 'parameters', or None)"},
     {"delta_flat", delta_flat, METH_VARARGS,
      "delta_flat(local, global): a new flat fp32 tensor cat(local - global) (flc_delta_flatten) on the tensors' device"},
     {"stacked_records_round", stacked_records_round, METH_VARARGS,

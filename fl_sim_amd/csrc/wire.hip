@@ -23,6 +23,10 @@
 // +0 + -0 = +0).  So the sparse fold records, per element, the last client that wrote it (a byte in LDS) and, before
 // each entry's fma and at the end, replays the skipped clients on a -0 (skip_clients) — the dense chain bit for bit.  Bytes: 4n written (+ 4n read when
 // accumulating) + the wires' 5 B per kept entry and tile pointers.
+//
+// The same kernel with a model as its accumulator (an IO policy): flc_fedopt_fold_records (ModelIO: δ, then the server
+// optimiser's step) and flc_avg_and_gradient_records (PairIO: a variance-reduced round's gradients from records, the
+// dense parameters folded in the same pass).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -192,6 +196,109 @@ struct ModelIO {
                 opt_step<OPT < 0 ? 0 : OPT>(th[o], a, &vi, m.lr, m.beta2, m.omb, m.nomb, m.tau);
                 if (OPT > 0) vv[o] = vi;
               }
+            }
+          }
+        }
+      }
+    }
+  }
+};
+
+// A variance-reduced server's round as the fold's accumulator (flc_avg_and_gradient_records): the records are the
+// messages' compressed gradients, folded into the server's gradient tensors (load: +0, or the stored partial sum of
+// a chained launch; store: the gradient), and in the same pass the tile's slice of the messages' dense parameters is
+// folded into the server's parameters (avg_parameters, nodes.py:1134-1163: θ = θ·inertia first, then
+// fmaf(w_m, p_m, θ) in message order) — pair_fold_kernel's two chains with the gradient's sources read from records.
+// The tensor walk is ModelIO's.
+constexpr int kPairSrc = 16;  // dense parameter sources per launch (kernel-argument budget)
+struct PairTab {
+  float* grad[kRoundT];
+  float* param[kRoundT];
+  const float* src[kPairSrc][kRoundT];
+  int64_t start[kRoundT + 1];
+  float w[kPairSrc];
+  int nt, ns;
+  unsigned gvec;  // bit t: the gradient tensor 16-B aligned and start[t] % 4 == 0
+  unsigned pvec;  // bit t: the parameter and every source of it 16-B aligned and start[t] % 4 == 0
+  int g_on;       // this launch folds records (else the gradients are neither read nor written)
+  int g_acc;      // the gradient chain continues from the stored partial sums
+  int p_on;       // this launch folds parameter sources
+  int p_scale;    // θ·inertia first (the first parameter launch)
+  float inertia;
+};
+struct PairIO {
+  PairTab m;
+  __device__ __forceinline__ int first_tensor(int64_t t0) const {
+    int t = 0;
+    while (t + 1 < m.nt && m.start[t + 1] <= t0) ++t;
+    return t;
+  }
+  __device__ __forceinline__ void load(int64_t t0, int lane, float4 acc[4]) const {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!(m.g_on && m.g_acc)) return;
+    for (int t = first_tensor(t0); t < m.nt && m.start[t] < t0 + FLC_TILE; ++t) {
+      const int64_t s0 = m.start[t], s1 = m.start[t + 1];
+      const float* __restrict__ d = m.grad[t];
+      const bool vec = (m.gvec >> t) & 1u;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t e = t0 + 4 * (int64_t)(lane + u * kWave);
+        if (vec && e >= s0 && e + 4 <= s1) {
+          acc[u] = *reinterpret_cast<const float4*>(d + (e - s0));
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (e + j >= s0 && e + j < s1) comp(acc[u], j) = d[e + j - s0];
+        }
+      }
+    }
+  }
+  __device__ __forceinline__ void store(int64_t t0, int lane, float4 acc[4]) const {
+    for (int t = first_tensor(t0); t < m.nt && m.start[t] < t0 + FLC_TILE; ++t) {
+      const int64_t s0 = m.start[t], s1 = m.start[t + 1];
+      float* __restrict__ d = m.grad[t];
+      float* __restrict__ th = m.param[t];
+      const bool gv = (m.gvec >> t) & 1u, pv = (m.pvec >> t) & 1u;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t e = t0 + 4 * (int64_t)(lane + u * kWave);
+        const bool whole = e >= s0 && e + 4 <= s1;
+        if (m.g_on) {
+          if (gv && whole) {
+            *reinterpret_cast<float4*>(d + (e - s0)) = acc[u];
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (e + j >= s0 && e + j < s1) d[e + j - s0] = comp(acc[u], j);
+          }
+        }
+        if (!m.p_on) continue;
+        if (pv && whole) {
+          const int64_t o = e - s0;
+          float4 sv[kPairSrc];
+#pragma unroll
+          for (int s = 0; s < kPairSrc; ++s)
+            if (s < m.ns) sv[s] = *reinterpret_cast<const float4*>(m.src[s][t] + o);
+          float4 a = *reinterpret_cast<const float4*>(th + o);
+          if (m.p_scale) a = make_float4(a.x * m.inertia, a.y * m.inertia, a.z * m.inertia, a.w * m.inertia);
+#pragma unroll
+          for (int s = 0; s < kPairSrc; ++s) {
+            if (s < m.ns) {
+              const float ws = m.w[s];
+              a = make_float4(fmaf(ws, sv[s].x, a.x), fmaf(ws, sv[s].y, a.y), fmaf(ws, sv[s].z, a.z),
+                              fmaf(ws, sv[s].w, a.w));
+            }
+          }
+          *reinterpret_cast<float4*>(th + o) = a;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (e + j >= s0 && e + j < s1) {
+              const int64_t o = e + j - s0;
+              float a = m.p_scale ? th[o] * m.inertia : th[o];
+              for (int s = 0; s < m.ns; ++s) a = fmaf(m.w[s], m.src[s][t][o], a);
+              th[o] = a;
             }
           }
         }
@@ -527,6 +634,98 @@ int flc_fedopt_fold_records(const void* const* records, const float* weights, in
     }
     c0 += nw;
   } while (c0 < n_records);
+  return FLC_OK;
+}
+
+int flc_avg_and_gradient_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                 const void* const* grad_records, const float* w_params, const float* w_grads,
+                                 int n_src, int64_t n, int64_t k, int levels, const int64_t* sizes, int n_tensors,
+                                 float inertia, void* stream) {
+  const bool p_on = param_srcs != nullptr;
+  if (n_src < 1 || !grad_records || !w_grads || n <= 0 || k < 0 || n_tensors < 1 || !grads || !sizes ||
+      (p_on && (!params || !w_params)))
+    return fail(FLC_EINVAL, "flc_avg_and_gradient_records: bad arguments");
+  if (n >= (1ll << 31) || k >= (1ll << 31))
+    return fail(FLC_EINVAL, "flc_avg_and_gradient_records: n and k must be < 2^31");
+  if (levels < 1 || levels > 127)
+    return fail(FLC_EINVAL, "flc_avg_and_gradient_records: levels must be in [1, 127]");
+  int64_t total = 0;
+  for (int t = 0; t < n_tensors; ++t) {
+    if (sizes[t] < 0) return fail(FLC_EINVAL, "flc_avg_and_gradient_records: negative size for tensor %d", t);
+    if (sizes[t] > 0 && (!grads[t] || (p_on && !params[t])))
+      return fail(FLC_EINVAL, "flc_avg_and_gradient_records: null pointer for tensor %d", t);
+    if (p_on && sizes[t] > 0)
+      for (int m = 0; m < n_src; ++m)
+        if (!param_srcs[(size_t)m * n_tensors + t])
+          return fail(FLC_EINVAL, "flc_avg_and_gradient_records: null source %d of tensor %d", m, t);
+    total += sizes[t];
+  }
+  if (total != n)
+    return fail(FLC_EINVAL, "flc_avg_and_gradient_records: the tensors hold %lld elements, the records %lld",
+                (long long)total, (long long)n);
+  for (int c = 0; c < n_src; ++c)
+    if (!grad_records[c] || !aligned16(grad_records[c]))
+      return fail(FLC_EINVAL, "flc_avg_and_gradient_records: record %d is null or not 16-B aligned", c);
+  size_t need = 0;
+  const WireLayout L = wire_layout(n, k, &need);
+  hipStream_t st = as_stream(stream);
+  const double step = 1.0 / (double)levels;
+  // the gradient chain starts at +0: with finite weights only the kept entries are fma'd (the sparse form, its -0
+  // rule as in flc_stacked_fold_wires); a non-finite weight takes every element through every record's fma
+  bool sparse = true;
+  for (int c = 0; c < n_src; ++c) sparse = sparse && std::isfinite(w_grads[c]);
+  // launch i of the chain folds records [64 i, 64 i + 64) and parameter sources [16 i, 16 i + 16), each chain
+  // continuing from its stored partial result; within it, one launch per group of <= kRoundT tensors
+  const int r_launches = (int)cdiv((int64_t)n_src, (int64_t)kMaxWires);
+  const int p_launches = p_on ? (int)cdiv((int64_t)n_src, (int64_t)kPairSrc) : 0;
+  for (int i = 0; i < std::max(r_launches, p_launches); ++i) {
+    const int c0 = i * kMaxWires, s0 = i * kPairSrc;
+    const int nw = i < r_launches ? std::min(kMaxWires, n_src - c0) : 0;
+    const int ns = i < p_launches ? std::min(kPairSrc, n_src - s0) : 0;
+    FoldArgs a;
+    for (int c = 0; c < kMaxWires; ++c) {
+      a.w[c] = c < nw ? w_grads[c0 + c] : 0.0f;
+      a.rec[c] = static_cast<const uint8_t*>(c < nw ? grad_records[c0 + c] : nullptr);
+    }
+    int64_t off = 0;
+    int t = 0;
+    while (t < n_tensors) {
+      PairIO io{};
+      PairTab& m = io.m;
+      m.ns = ns;
+      m.g_on = nw > 0;
+      m.g_acc = i > 0;
+      m.p_on = ns > 0;
+      m.p_scale = i == 0;
+      m.inertia = inertia;
+      for (int s = 0; s < ns; ++s) m.w[s] = w_params[s0 + s];
+      for (; t < n_tensors && m.nt < kRoundT; ++t) {
+        if (sizes[t] == 0) continue;
+        const int j = m.nt++;
+        m.grad[j] = grads[t];
+        m.param[j] = p_on ? params[t] : nullptr;
+        m.start[j] = off;
+        if (off % 4 == 0 && aligned16(m.grad[j])) m.gvec |= 1u << j;
+        bool pv = off % 4 == 0 && p_on && aligned16(m.param[j]);
+        for (int s = 0; s < ns; ++s) {
+          m.src[s][j] = param_srcs[(size_t)(s0 + s) * n_tensors + t];
+          pv = pv && aligned16(m.src[s][j]);
+        }
+        if (pv) m.pvec |= 1u << j;
+        off += sizes[t];
+      }
+      if (m.nt == 0) break;
+      m.start[m.nt] = off;
+      const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
+      const dim3 grid((unsigned)(tile_hi - tile_lo));
+      if (sparse)
+        FLC_LAUNCH("avg_and_gradient_records", (stacked_fold_wires_kernel<true, PairIO>), grid, dim3(kWave), 0, st, a,
+                   L, nw, levels, step, tile_lo, io, (unsigned)k);
+      else
+        FLC_LAUNCH("avg_and_gradient_records", (stacked_fold_wires_kernel<false, PairIO>), grid, dim3(kWave), 0, st,
+                   a, L, nw, levels, step, tile_lo, io, (unsigned)k);
+    }
+  }
   return FLC_OK;
 }
 

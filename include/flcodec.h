@@ -438,6 +438,26 @@ int flc_model_fold(float* const* dst, const float* const* srcs, const float* wei
 int flc_avg_and_gradients(float* const* params, float* const* grads, const float* const* param_srcs,
                           const float* const* grad_srcs, const float* w_params, const float* w_grads, int n_src,
                           const int64_t* sizes, int n_tensors, float inertia, void* stream);
+/* The same round when every message carries its gradients as a packed stacked record (the codec's call site for the
+ * variance-reduced algorithms, fl_sim_amd/compressed.py: CompressedGradientsClientMixin; replaces
+ * fedprox/_fedprox.py:163-167 and 208-217, fedpd/_fedpd.py:197-202 and 252-275, proxskip/_proxskip.py:212-216 and
+ * 265-276, pfedmac/_pfedmac.py:158-162 and 203-212, nodes.py:1134-1180).  Over the flat concatenation of the model's
+ * tensors (element e of a record = element e - start_t of tensor t, the order the client flattens its gradient list):
+ *   params[t] = params[t] * inertia, then fmaf(w_params[m], param_srcs[m * n_tensors + t], .) for m in order
+ *               (exactly flc_avg_and_gradients' parameters; param_srcs == NULL: params is not touched — that form is
+ *               update_gradients alone);
+ *   grads[t]  = +0, then fmaf(w_grads[m], decode(grad_records[m])[e], .) for m in order;
+ * bit-identical to decoding every record densely (flc_stacked_decode_tiled) and calling flc_avg_and_gradients — -0
+ * results, empty tiles and weights of either sign or zero included.  One wave per FLC_TILE-element tile decodes the
+ * tile's slice of every record into the gradient and folds the same slice of the dense parameter sources.
+ * grad_records: HOST array of n_src device pointers to records of the flc_stacked_wire_layout(n, k) layout (16-B
+ * aligned); params / grads / sizes: HOST arrays of n_tensors, sizes summing to n.  One launch for n_src <= 16 and
+ * n_tensors <= 16; records chain per 64, parameter sources per 16, tensors per 16 (each later launch continues the
+ * stored partial results). */
+int flc_avg_and_gradient_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                 const void* const* grad_records, const float* w_params, const float* w_grads,
+                                 int n_src, int64_t n, int64_t k, int levels, const int64_t* sizes, int n_tensors,
+                                 float inertia, void* stream);
 /* FedDyn's and pFedMe's server updates on a whole model, one pass per <= 16 tensors and <= 16 messages
  * (theta = the model, aux = the per-element second state; srcs[m * n_tensors + t] = message m's tensor t):
  *   FLC_SRV_FEDDYN (feddyn/_feddyn.py:172-184): h = aux, for each message in order h = fmaf(c, fl(src - theta0), h)
