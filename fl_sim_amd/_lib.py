@@ -133,6 +133,10 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
          c_int, c_double, c_double, c_double, c_void_p],
     ),
+    "flc_fold_record_groups": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p],
+    ),
     "flc_comm_id_bytes": (c_size_t, []),
     "flc_comm_rccl_origin": (c_char_p, []),
     "flc_comm_unique_id": (c_int, [c_void_p]),

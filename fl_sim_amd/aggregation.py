@@ -431,30 +431,84 @@ def fedopt_update(model_params: Sequence[torch.Tensor], delta_parameters: Sequen
         _contig_call(codec.fedopt_step, sp, dp, vp, opt if vp is not None else "avg", lr, betas[1], tau)
 
 
+def _as_lists(messages: Sequence[Mapping], key: str) -> Sequence[Mapping]:
+    """The messages with a compressed ``key`` read as its list of decoded tensors (the dense path of a round the
+    grouped record fold does not take); messages without one are returned as they are."""
+    if not any(isinstance(m[key], compressed.CompressedDelta) for m in messages):
+        return messages
+    return [{key: list(m[key])} for m in messages]
+
+
+def _add_round(dsts: Sequence[torch.Tensor], messages: Sequence[Mapping], key: str, ratio: float) -> None:
+    """``dst += Σ_m ratio · m[key]`` in message order: one launch, else one per tensor."""
+    messages = _as_lists(messages, key)
+    if not _fold(dsts, messages, [ratio] * len(messages), 2, key=key):
+        for j, sp in enumerate(dsts):
+            _weighted_sum_any(sp, [m[key][j] for m in messages], [ratio] * len(messages), 2)
+
+
+def _fold_groups(groups, records=None) -> List[bool]:
+    """compressed.fold_record_groups over ``groups`` (deltas, weights, dsts): the groups whose records share one
+    (n, k, levels) in one pass (SCAFFOLD's two compressor sets may differ); per group, whether it was folded."""
+    done = [False] * len(groups)
+    shapes: dict = {}
+    for i, (ds, _, _) in enumerate(groups):
+        shapes.setdefault((ds[0].n, ds[0].k, ds[0].levels), []).append(i)
+    for ids in shapes.values():
+        ok = compressed.fold_record_groups([groups[i] for i in ids],
+                                           None if records is None else [records[i] for i in ids])
+        for i in ids:
+            done[i] = ok
+    return done
+
+
 def scaffold_update(model_params: Sequence[torch.Tensor], control_variates: Sequence[torch.Tensor],
                     messages: Sequence[Mapping], lr: float, num_clients: int) -> None:
     """_scaffold.py:158-167.  The reference interleaves the two folds per message; they touch different tensors,
-    so each tensor's fmaf chain (message order) is the same when folded in one launch per tensor."""
+    so each tensor's fmaf chain (message order) is the same when folded in one launch per tensor.  A round whose
+    ``parameters_delta`` and / or ``control_variates_delta`` are stacked records (the codec's call site,
+    compressed.CompressedSCAFFOLDClientMixin) folds those vectors from the records in one grouped pass
+    (flc_fold_record_groups: θ and c are its two groups); the other vector, and any other round, takes the dense
+    path."""
     if len(messages) == 0:
         raise ZeroDivisionError("division by zero")  # ratio_p = lr / len(messages) in the reference
     ratio_p = lr / len(messages)
     ratio_c = 1 / num_clients
     model_params, control_variates = list(model_params), list(control_variates)
+    keys = ("parameters_delta", "control_variates_delta")
+    recs = [compressed.stacked_round(messages, key) for key in keys]
+    n = len(messages)
     if hoststage.is_host(model_params):
-        n = len(messages)
+        msgs = [[[d.record] for d in r] if r is not None else [m[key] for m in messages] for key, r in zip(keys, recs)]
         with hoststage.staged([model_params, control_variates], [True, True], [True, True],
-                              [m["parameters_delta"] for m in messages]
-                              + [m["control_variates_delta"] for m in messages]) as ((dps, dcvs), dm):
-            scaffold_update(dps, dcvs, [{"parameters_delta": a, "control_variates_delta": b}
-                                        for a, b in zip(dm[:n], dm[n:])], lr, num_clients)
+                              msgs[0] + msgs[1]) as ((dps, dcvs), dm):
+            if recs[0] is None and recs[1] is None:
+                scaffold_update(dps, dcvs, [{"parameters_delta": a, "control_variates_delta": b}
+                                            for a, b in zip(dm[:n], dm[n:])], lr, num_clients)
+                return
+            staged = [dm[:n], dm[n:]]
+            live = [i for i in (0, 1) if recs[i] is not None]
+            done = _fold_groups([(recs[i], [(ratio_p, ratio_c)[i]] * n, (dps, dcvs)[i]) for i in live],
+                                [[r[0] for r in staged[i]] for i in live])
+            for i, (key, dst, ratio) in enumerate(zip(keys, (_params(dps), list(dcvs)), (ratio_p, ratio_c))):
+                if i in live and done[live.index(i)]:
+                    continue
+                _add_round(dst, messages if recs[i] is not None else [{key: d} for d in staged[i]], key, ratio)
         return
     ps, cvs = _params(model_params), list(control_variates)
-    if not _fold(ps, messages, [ratio_p] * len(messages), 2, key="parameters_delta"):
-        for j, sp in enumerate(ps):
-            _weighted_sum_any(sp, [m["parameters_delta"][j] for m in messages], [ratio_p] * len(messages), 2)
-    if not _fold(cvs, messages, [ratio_c] * len(messages), 2, key="control_variates_delta"):
-        for j, cv in enumerate(cvs):
-            _weighted_sum_any(cv, [m["control_variates_delta"][j] for m in messages], [ratio_c] * len(messages), 2)
+    if recs[0] is None and recs[1] is None:
+        if not _fold(ps, messages, [ratio_p] * len(messages), 2, key="parameters_delta"):
+            for j, sp in enumerate(ps):
+                _weighted_sum_any(sp, [m["parameters_delta"][j] for m in messages], [ratio_p] * len(messages), 2)
+        if not _fold(cvs, messages, [ratio_c] * len(messages), 2, key="control_variates_delta"):
+            for j, cv in enumerate(cvs):
+                _weighted_sum_any(cv, [m["control_variates_delta"][j] for m in messages], [ratio_c] * len(messages), 2)
+        return
+    live = [i for i in (0, 1) if recs[i] is not None]
+    done = _fold_groups([(recs[i], [(ratio_p, ratio_c)[i]] * n, (ps, cvs)[i]) for i in live])
+    for i, (key, dst, ratio) in enumerate(zip(keys, (ps, cvs), (ratio_p, ratio_c))):
+        if not (i in live and done[live.index(i)]):
+            _add_round(dst, messages, key, ratio)
 
 
 def ifca_update(cluster_centers: Mapping[int, dict], messages: Sequence[Mapping], num_clusters: int) -> None:
@@ -462,7 +516,9 @@ def ifca_update(cluster_centers: Mapping[int, dict], messages: Sequence[Mapping]
 
     Host bookkeeping as in the reference: the round's members are listed, idle members of the previous round rejoin
     their cluster, and each member is appended once more while its delta is folded (the reference's duplicate
-    entries are kept, so downstream code sees the same lists).  Each center tensor is folded in one launch."""
+    entries are kept, so downstream code sees the same lists).  Each center tensor is folded in one launch; a round
+    whose messages are all stacked records of one (n, k, levels) (compressed.CompressedIFCAClientMixin) folds every
+    cluster that has messages in one grouped pass (flc_fold_record_groups: the clusters are its groups)."""
     prev = {c: list(v["client_ids"]) for c, v in cluster_centers.items()}
     for v in cluster_centers.values():
         v["client_ids"] = []
@@ -475,17 +531,47 @@ def ifca_update(cluster_centers: Mapping[int, dict], messages: Sequence[Mapping]
     collected = set(i for v in cluster_centers.values() for i in v["client_ids"])
     for c, v in cluster_centers.items():
         v["client_ids"].extend(i for i in prev[c] if i not in collected)
-    for c, ms in members.items():
-        center = list(cluster_centers[c]["center_model_params"])
-        if hoststage.is_host(center):
-            with hoststage.staged([center], [True], [True], [m["delta_parameters"] for m in ms]) as ((dc,), dm):
-                for j, p in enumerate(dc):
-                    _weighted_sum_any(p, [d[j] for d in dm], [1 / sizes[c]] * len(ms), 2)
-            continue
-        for j, p in enumerate(_params(center)):
-            _weighted_sum_any(p, [m["delta_parameters"][j] for m in ms], [1 / sizes[c]] * len(ms), 2)
+    if not (compressed.stacked_round(messages) is not None and _ifca_records(cluster_centers, members, sizes)):
+        for c, ms in members.items():
+            center = list(cluster_centers[c]["center_model_params"])
+            if hoststage.is_host(center):
+                with hoststage.staged([center], [True], [True], [m["delta_parameters"] for m in ms]) as ((dc,), dm):
+                    for j, p in enumerate(dc):
+                        _weighted_sum_any(p, [d[j] for d in dm], [1 / sizes[c]] * len(ms), 2)
+                continue
+            for j, p in enumerate(_params(center)):
+                _weighted_sum_any(p, [m["delta_parameters"][j] for m in ms], [1 / sizes[c]] * len(ms), 2)
     for m in messages:
         cluster_centers[m["cluster_id"]]["client_ids"].append(m["client_id"])
+
+
+def _ifca_records(cluster_centers: Mapping[int, dict], members: Mapping[int, list], sizes: Mapping[int, int]) -> bool:
+    """A round of stacked records: every cluster with messages folded in one grouped pass, each centre in place
+    (host-resident centres staged together: the records in, the centres out).  False: nothing launched."""
+    cs = list(members)
+    centers = [list(cluster_centers[c]["center_model_params"]) for c in cs]
+    deltas = [[m["delta_parameters"] for m in members[c]] for c in cs]
+    weights = [[1 / sizes[c]] * len(members[c]) for c in cs]
+    host = [hoststage.is_host(center) for center in centers]
+    if all(host):
+        # every cluster's centre staged together, in the centres' own order (the mixin adopts them so); the idle
+        # clusters' are neither copied in nor written back
+        every = list(cluster_centers)
+        groups = [list(cluster_centers[c]["center_model_params"]) for c in every]
+        if not all(isinstance(p, torch.Tensor) and p.is_cpu and p.dtype is torch.float32 for g in groups for p in g):
+            return False
+        live = [c in members for c in every]
+        flat = [[d.record] for ds in deltas for d in ds]
+        with hoststage.staged(groups, live, live, flat) as (dcs, dm):
+            staged, off = [], 0
+            for ds in deltas:
+                staged.append([r[0] for r in dm[off:off + len(ds)]])
+                off += len(ds)
+            dsts = [_params(dcs[every.index(c)]) for c in cs]
+            return compressed.fold_record_groups(list(zip(deltas, weights, dsts)), staged)
+    if any(host):
+        return False
+    return compressed.fold_record_groups(list(zip(deltas, weights, [_params(center) for center in centers])))
 
 
 _PROX_KIND = {"l1": "l1", "l2": "l2", "l2squared": "l2squared", "no": "none", "empty": "none", "zero": "none",
@@ -749,8 +835,11 @@ class SCAFFOLDUpdateMixin:
     """Device ``update()`` for the reference's ``SCAFFOLDServer`` (_scaffold.py:158-167)."""
 
     def update(self) -> None:
+        recs = (compressed.stacked_round(self._received_messages, "parameters_delta")
+                or compressed.stacked_round(self._received_messages, "control_variates_delta"))
         _adopt([list(self.model.parameters()), self._control_variates],
-               [m["parameters_delta"] for m in self._received_messages])
+               [[d.record] for d in recs] if recs is not None
+               else [m["parameters_delta"] for m in self._received_messages])
         scaffold_update(list(self.model.parameters()), self._control_variates, self._received_messages,
                         self.config.lr, len(self._clients))
 
@@ -759,6 +848,9 @@ class IFCAUpdateMixin:
     """Device ``update()`` for the reference's ``IFCAServer`` (_ifca.py:167-195)."""
 
     def update(self) -> None:
+        recs = compressed.stacked_round(self._received_messages)  # (compressed messages: the fold reads the records)
+        if recs is not None:
+            _adopt([v["center_model_params"] for v in self._cluster_centers.values()], [[d.record] for d in recs])
         ifca_update(self._cluster_centers, self._received_messages, self.config.num_clusters)
 
 

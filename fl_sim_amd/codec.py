@@ -892,6 +892,22 @@ def _pyrecs():
     return _PYRECS[0]
 
 
+_PYGROUPS: list = []
+
+
+def _pygroups():
+    """fl_sim_amd._flcfold.fold_record_groups (flc_fold_record_groups on Python lists, one C call) when built, else
+    None."""
+    if not _PYGROUPS:
+        try:
+            from . import _flcfold
+
+            _PYGROUPS.append(_flcfold.fold_record_groups)
+        except (ImportError, AttributeError):
+            _PYGROUPS.append(None)
+    return _PYGROUPS[0]
+
+
 _PYGRECS: list = []
 
 

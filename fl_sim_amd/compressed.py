@@ -37,6 +37,16 @@ the one whose server fold starts from +0 (``tests/golden/gen_golden_vr_codec.py`
 * ``aggregation.avg_parameters_and_gradients`` / ``update_gradients`` (and the ``VRUpdateMixin`` family) recognise a
   round of stacked records and run :func:`fold_gradient_records`: every record decoded and folded into the gradients
   and the dense parameters folded into the model in one ``flc_avg_and_gradient_records`` pass.
+
+SCAFFOLD and IFCA send deltas (scaffold/_scaffold.py:210-222: ``parameters_delta`` and ``control_variates_delta``;
+ifca/_ifca.py:228-240: ``delta_parameters`` and a ``cluster_id``), and their servers accumulate each message in place
+into one of several destinations (θ and c; the message's cluster centre):
+
+* :class:`CompressedSCAFFOLDClientMixin` / :class:`CompressedIFCAClientMixin` — ``communicate`` with every delta sent
+  through :func:`compress_delta` (``tests/golden/gen_golden_delta_codec.py`` fixes the meaning);
+* ``aggregation.scaffold_update`` / ``ifca_update`` recognise a round of stacked records and run
+  :func:`fold_record_groups`: every destination's records decoded and folded in ONE ``flc_fold_record_groups`` pass
+  (grid = tiles × groups).
 """
 
 from __future__ import annotations
@@ -542,6 +552,66 @@ def fold_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequence[f
     return True
 
 
+def fold_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequence[float], Sequence[torch.Tensor]]],
+                       records: Optional[Sequence[Optional[Sequence[torch.Tensor]]]] = None) -> bool:
+    """For every ``(deltas, weights, dst_tensors)`` of ``groups``: ``dst += Σ_c w_c·decode(record_c)`` in place, in
+    the group's message order (``add_parameters``' accumulation) — all groups in one ``flc_fold_record_groups`` pass.
+    A group without deltas is left alone.  ``records[g]``: group ``g``'s records where they were staged (default: the
+    deltas' own).  False (nothing launched) when the records are not of one (n, k, levels), or a destination tensor
+    is not a contiguous fp32 tensor of one HIP device, or the groups' tensors do not all hold the records' element
+    counts tensor by tensor, or two groups share a destination (the caller then takes the dense path); records on
+    another device are moved."""
+    recs_of = list(records) if records is not None else [None] * len(groups)
+    live = [(list(ds), list(ws), [p.data if isinstance(p, torch.nn.Parameter) else p for p in dst], rs)
+            for (ds, ws, dst), rs in zip(groups, recs_of) if len(ds)]
+    if not live:
+        return True
+    d0 = live[0][0][0]
+    if any((d.n, d.k, d.levels) != (d0.n, d0.k, d0.levels) for ds, _, _, _ in live for d in ds):
+        return False
+    if any(len(ws) != len(ds) or (rs is not None and len(rs) != len(ds)) for ds, ws, _, rs in live):
+        return False
+    fast = codec._pygroups()
+    if fast is not None:
+        try:  # one C call: every tensor checked in place; TypeError: nothing launched, the checks below decide
+            fast([[d.record for d in ds] if rs is None else rs for ds, _, _, rs in live],
+                 [ws for _, ws, _, _ in live], [dst for _, _, dst, _ in live], d0.n, d0.k, d0.levels)
+            return True
+        except TypeError:
+            pass
+    first = live[0][2]
+    if not first or not isinstance(first[0], torch.Tensor) or not first[0].is_cuda:
+        return False
+    dev = first[0].device
+    sizes = [t.numel() for t in first]
+    if sum(sizes) != d0.n:
+        return False
+    seen = set()
+    for ds, ws, dst, rs in live:
+        if len(dst) != len(sizes):
+            return False
+        for t, m in zip(dst, sizes):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype is torch.float32
+                    and t.is_contiguous() and t.numel() == m):
+                return False
+            if m and t.data_ptr() in seen:
+                return False
+            if m:
+                seen.add(t.data_ptr())
+    recs, ws, gof, dsts = [], [], [], []
+    for g, (ds, w, dst, rs) in enumerate(live):
+        rl = [d.record for d in ds] if rs is None else list(rs)
+        recs += [r if r.device == dev else r.to(dev) for r in rl]
+        ws += [float(x) for x in w]
+        gof += [g] * len(ds)
+        dsts += dst
+    m, T = len(recs), len(sizes)
+    with torch.cuda.device(dev):
+        _lib.call("flc_fold_record_groups", _ptrs(recs), (ctypes.c_float * m)(*ws), (ctypes.c_int32 * m)(*gof), m,
+                  d0.n, d0.k, d0.levels, _ptrs(dsts), len(live), (ctypes.c_int64 * T)(*sizes), T, codec._stream(dev))
+    return True
+
+
 def _compressors_of(node, name: str = "compressors") -> List[Compressor]:
     cs = getattr(node, name, None)
     if cs is None:
@@ -565,6 +635,68 @@ class CompressedFedOptClientMixin:
             client_message_class()(
                 **{
                     "client_id": self.client_id,
+                    "delta_parameters": delta,
+                    "train_samples": len(self.train_loader.dataset),
+                    "metrics": self._metrics,
+                }
+            )
+        )
+
+
+class CompressedSCAFFOLDClientMixin:
+    """Mix in before the reference's ``SCAFFOLDClient`` (``class C(CompressedSCAFFOLDClientMixin, SCAFFOLDClient)``):
+    ``communicate`` (scaffold/_scaffold.py:210-222) sends ``parameters_delta`` through the client's ``compressors`` and
+    ``control_variates_delta`` through its ``control_compressors`` (each looked up on the client, then on its config:
+    one :class:`~fl_sim_amd.compressors.Compressor` or a sequence applied in order; a missing set sends that vector as
+    the reference does), in that order, then applies the reference's side effects (the control variates take the
+    updated ones, which are released).  In philox mode with the stacked pipeline both records join the round's one
+    batched encode, each with its own counter; the deferred encode reads a snapshot of the flat delta taken here, so
+    overwriting the control variates afterwards is safe.  The server side is
+    :class:`~fl_sim_amd.aggregation.SCAFFOLDUpdateMixin`, which folds both vectors' records in one pass (or any
+    reference server: the compressed deltas read as lists of tensors)."""
+
+    def communicate(self, target) -> None:
+        cs, ccs = _compressors_of(self), _compressors_of(self, "control_compressors")
+        params = list(self.model.parameters())
+        if cs:
+            pd = compress_delta(params, self._cached_parameters, cs)
+        else:
+            pd = [mp.detach().sub(cp) for mp, cp in zip(params, self._cached_parameters)]
+        if ccs:
+            cd = compress_delta(list(self._updated_control_variates), self._control_variates, ccs)
+        else:
+            cd = [ucv.sub(cv) for ucv, cv in zip(self._updated_control_variates, self._control_variates)]
+        target._received_messages.append(
+            client_message_class()(
+                **{
+                    "client_id": self.client_id,
+                    "parameters_delta": pd,
+                    "control_variates_delta": cd,
+                    "train_samples": len(self.train_loader.dataset),
+                    "metrics": self._metrics,
+                }
+            )
+        )
+        for cv, ucv in zip(self._control_variates, self._updated_control_variates):
+            cv.copy_(ucv)
+        del self._updated_control_variates  # free memory
+        self._updated_control_variates = None
+
+
+class CompressedIFCAClientMixin:
+    """Mix in before the reference's ``IFCAClient`` (``class C(CompressedIFCAClientMixin, IFCAClient)``):
+    ``communicate`` (ifca/_ifca.py:228-240) sends the delta through the client's compressors
+    (:class:`CompressedFedOptClientMixin`'s message) and the client's ``cluster_id`` beside it.  The server side is
+    :class:`~fl_sim_amd.aggregation.IFCAUpdateMixin`, which folds every cluster's records in one pass (or any
+    reference server)."""
+
+    def communicate(self, target) -> None:
+        delta = compress_delta(list(self.model.parameters()), self._cached_parameters, _compressors_of(self))
+        target._received_messages.append(
+            client_message_class()(
+                **{
+                    "client_id": self.client_id,
+                    "cluster_id": self.cluster_id,
                     "delta_parameters": delta,
                     "train_samples": len(self.train_loader.dataset),
                     "metrics": self._metrics,

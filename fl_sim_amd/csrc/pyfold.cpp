@@ -3,7 +3,8 @@
 // update_gradients (_fedopt.py:196-240, nodes.py:1116-1180); `server_fold`, the same for FedDyn's and pFedMe's server
 // updates (flc_model_fold_server); `avg_and_gradients`, the variance-reduced servers' avg_parameters + update_gradients
 // (flc_avg_and_gradients), and `avg_and_gradient_records`, the same over compressed gradients
-// (flc_avg_and_gradient_records); `stacked_delta_record`, a client's compressed message (flc_stacked_encode_delta into a wire
+// (flc_avg_and_gradient_records); `fold_record_groups`, a round of records folded into several models
+// (flc_fold_record_groups); `stacked_delta_record`, a client's compressed message (flc_stacked_encode_delta into a wire
 // record + flc_delta_count_nonzero_at).
 //
 // At configs[0] (cnn_femmist_tiny: 8 tensors, 10 clients) the kernel takes ~9 us, but going through the dispatcher
@@ -744,6 +745,95 @@ PyObject* fold_records(PyObject*, PyObject* args) {
   return done((Py_INCREF(Py_None), Py_None));
 }
 
+// fold_record_groups(records, weights, dsts, n, k, levels): a round whose stacked records fall into groups, each
+// folded in place into its own model (flc_fold_record_groups) on Python lists — records / weights / dsts hold one
+// sequence per group (SCAFFOLD: θ and c; IFCA: the clusters with messages).  TypeError (nothing launched) when a tensor
+// is not what the pass takes — every group's tensors contiguous fp32 HIP tensors of one device holding, tensor by
+// tensor, the first group's element counts summing to n, no tensor in two groups, the records 16-B aligned uint8
+// tensors of at least the wire layout's bytes on that device — so the caller can take its other path.
+PyObject* fold_record_groups(PyObject*, PyObject* args) {
+  PyObject *recs, *weights, *dsts;
+  long long n, k;
+  int levels;
+  if (!PyArg_ParseTuple(args, "OOOLLi", &recs, &weights, &dsts, &n, &k, &levels)) return nullptr;
+  std::vector<PyObject*> keep;
+  auto done = [&](PyObject* r) {
+    for (PyObject* o : keep) Py_XDECREF(o);
+    return r;
+  };
+  auto fast = [&](PyObject* o) {
+    PyObject* f = PySequence_Fast(o, "fold_record_groups takes sequences of sequences");
+    if (f) keep.push_back(f);
+    return f;
+  };
+  PyObject *fr = fast(recs), *fw = fr ? fast(weights) : nullptr, *fd = fw ? fast(dsts) : nullptr;
+  if (!fd) return done(nullptr);
+  const Py_ssize_t ng = PySequence_Fast_GET_SIZE(fd);
+  if (ng < 1 || PySequence_Fast_GET_SIZE(fr) != ng || PySequence_Fast_GET_SIZE(fw) != ng)
+    return done(type_error("fold_record_groups needs one record list, weight list and tensor list per group"));
+  int64_t off[4];
+  const size_t stride = flc_stacked_wire_layout(n, k, off);
+  if (stride == 0) return done(value_error("bad wire shape"));
+  int dev = -1;
+  std::vector<float*> dp;
+  std::vector<int64_t> sz;
+  std::vector<const void*> rp;
+  std::vector<float> w;
+  std::vector<int32_t> gof;
+  for (Py_ssize_t g = 0; g < ng; ++g) {
+    PyObject* ft = fast(PySequence_Fast_ITEMS(fd)[g]);
+    if (!ft) return done(nullptr);
+    const Py_ssize_t nt = PySequence_Fast_GET_SIZE(ft);
+    if (nt < 1 || (g > 0 && (size_t)nt != sz.size()))
+      return done(type_error("every group needs the first group's number of tensors"));
+    if (g == 0) sz.resize(nt);
+    int64_t total = 0;
+    for (Py_ssize_t t = 0; t < nt; ++t) {
+      const at::Tensor* a = usable(PySequence_Fast_ITEMS(ft)[t], &dev);
+      if (!a) return done(type_error("server tensors must be contiguous fp32 HIP tensors on one device"));
+      if (g == 0) sz[t] = a->numel();
+      else if (a->numel() != sz[t]) return done(type_error("every group's tensors must match the first group's sizes"));
+      total += sz[t];
+      float* q = a->data_ptr<float>();
+      if (sz[t] > 0)
+        for (float* other : dp)
+          if (other == q) return done(type_error("a server tensor in two places"));
+      dp.push_back(q);
+    }
+    if (total != n) return done(type_error("the server tensors do not hold the records' element count"));
+    PyObject* frg = fast(PySequence_Fast_ITEMS(fr)[g]);
+    PyObject* fwg = frg ? fast(PySequence_Fast_ITEMS(fw)[g]) : nullptr;
+    if (!fwg) return done(nullptr);
+    const Py_ssize_t nr = PySequence_Fast_GET_SIZE(frg);
+    if (PySequence_Fast_GET_SIZE(fwg) != nr) return done(value_error("one weight per record"));
+    for (Py_ssize_t c = 0; c < nr; ++c) {
+      const at::Tensor* r = usable_as(PySequence_Fast_ITEMS(frg)[c], at::kByte, &dev);
+      if (!r || (size_t)r->numel() < stride || reinterpret_cast<uintptr_t>(r->data_ptr()) % 16 != 0)
+        return done(type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the server's device"));
+      rp.push_back(r->data_ptr());
+      const double wd = PyFloat_AsDouble(PySequence_Fast_ITEMS(fwg)[c]);
+      if (wd == -1.0 && PyErr_Occurred()) return done(nullptr);
+      w.push_back((float)wd);
+      gof.push_back((int32_t)g);
+    }
+  }
+  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
+  int rc = FLC_OK;
+  Py_BEGIN_ALLOW_THREADS
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  if (cur != dev) (void)hipSetDevice(dev);
+  rc = flc_fold_record_groups(rp.data(), w.data(), gof.data(), (int)rp.size(), n, k, levels, dp.data(), (int)ng,
+                              sz.data(), (int)sz.size(), st);
+  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
+  Py_END_ALLOW_THREADS
+  if (rc != FLC_OK) {
+    PyErr_Format(PyExc_RuntimeError, "flc_fold_record_groups failed with status %d: %s", rc, flc_last_error());
+    return done(nullptr);
+  }
+  return done((Py_INCREF(Py_None), Py_None));
+}
+
 // avg_and_gradient_records(params, msgs, records, w_params, w_grads, n, k, levels, inertia, set_grad): a
 // variance-reduced round whose gradients are stacked records (flc_avg_and_gradient_records) on Python lists.  `params`
 // folded in place from every message's "parameters" (`msgs` None: left untouched — update_gradients alone, `w_params`
@@ -917,6 +1007,9 @@ PyMethodDef kMethods[] = {
     {"fold_records", fold_records, METH_VARARGS,
      "fold_records(records, weights, n, k, levels, delta, theta, v, beta0, opt, lr, beta2, tau): "
      "flc_fedopt_fold_records on Python lists"},
+    {"fold_record_groups", fold_record_groups, METH_VARARGS,
+     "fold_record_groups(records, weights, dsts, n, k, levels): flc_fold_record_groups on Python lists (one sequence "
+     "per group)"},
     {"avg_and_gradient_records", avg_and_gradient_records, METH_VARARGS,
      "avg_and_gradient_records(params, msgs, records, w_params, w_grads, n, k, levels, inertia[, set_grad]): "
      "flc_avg_and_gradient_records on Python lists (messages: mappings with 'parameters', or None)"},

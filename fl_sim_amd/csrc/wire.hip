@@ -26,11 +26,14 @@
 //
 // The same kernel with a model as its accumulator (an IO policy): flc_fedopt_fold_records (ModelIO: δ, then the server
 // optimiser's step) and flc_avg_and_gradient_records (PairIO: a variance-reduced round's gradients from records, the
-// dense parameters folded in the same pass).
+// dense parameters folded in the same pass) and flc_fold_record_groups (GroupIO: the launch's records fall into
+// groups, each folded in place into its own model — SCAFFOLD's two vectors, IFCA's clusters).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <utility>
+#include <vector>
 
 #include "flc_device.hpp"
 #include "flc_runtime.hpp"
@@ -70,6 +73,7 @@ __device__ __forceinline__ float skip_clients(float a, unsigned from, unsigned t
 // Where a tile's accumulator comes from and where it goes.  Lane `lane` owns float4 groups q = lane + 64 u (u < 4)
 // of the tile starting at flat element t0.
 struct FlatIO {  // one flat vector: out = fold (from +0, or from out itself)
+  static constexpr bool kGrouped = false;
   float* out;
   int64_t n;
   int acc_in;
@@ -125,6 +129,7 @@ struct ModelTab {
 };
 template <int OPT>  // OPT < 0: the fold only (δ written, no step)
 struct ModelIO {
+  static constexpr bool kGrouped = false;
   ModelTab m;
   __device__ __forceinline__ int first_tensor(int64_t t0) const {
     int t = 0;
@@ -227,6 +232,7 @@ struct PairTab {
   float inertia;
 };
 struct PairIO {
+  static constexpr bool kGrouped = false;
   PairTab m;
   __device__ __forceinline__ int first_tensor(int64_t t0) const {
     int t = 0;
@@ -307,13 +313,84 @@ struct PairIO {
   }
 };
 
+// A round whose records fall into groups, each accumulating in place into its own model (flc_fold_record_groups):
+// SCAFFOLD's two vectors (θ and c, _scaffold.py:160-169), IFCA's cluster centres (_ifca.py:186-195).  blockIdx.y
+// is the launch's group: its records are the [first, first + count) slice of FoldArgs (the host orders a launch's
+// records by group), its accumulator the group's own tensors (load: the stored values — add_parameters' in-place
+// accumulation, nothing scaled or zeroed; store: the fold).  The tensor walk is ModelIO's.
+constexpr int kMaxGroups = 16;  // groups per launch (kernel-argument budget: 2 KB of destination pointers)
+struct GroupTab {
+  float* dst[kMaxGroups][kRoundT];
+  int64_t start[kRoundT + 1];
+  unsigned vec[kMaxGroups];  // bit t: the group's tensor t 16-B aligned and start[t] % 4 == 0
+  int first[kMaxGroups], count[kMaxGroups];
+  int nt;
+};
+struct GroupIO {
+  static constexpr bool kGrouped = true;
+  GroupTab m;
+  __device__ __forceinline__ int first() const { return m.first[blockIdx.y]; }
+  __device__ __forceinline__ int count() const { return m.count[blockIdx.y]; }
+  __device__ __forceinline__ int first_tensor(int64_t t0) const {
+    int t = 0;
+    while (t + 1 < m.nt && m.start[t + 1] <= t0) ++t;
+    return t;
+  }
+  __device__ __forceinline__ void load(int64_t t0, int lane, float4 acc[4]) const {
+    const int g = blockIdx.y;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int t = first_tensor(t0); t < m.nt && m.start[t] < t0 + FLC_TILE; ++t) {
+      const int64_t s0 = m.start[t], s1 = m.start[t + 1];
+      const float* __restrict__ d = m.dst[g][t];
+      const bool vec = (m.vec[g] >> t) & 1u;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t e = t0 + 4 * (int64_t)(lane + u * kWave);
+        if (vec && e >= s0 && e + 4 <= s1) {
+          acc[u] = *reinterpret_cast<const float4*>(d + (e - s0));
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (e + j >= s0 && e + j < s1) comp(acc[u], j) = d[e + j - s0];
+        }
+      }
+    }
+  }
+  __device__ __forceinline__ void store(int64_t t0, int lane, float4 acc[4]) const {
+    const int g = blockIdx.y;
+    for (int t = first_tensor(t0); t < m.nt && m.start[t] < t0 + FLC_TILE; ++t) {
+      const int64_t s0 = m.start[t], s1 = m.start[t + 1];
+      float* __restrict__ d = m.dst[g][t];
+      const bool vec = (m.vec[g] >> t) & 1u;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t e = t0 + 4 * (int64_t)(lane + u * kWave);
+        if (vec && e >= s0 && e + 4 <= s1) {
+          *reinterpret_cast<float4*>(d + (e - s0)) = acc[u];
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (e + j >= s0 && e + j < s1) d[e + j - s0] = comp(acc[u], j);
+        }
+      }
+    }
+  }
+};
+
 template <bool SPARSE, class IO>
-__global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, WireLayout L, int nw, int levels,
+__global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, WireLayout L, int nw_all, int levels,
                                                                    double step, int64_t tile0, IO io, unsigned k) {
   __shared__ __attribute__((aligned(16))) float s_tile[FLC_TILE];
   __shared__ __attribute__((aligned(16))) uint8_t s_last[SPARSE ? FLC_TILE : 4];  // sparse: last writer + 1 (0: none)
   float4* tile4 = reinterpret_cast<float4*>(s_tile);
   const int lane = threadIdx.x;
+  // the block's records: the whole launch's, or (a grouped launch) its group's slice of them
+  int nw = nw_all, rec0 = 0;
+  if constexpr (IO::kGrouped) {
+    nw = io.count();
+    rec0 = io.first();
+  }
   const int64_t t = tile0 + blockIdx.x;
   const int64_t t0 = t * FLC_TILE;
   // the tile's slice of the accumulator: lane owns float4 q = lane + 64 u
@@ -330,8 +407,8 @@ __global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, W
   unsigned lo = 0, cnt = 0;
   float nrm = 0.0f, wl = 0.0f;
   if (lane < nw) {
-    rec = a.rec[lane];
-    wl = a.w[lane];
+    rec = a.rec[rec0 + lane];
+    wl = a.w[rec0 + lane];
     const unsigned* tiles = reinterpret_cast<const unsigned*>(rec + L.tiles);
     // (clamped to the record's k entries: a malformed or unwritten tile pointer never reads past the record)
     lo = min(tiles[t], k);
@@ -725,6 +802,120 @@ int flc_avg_and_gradient_records(float* const* params, float* const* grads, cons
         FLC_LAUNCH("avg_and_gradient_records", (stacked_fold_wires_kernel<false, PairIO>), grid, dim3(kWave), 0, st,
                    a, L, nw, levels, step, tile_lo, io, (unsigned)k);
     }
+  }
+  return FLC_OK;
+}
+
+int flc_fold_record_groups(const void* const* records, const float* weights, const int32_t* group_of, int n_records,
+                           int64_t n, int64_t k, int levels, float* const* dsts, int n_groups, const int64_t* sizes,
+                           int n_tensors, void* stream) {
+  if (n_records < 0 || (n_records > 0 && (!records || !weights || !group_of)) || n <= 0 || k < 0 || n_groups < 1 ||
+      n_tensors < 1 || !dsts || !sizes)
+    return fail(FLC_EINVAL, "flc_fold_record_groups: bad arguments");
+  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "flc_fold_record_groups: n and k must be < 2^31");
+  if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "flc_fold_record_groups: levels must be in [1, 127]");
+  int64_t total = 0;
+  for (int t = 0; t < n_tensors; ++t) {
+    if (sizes[t] < 0) return fail(FLC_EINVAL, "flc_fold_record_groups: negative size for tensor %d", t);
+    total += sizes[t];
+  }
+  if (total != n)
+    return fail(FLC_EINVAL, "flc_fold_record_groups: the tensors hold %lld elements, the records %lld",
+                (long long)total, (long long)n);
+  std::vector<int> members(n_groups, 0);
+  for (int c = 0; c < n_records; ++c) {
+    if (!records[c] || !aligned16(records[c]))
+      return fail(FLC_EINVAL, "flc_fold_record_groups: record %d is null or not 16-B aligned", c);
+    if (group_of[c] < 0 || group_of[c] >= n_groups)
+      return fail(FLC_EINVAL, "flc_fold_record_groups: record %d names group %d outside [0, %d)", c, (int)group_of[c],
+                  n_groups);
+    ++members[group_of[c]];
+  }
+  std::vector<std::pair<uintptr_t, int>> owners;  // (destination, group) of every non-empty tensor
+  for (int g = 0; g < n_groups; ++g)
+    for (int t = 0; t < n_tensors; ++t) {
+      float* d = dsts[(size_t)g * n_tensors + t];
+      if (sizes[t] == 0) continue;
+      if (!d) {
+        if (members[g] > 0)
+          return fail(FLC_EINVAL, "flc_fold_record_groups: null pointer for tensor %d of group %d", t, g);
+        continue;
+      }
+      owners.emplace_back(reinterpret_cast<uintptr_t>(d), g);
+    }
+  std::sort(owners.begin(), owners.end());
+  for (size_t i = 1; i < owners.size(); ++i)
+    if (owners[i].first == owners[i - 1].first && owners[i].second != owners[i - 1].second)
+      return fail(FLC_EINVAL, "flc_fold_record_groups: groups %d and %d share a destination", owners[i - 1].second,
+                  owners[i].second);
+  if (n_records == 0) return FLC_OK;
+  size_t need = 0;
+  const WireLayout L = wire_layout(n, k, &need);
+  hipStream_t st = as_stream(stream);
+  const double step = 1.0 / (double)levels;
+  // the records ordered by group, each group's in message order
+  std::vector<int> order(n_records);
+  for (int c = 0; c < n_records; ++c) order[c] = c;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return group_of[x] < group_of[y]; });
+  // launches over the ordered records: each takes <= kMaxWires records of <= kMaxGroups groups (a group cut by a
+  // launch's end continues in the next one from its stored results); within it, one launch per <= kRoundT tensors
+  int c0 = 0;
+  while (c0 < n_records) {
+    FoldArgs a;
+    GroupIO io{};
+    GroupTab& m = io.m;
+    int gsel[kMaxGroups];
+    int nw = 0, ng = 0;
+    // Sparse form (only the kept entries are fma'd, a -0 resolved as the dense chain resolves it) whenever every
+    // weight of the launch is finite: from ANY stored accumulator a, fmaf(w, +0, a) with a finite w returns a itself
+    // unless a is -0 and w's sign bit is clear — exactly skip_clients' rule (NaN stays NaN, ±inf stays ±inf).
+    bool sparse = true;
+    while (c0 + nw < n_records && nw < kMaxWires) {
+      const int c = order[c0 + nw], g = group_of[c];
+      if (ng == 0 || gsel[ng - 1] != g) {
+        if (ng == kMaxGroups) break;
+        gsel[ng] = g;
+        m.first[ng] = nw;
+        m.count[ng] = 0;
+        ++ng;
+      }
+      a.rec[nw] = static_cast<const uint8_t*>(records[c]);
+      a.w[nw] = weights[c];
+      sparse = sparse && std::isfinite(weights[c]);
+      ++m.count[ng - 1];
+      ++nw;
+    }
+    for (int c = nw; c < kMaxWires; ++c) {
+      a.rec[c] = nullptr;
+      a.w[c] = 0.0f;
+    }
+    int64_t off = 0;
+    int t = 0;
+    while (t < n_tensors) {
+      m.nt = 0;
+      for (int g = 0; g < kMaxGroups; ++g) m.vec[g] = 0u;
+      for (; t < n_tensors && m.nt < kRoundT; ++t) {
+        if (sizes[t] == 0) continue;
+        const int i = m.nt++;
+        m.start[i] = off;
+        for (int g = 0; g < ng; ++g) {
+          m.dst[g][i] = dsts[(size_t)gsel[g] * n_tensors + t];
+          if (off % 4 == 0 && aligned16(m.dst[g][i])) m.vec[g] |= 1u << i;
+        }
+        off += sizes[t];
+      }
+      if (m.nt == 0) break;
+      m.start[m.nt] = off;
+      const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
+      const dim3 grid((unsigned)(tile_hi - tile_lo), (unsigned)ng);
+      if (sparse)
+        FLC_LAUNCH("fold_record_groups", (stacked_fold_wires_kernel<true, GroupIO>), grid, dim3(kWave), 0, st, a, L, nw,
+                   levels, step, tile_lo, io, (unsigned)k);
+      else
+        FLC_LAUNCH("fold_record_groups", (stacked_fold_wires_kernel<false, GroupIO>), grid, dim3(kWave), 0, st, a, L,
+                   nw, levels, step, tile_lo, io, (unsigned)k);
+    }
+    c0 += nw;
   }
   return FLC_OK;
 }

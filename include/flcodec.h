@@ -222,6 +222,28 @@ int flc_fedopt_fold_records(const void* const* records, const float* weights, in
                             int levels, float* const* delta, float* const* theta, float* const* v,
                             const int64_t* sizes, int n_tensors, float beta0, int opt, double lr, double beta2,
                             double tau, void* stream);
+/* A round whose records fall into groups, each group accumulating in place into its own model, in ONE pass: the
+ * server side of a compressed SCAFFOLD round (the groups are its two vectors: theta += lr/|msgs| * parameters_delta,
+ * c += 1/N * control_variates_delta; replaces SCAFFOLDServer.update, scaffold/_scaffold.py:160-169, when the clients
+ * send both deltas as packed stacked records in place of _scaffold.py:210-222) and of a compressed IFCA round (the
+ * groups are the clusters: center += 1/cluster_size * delta; replaces ifca/_ifca.py:186-195 over the messages of
+ * _ifca.py:228-240).  For every group g, tensor t and element e of tensor t (flat element start_t + e of the records):
+ *   a = dsts[g * n_tensors + t][e];
+ *   for c = 0 .. n_records-1 with group_of[c] == g, in that order:  a = fmaf(weights[c], decode(records[c]), a);
+ *   dsts[g * n_tensors + t][e] = a
+ * — add_parameters' in-place accumulation (nodes.py:1116-1132): nothing scaled, nothing zeroed.  A group without a
+ * record is neither read nor written (its pointers may be NULL).  Bit-identical to decoding every record densely
+ * (flc_stacked_decode_tiled) and calling flc_weighted_sum(init_mode 2) per tensor: -0 and +-inf accumulators, empty
+ * tiles and weights of either sign or zero included; a NaN accumulator stays NaN.  records / weights / group_of / dsts
+ * / sizes: HOST arrays; records of the flc_stacked_wire_layout(n, k) layout, 16-B aligned; sizes summing to n.  One
+ * launch (grid = tiles x groups) for n_records <= 64 over all groups, <= 16 groups with records and n_tensors <= 16;
+ * beyond that launches chain, each continuing from the stored results, the order within a group kept.  FLC_EINVAL
+ * (nothing launched): a null or misaligned record, a group_of outside [0, n_groups), sizes not summing to n, n or
+ * k >= 2^31, levels outside [1, 127], a null destination of a non-empty tensor in a group that has records, the same
+ * destination in two groups. */
+int flc_fold_record_groups(const void* const* records, const float* weights, const int32_t* group_of, int n_records,
+                           int64_t n, int64_t k, int levels, float* const* dsts /* [n_groups][n_tensors] */,
+                           int n_groups, const int64_t* sizes, int n_tensors, void* stream);
 
 /* ------------------------------------------------------------------ multi-GPU exchange (RCCL over xGMI)
  * For callers outside torch; one process per GPU.  RCCL is the NCCL API on ROCm, looked
