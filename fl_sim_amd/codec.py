@@ -1134,6 +1134,103 @@ def delta_flatten(local_params: Sequence[torch.Tensor], global_params: Sequence[
     return out
 
 
+# ---------------------------------------------------------------------------------------- error feedback
+def _ef_memory(e: torch.Tensor, name: str = "e") -> torch.Tensor:
+    """An error-feedback memory is written in place: a contiguous fp32 HIP tensor as it is (never a copy)."""
+    if not isinstance(e, torch.Tensor) or e.device.type != "cuda" or e.dtype != torch.float32 or not e.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous float32 tensor on a HIP device")
+    return e
+
+
+def _ef_input(t: torch.Tensor, name: str) -> torch.Tensor:
+    """A read-only operand of the feedback kernels: contiguous fp32 on a HIP device, any 4-B alignment."""
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise TypeError(f"{name} must be a torch tensor on a HIP device")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32 (got {t.dtype}); the codec path is fp32")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def ef_accumulate(local_params: Sequence[torch.Tensor], global_params: Optional[Sequence[torch.Tensor]],
+                  e: torch.Tensor) -> torch.Tensor:
+    """``e += cat([l - g ...])`` in place (``global_params`` None: ``e += cat(local)``) — flc_ef_accumulate, the
+    accumulate of an error-feedback message into the client's memory.  Returns ``e``."""
+    import ctypes
+
+    e = _ef_memory(e)
+    ls = [_ef_input(t, "local") for t in local_params]
+    gs = None if global_params is None else [_ef_input(t, "global") for t in global_params]
+    if gs is not None and len(ls) != len(gs):
+        raise ValueError("one global tensor per local tensor")
+    for a, b in zip(ls, gs if gs is not None else ls):
+        if a.numel() != b.numel() or a.device != e.device or b.device != e.device:
+            raise ValueError("local and global tensors must match in size and lie on the memory's device")
+    if sum(t.numel() for t in ls) != e.numel():
+        raise ValueError(f"the memory holds {e.numel()} elements, the tensors {sum(t.numel() for t in ls)}")
+    m = max(len(ls), 1)
+    lp = (ctypes.c_void_p * m)(*[t.data_ptr() for t in ls])
+    gp = None if gs is None else ctypes.cast((ctypes.c_void_p * m)(*[t.data_ptr() for t in gs]), ctypes.c_void_p)
+    sz = (ctypes.c_int64 * m)(*[t.numel() for t in ls])
+    with torch.cuda.device(e.device):
+        call("flc_ef_accumulate", ctypes.cast(lp, ctypes.c_void_p), gp, ctypes.cast(sz, ctypes.c_void_p), len(ls),
+             _p(e), _stream(e.device))
+    return e
+
+
+def ef_residual_round(records: Sequence[torch.Tensor], memories: Sequence[torch.Tensor], n: int, k: int,
+                      levels: int) -> None:
+    """``memories[c][idx] -= decode(records[c])`` at every record's kept entries, all clients in one launch
+    (flc_ef_residual_round): the residual ``e' = a − c`` of a round's stacked records, ``a`` held in the memories."""
+    import ctypes
+
+    if len(records) != len(memories):
+        raise ValueError("one memory per record")
+    if not records:
+        return
+    dev = memories[0].device
+    stride, _ = stacked_wire_layout(n, k) if k > 0 else (0, None)
+    for r, e in zip(records, memories):
+        _ef_memory(e, "a memory")
+        if e.numel() != n or e.device != dev:
+            raise ValueError(f"every memory holds n = {n} elements on one device")
+        if r.dtype != torch.uint8 or r.device != dev or not r.is_contiguous() or r.numel() < stride:
+            raise ValueError(f"a wire record is a contiguous uint8 tensor of at least {stride} bytes on the memories' "
+                             "device")
+    C = len(records)
+    rp = (ctypes.c_void_p * C)(*[r.data_ptr() for r in records])
+    ep = (ctypes.c_void_p * C)(*[e.data_ptr() for e in memories])
+    with torch.cuda.device(dev):
+        call("flc_ef_residual_round", ctypes.cast(rp, ctypes.c_void_p), ctypes.cast(ep, ctypes.c_void_p), C, int(n),
+             int(k), int(levels), _stream(dev))
+
+
+def ef_residual_dense(e: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """``e -= c`` in place (flc_ef_residual_dense): the residual of a message that carries its decoded flat vector."""
+    e = _ef_memory(e)
+    c = _ef_input(c, "c")
+    if c.numel() != e.numel() or c.device != e.device:
+        raise ValueError("c must hold the memory's element count on its device")
+    with torch.cuda.device(e.device):
+        call("flc_ef_residual_dense", _p(e), _p(c), e.numel(), _stream(e.device))
+    return e
+
+
+_PYEF: list = []
+
+
+def _pyef():
+    """fl_sim_amd._flcfold.ef_accumulate (flc_ef_accumulate on Python lists of tensors, one C call) when built, else
+    None."""
+    if not _PYEF:
+        try:
+            from . import _flcfold
+
+            _PYEF.append(_flcfold.ef_accumulate)
+        except (ImportError, AttributeError):
+            _PYEF.append(None)
+    return _PYEF[0]
+
+
 # ---------------------------------------------------------------------------------------- float64 inputs
 # The reference runs every compressor on whatever dtype x has (compressors.py:267-410); these are the float64 forms
 # (f64.hip): a float64 HIP vector in, a float64 HIP vector out.  Uniforms as for float32 (compat_u: one double per

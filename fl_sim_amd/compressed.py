@@ -47,6 +47,18 @@ into one of several destinations (θ and c; the message's cluster centre):
 * ``aggregation.scaffold_update`` / ``ifca_update`` recognise a round of stacked records and run
   :func:`fold_record_groups`: every destination's records decoded and folded in ONE ``flc_fold_record_groups`` pass
   (grid = tiles × groups).
+
+Error feedback (``fl_sim_amd/feedback.py``; ``tests/golden/gen_golden_ef.py`` fixes the meaning): with
+``error_feedback`` truthy on the client or its config, every client mixin keeps one
+:class:`~fl_sim_amd.feedback.ErrorMemory` ``e`` per message vector (``client.error_memory(key)``) and sends the message
+of ``a = e + (local − cached)``; the memory takes ``a − c``.  :func:`compress_delta` / :func:`compress_tensors` take
+the memory as ``feedback=``: ``flc_ef_accumulate`` writes ``a`` into it in place, the memory tensor is the deferred
+batch item's flat input (no snapshot), and after the batch's ``flc_stacked_encode_round`` has succeeded one
+``flc_ef_residual_round`` subtracts what the round's records carry at their K kept entries (a batch whose encode raised
+stays pending with its memories holding ``a``; a memory still waiting in a batch when its client communicates again
+has that batch run first).  The immediate stacked paths encode the memory and run the residual with one client; any
+other compressor chain runs on the memory's values, then ``flc_ef_residual_dense``.  ``feedback=None`` is the path
+above, untouched.
 """
 
 from __future__ import annotations
@@ -63,6 +75,7 @@ import torch
 from . import _lib, codec
 from ._lib import FLC_NORM_INF, FLC_Q_STANDARD_DITHER
 from .compressors import Compressor, CompressorType
+from .feedback import ErrorFeedbackClientMixin, ErrorMemory
 
 
 _MSG_CLS: list = []
@@ -198,17 +211,24 @@ def _norm_stage_send(sd: Compressor, norm: torch.Tensor) -> float:
 
 
 def compress_delta(local: Sequence[torch.Tensor], cached: Sequence[torch.Tensor],
-                   compressors: Sequence[Compressor]) -> CompressedDelta:
+                   compressors: Sequence[Compressor], feedback: Optional[ErrorMemory] = None) -> CompressedDelta:
     """The client's compressed delta ``compressors(cat(local − cached))`` (see the module docstring); every compressor's
-    RNG stream and send statistics advance as its own ``compressVector`` call would advance them."""
+    RNG stream and send statistics advance as its own ``compressVector`` call would advance them.  ``feedback``: the
+    client's :class:`~fl_sim_amd.feedback.ErrorMemory` ``e`` for this vector — the message is then that of the input
+    ``a = e + (local − cached)`` and the memory takes ``a − c`` (error feedback; None: nothing remembered)."""
+    if feedback is not None:
+        return _compress_feedback(list(local), cached, compressors, feedback)
     return _compress(list(local), cached, compressors)
 
 
-def compress_tensors(tensors: Sequence[torch.Tensor], compressors: Sequence[Compressor]) -> CompressedDelta:
+def compress_tensors(tensors: Sequence[torch.Tensor], compressors: Sequence[Compressor],
+                     feedback: Optional[ErrorMemory] = None) -> CompressedDelta:
     """``compressors(cat(tensors))`` — :func:`compress_delta` with nothing subtracted (a client's gradient list): the
     stacked pipeline gives a packed record, any other compressor the decoded flat vector; the compressors' RNG streams
     and send statistics advance alike, and in philox mode a deferred message joins the round's batched encode with the
-    flat vector as its snapshot."""
+    flat vector as its snapshot.  ``feedback``: as for :func:`compress_delta` (``a = e + cat(tensors)``)."""
+    if feedback is not None:
+        return _compress_feedback(list(tensors), None, compressors, feedback)
     return _compress(list(tensors), None, compressors)
 
 
@@ -262,6 +282,54 @@ def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]
     return CompressedDelta(shapes, dev, n, flat=out)
 
 
+def _accumulate(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]], e: torch.Tensor, dev) -> None:
+    """``e += cat(local − cached)`` in place (flc_ef_accumulate): one C call on the tensors as they are, or — a tensor
+    it does not take (host-resident, not fp32 or not contiguous) — on their converted copies."""
+    fast = codec._pyef()
+    if fast is not None:
+        try:
+            fast(local, cached, e)
+            return
+        except TypeError:
+            pass  # (nothing launched)
+    codec.ef_accumulate(_fp32_on(local, dev), None if cached is None else _fp32_on(cached, dev), e)
+
+
+def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
+                       compressors: Sequence[Compressor], mem: ErrorMemory) -> CompressedDelta:
+    """:func:`_compress` of ``a = e + (local − cached)`` with the memory ``e`` of ``mem`` as the encoders' flat input,
+    then ``e = a − c`` (fl_sim_amd/feedback.py): the K-entry residual of a stacked record (after the batched encode
+    when the message is deferred), the dense one of any other compressor's decoded vector."""
+    dev = local[0].device if local[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
+    shapes = [t.shape for t in local]
+    n = sum(t.numel() for t in local)
+    if mem.n != n:
+        raise ValueError(f"the error memory holds {mem.n} elements, the message {n}")
+    if mem.device != dev:
+        raise ValueError(f"the error memory is on {mem.device}, the encode on {dev}")
+    mem._settle()  # (the memory's earlier message still waits in a batch: that batch runs first)
+    e = mem._acquire()
+    _accumulate(local, cached, e, dev)
+    pipe = stacked_pipeline(compressors)
+    if pipe is not None and 0 < pipe[0] < n:
+        tk, sd = compressors
+        seed_ctr = None
+        if sd.rng_mode == "philox":
+            seed_ctr = sd.philox.next()
+            if DEFER_ENCODE and n <= _DEFER_MAX_N and _identical(sd.vectorNormCompressor):
+                return _defer(e, shapes, n, pipe[0], pipe[1], tk, sd, dev, seed_ctr, mem)
+        d = _stacked(e, None, shapes, n, pipe[0], pipe[1], tk, sd, dev, seed_ctr)
+        codec.ef_residual_round([d._record], [e], n, pipe[0], pipe[1])
+        return d
+    out = e
+    for comp in compressors:  # the drop-in compressors on the device, in order (each returns a new vector)
+        out = comp.compressVector(out)
+    if out is e or out.data_ptr() == e.data_ptr():  # (no compressor: the message carries a itself, e becomes +0)
+        out = e.clone()
+    codec.ef_residual_dense(e, out)
+    return CompressedDelta(shapes, dev, n, flat=out)
+
+
 # Deferred encodes (philox mode, the stacked pipeline, an identical norm compressor, models up to 16 M parameters).
 # A model-sized encode is all fixed latency on the GPU — ~44 us per message at configs[0] (417,482 parameters), most of
 # it the persistent select's grid exchanges — so a round's messages are encoded together: `communicate` flattens the
@@ -295,7 +363,8 @@ class _Batch:
 
     def __init__(self, key):
         self.key = key
-        # (CompressedDelta, flat delta, seed, count slot, dithering compressor, stream, its handle, counter)
+        # (CompressedDelta, flat delta, seed, count slot, dithering compressor, stream, its handle, counter,
+        #  ErrorMemory whose tensor the flat delta is, or None)
         self.items = []
 
     def run(self) -> None:
@@ -332,12 +401,19 @@ class _Batch:
             else:
                 codec.stacked_encode_batch(flats, k, levels, seeds=seeds, counters=ctrs, counts=cnts, wires=recs)
             codec._after_encode(dev)
+            rows = recs.unbind(0)
+            fed = [(r, it[8]) for it, r in zip(items, rows) if it[8] is not None]
+            if fed:  # error feedback: e = a − c at the records' kept entries, one launch for the round (an encode
+                # that raised never gets here: the memories then still hold a, and the retry encodes the same a)
+                codec.ef_residual_round([r for r, _ in fed], [m._e for _, m in fed], n, k, levels)
             _STATS["batches"] += 1
             _STATS["messages"] += C
-            for (d, flat, _, _, sd, _, sh, _), r in zip(items, recs.unbind(0)):
+            for (d, flat, _, _, sd, _, sh, _, mem), r in zip(items, rows):
                 if sh != ch:
                     flat.record_stream(cur)
                     sd._note_slab_stream(cur)  # (the count was written on this stream, not the slot's own)
+                if mem is not None:
+                    mem._written(cur)
                 d._record, d._batch = r, None
 
 
@@ -365,6 +441,13 @@ def _deferred(local, cached, shapes, n: int, K: int, s: int, tk: Compressor, sd:
             flat = codec.delta_flatten(_fp32_on(local, dev), _fp32_on(cached, dev))
     if flat.device != dev:
         return None
+    return _defer(flat, shapes, n, K, s, tk, sd, dev, seed_ctr, None)
+
+
+def _defer(flat: torch.Tensor, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compressor, dev, seed_ctr,
+           mem: Optional[ErrorMemory]) -> CompressedDelta:
+    """The message of the flat vector ``flat`` joins the round's batched encode (``mem``: ``flat`` is that error
+    memory's tensor, which takes the residual once the batch has encoded)."""
     st = torch.cuda.current_stream(dev)
     cnt = sd._count_slot(dev, st)  # (before the batch is looked up: a full slab is read back, running the batches)
     key = (dev.index, n, K, s)
@@ -372,7 +455,9 @@ def _deferred(local, cached, shapes, n: int, K: int, s: int, tk: Compressor, sd:
     if b is None:
         b = _PENDING[key] = _Batch(key)
     d = CompressedDelta(shapes, dev, n, k=K, levels=s, batch=b)
-    b.items.append((d, flat, seed_ctr[0], cnt, sd, st, st.cuda_stream, seed_ctr[1]))
+    b.items.append((d, flat, seed_ctr[0], cnt, sd, st, st.cuda_stream, seed_ctr[1], mem))
+    if mem is not None:
+        mem._batch = b
     tk._finish(n, tk.K)
     base = _norm_stage_send(sd, None)
     sd._finish_pending(n, cnt, base, (1.0 + np.ceil(math.log2(sd.s))) / 32.0)  # compressors.py:365
@@ -621,16 +706,20 @@ def _compressors_of(node, name: str = "compressors") -> List[Compressor]:
     return [cs] if isinstance(cs, Compressor) else list(cs)
 
 
-class CompressedFedOptClientMixin:
+class CompressedFedOptClientMixin(ErrorFeedbackClientMixin):
     """Mix in before the reference's ``FedOptClient`` (``class C(CompressedFedOptClientMixin, FedOptClient)``):
     ``communicate`` (_fedopt.py:295-308) sends the delta through the client's compressors (``self.compressors``, or
     ``self.config.compressors``: one :class:`~fl_sim_amd.compressors.Compressor` or a sequence applied in order; none
     sends the plain delta).  The server side is :class:`~fl_sim_amd.aggregation.FedOptUpdateMixin`, which folds a
-    round of stacked records in one pass (or any reference server, which reads the message's delta unchanged)."""
+    round of stacked records in one pass (or any reference server, which reads the message's delta unchanged).
+    ``self.error_feedback`` (or ``self.config.error_feedback``) truthy: error feedback through the memory
+    ``self.error_memory("delta_parameters")`` (fl_sim_amd/feedback.py)."""
 
     def communicate(self, target) -> None:
         # (the parameters as they are: the codec only reads them, and every converting path detaches first)
-        delta = compress_delta(list(self.model.parameters()), self._cached_parameters, _compressors_of(self))
+        params = list(self.model.parameters())
+        delta = compress_delta(params, self._cached_parameters, _compressors_of(self),
+                               self._feedback_for("delta_parameters", params))
         target._received_messages.append(
             client_message_class()(
                 **{
@@ -643,7 +732,7 @@ class CompressedFedOptClientMixin:
         )
 
 
-class CompressedSCAFFOLDClientMixin:
+class CompressedSCAFFOLDClientMixin(ErrorFeedbackClientMixin):
     """Mix in before the reference's ``SCAFFOLDClient`` (``class C(CompressedSCAFFOLDClientMixin, SCAFFOLDClient)``):
     ``communicate`` (scaffold/_scaffold.py:210-222) sends ``parameters_delta`` through the client's ``compressors`` and
     ``control_variates_delta`` through its ``control_compressors`` (each looked up on the client, then on its config:
@@ -653,17 +742,19 @@ class CompressedSCAFFOLDClientMixin:
     batched encode, each with its own counter; the deferred encode reads a snapshot of the flat delta taken here, so
     overwriting the control variates afterwards is safe.  The server side is
     :class:`~fl_sim_amd.aggregation.SCAFFOLDUpdateMixin`, which folds both vectors' records in one pass (or any
-    reference server: the compressed deltas read as lists of tensors)."""
+    reference server: the compressed deltas read as lists of tensors).  With ``error_feedback`` the two vectors keep
+    two memories, ``self.error_memory("parameters_delta")`` and ``self.error_memory("control_variates_delta")``."""
 
     def communicate(self, target) -> None:
         cs, ccs = _compressors_of(self), _compressors_of(self, "control_compressors")
         params = list(self.model.parameters())
         if cs:
-            pd = compress_delta(params, self._cached_parameters, cs)
+            pd = compress_delta(params, self._cached_parameters, cs, self._feedback_for("parameters_delta", params))
         else:
             pd = [mp.detach().sub(cp) for mp, cp in zip(params, self._cached_parameters)]
         if ccs:
-            cd = compress_delta(list(self._updated_control_variates), self._control_variates, ccs)
+            ucvs = list(self._updated_control_variates)
+            cd = compress_delta(ucvs, self._control_variates, ccs, self._feedback_for("control_variates_delta", ucvs))
         else:
             cd = [ucv.sub(cv) for ucv, cv in zip(self._updated_control_variates, self._control_variates)]
         target._received_messages.append(
@@ -683,15 +774,17 @@ class CompressedSCAFFOLDClientMixin:
         self._updated_control_variates = None
 
 
-class CompressedIFCAClientMixin:
+class CompressedIFCAClientMixin(ErrorFeedbackClientMixin):
     """Mix in before the reference's ``IFCAClient`` (``class C(CompressedIFCAClientMixin, IFCAClient)``):
     ``communicate`` (ifca/_ifca.py:228-240) sends the delta through the client's compressors
     (:class:`CompressedFedOptClientMixin`'s message) and the client's ``cluster_id`` beside it.  The server side is
     :class:`~fl_sim_amd.aggregation.IFCAUpdateMixin`, which folds every cluster's records in one pass (or any
-    reference server)."""
+    reference server).  ``error_feedback``: as for :class:`CompressedFedOptClientMixin`."""
 
     def communicate(self, target) -> None:
-        delta = compress_delta(list(self.model.parameters()), self._cached_parameters, _compressors_of(self))
+        params = list(self.model.parameters())
+        delta = compress_delta(params, self._cached_parameters, _compressors_of(self),
+                               self._feedback_for("delta_parameters", params))
         target._received_messages.append(
             client_message_class()(
                 **{
@@ -705,16 +798,19 @@ class CompressedIFCAClientMixin:
         )
 
 
-def compress_message_gradients(message, compressors: Sequence[Compressor]) -> None:
+def compress_message_gradients(message, compressors: Sequence[Compressor], feedback=None) -> None:
     """Replace ``message["gradients"]`` (a list of tensors) with the :class:`CompressedDelta` made from them
-    (:func:`compress_tensors`); no compressors, no gradients or gradients already compressed: the message as it is."""
+    (:func:`compress_tensors`); no compressors, no gradients or gradients already compressed: the message as it is.
+    ``feedback``: the client's error memory for the vector, or a callable that makes it from the gradient list (called
+    only when a message is compressed), or None."""
     gs = message.get("gradients")
     if not compressors or gs is None or isinstance(gs, CompressedDelta) or len(gs) == 0:
         return
-    message["gradients"] = compress_tensors(list(gs), compressors)
+    gs = list(gs)
+    message["gradients"] = compress_tensors(gs, compressors, feedback(gs) if callable(feedback) else feedback)
 
 
-class CompressedGradientsClientMixin:
+class CompressedGradientsClientMixin(ErrorFeedbackClientMixin):
     """Mix in before the reference's ``FedProxClient``, ``FedPDClient``, ``ProxSkipClient`` or ``pFedMacClient``
     (``class C(CompressedGradientsClientMixin, FedProxClient)``): the client's own ``communicate``
     (fedprox/_fedprox.py:208-217, fedpd/_fedpd.py:252-275, proxskip/_proxskip.py:265-276, pfedmac/_pfedmac.py:203-212)
@@ -724,7 +820,8 @@ class CompressedGradientsClientMixin:
     A client that skips the round appends nothing, so nothing is compressed and no compressor advances; ``parameters``
     stay as the reference sends them.  The server side is :class:`~fl_sim_amd.aggregation.VRUpdateMixin`, which folds a
     round of stacked records and the dense parameters in one pass (or any reference server: the compressed gradients
-    read as a list of tensors)."""
+    read as a list of tensors).  With ``error_feedback`` the gradients go through the memory
+    ``self.error_memory("gradients")``; a client that skips the round touches no memory."""
 
     def communicate(self, target) -> None:
         received = target._received_messages
@@ -735,4 +832,4 @@ class CompressedGradientsClientMixin:
             return
         for m in target._received_messages[before if target._received_messages is received else 0:]:
             if isinstance(m, dict) and "gradients" in m:
-                compress_message_gradients(m, cs)
+                compress_message_gradients(m, cs, lambda gs: self._feedback_for("gradients", gs))

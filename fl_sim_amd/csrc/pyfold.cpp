@@ -537,6 +537,67 @@ PyObject* delta_flat(PyObject*, PyObject* args) {
   return done(THPVariable_Wrap(out));
 }
 
+// ef_accumulate(local, global_or_None, e): e += cat(local_t - global_t) in place (flc_ef_accumulate; None: e +=
+// cat(local_t)) — an error-feedback message's accumulate into the client's memory (feedback.py), `e` a contiguous fp32
+// HIP tensor holding the tensors' element count.  TypeError (nothing launched) for a tensor that is not a contiguous
+// fp32 HIP tensor of e's device; ValueError for mismatched sizes.
+PyObject* ef_accumulate(PyObject*, PyObject* args) {
+  PyObject *loc, *glo, *mem;
+  if (!PyArg_ParseTuple(args, "OOO", &loc, &glo, &mem)) return nullptr;
+  std::vector<PyObject*> keep;
+  auto done = [&](PyObject* r) {
+    for (PyObject* o : keep) Py_XDECREF(o);
+    return r;
+  };
+  int dev = -1;
+  const at::Tensor* et = usable(mem, &dev);
+  if (!et) return type_error("the memory must be a contiguous fp32 HIP tensor");
+  PyObject* fl = PySequence_Fast(loc, "local must be a sequence of tensors");
+  if (!fl) return nullptr;
+  keep.push_back(fl);
+  PyObject* fg = nullptr;
+  if (glo != Py_None) {
+    fg = PySequence_Fast(glo, "global must be a sequence of tensors or None");
+    if (!fg) return done(nullptr);
+    keep.push_back(fg);
+  }
+  const Py_ssize_t m = PySequence_Fast_GET_SIZE(fl);
+  if (m < 1 || (fg && PySequence_Fast_GET_SIZE(fg) != m))
+    return done(value_error("one global tensor per local tensor, at least one"));
+  std::vector<const float*> lp(m), gp(fg ? m : 0);
+  std::vector<int64_t> sz(m);
+  PyObject** li = PySequence_Fast_ITEMS(fl);
+  PyObject** gi = fg ? PySequence_Fast_ITEMS(fg) : nullptr;
+  int64_t n = 0;
+  for (Py_ssize_t t = 0; t < m; ++t) {
+    const at::Tensor* a = usable(li[t], &dev);
+    const at::Tensor* b = fg ? usable(gi[t], &dev) : nullptr;
+    if (!a || (fg && !b))
+      return done(type_error("local / global tensors must be contiguous fp32 HIP tensors on the memory's device"));
+    if (fg && a->numel() != b->numel()) return done(value_error("local and global tensors must have matching sizes"));
+    lp[t] = a->data_ptr<float>();
+    if (fg) gp[t] = b->data_ptr<float>();
+    sz[t] = a->numel();
+    n += sz[t];
+  }
+  if (et->numel() != n) return done(value_error("the memory must hold the tensors' element count"));
+  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
+  int rc = FLC_OK;
+  float* ep = et->data_ptr<float>();
+  Py_BEGIN_ALLOW_THREADS
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  if (cur != dev) (void)hipSetDevice(dev);
+  rc = flc_ef_accumulate(lp.data(), fg ? gp.data() : nullptr, sz.data(), (int)m, ep, st);
+  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
+  Py_END_ALLOW_THREADS
+  if (rc != FLC_OK) {
+    PyErr_Format(PyExc_RuntimeError, "flc_ef_accumulate failed with status %d: %s", rc, flc_last_error());
+    return done(nullptr);
+  }
+  return done((Py_INCREF(Py_None), Py_None));
+}
+
 // stacked_records_batch(flats, seeds, counter, k, levels, records, counts, ws): the deferred messages of a round in
 // one C call — flc_stacked_encode_batch of the flat deltas into rows of the [C, >= stride] record block (row c equals
 // client c's one-message record), then flc_count_nonzero_at_batch of each delta at its kept indices into counts[c].
@@ -1015,6 +1076,9 @@ PyMethodDef kMethods[] = {
      "flc_avg_and_gradient_records on Python lists (messages: mappings with 'parameters', or None)"},
     {"delta_flat", delta_flat, METH_VARARGS,
      "delta_flat(local, global): a new flat fp32 tensor cat(local - global) (flc_delta_flatten) on the tensors' device"},
+    {"ef_accumulate", ef_accumulate, METH_VARARGS,
+     "ef_accumulate(local, global_or_None, e): e += cat(local - global) in place (flc_ef_accumulate) on the current "
+     "stream of the memory's device"},
     {"stacked_records_round", stacked_records_round, METH_VARARGS,
      "stacked_records_round(flats, seeds, counters, k, levels, records, counts, ws): flc_stacked_encode_round into the "
      "rows of a record block, one Philox counter per message, the send counts written by the encode itself"},

@@ -430,6 +430,36 @@ int flc_delta_count_nonzero_at(const float* const* local, const float* const* gl
 int flc_count_nonzero_at_batch(const float* const* xs, const int32_t* const* idx, int n_clients, int64_t n,
                                int64_t k, int64_t* const* counts, void* stream);
 
+/* ------------------------------------------------------------------ error feedback
+ * A client's residual memory e for a biased compressor (fl_sim_amd/feedback.py): per round and message vector
+ *   a = fp32(e + fp32(local - cached));  c = compressors(a);  e' = fp32(a - c)
+ * with e the flat fp32 vector the encoders read as their input (zero at the start).
+ *
+ * flc_ef_accumulate: e[off_t + i] = e[off_t + i] + (local[t][i] - global[t][i]) in place, off_t = sizes[0] + ... +
+ * sizes[t-1]: two roundings per element, nothing contracted; global == NULL: e[off_t + i] + local[t][i] (a gradient
+ * list).  Bit-identical to flc_delta_flatten into a fresh vector d followed by e = e + d; NaN, +-inf, -0 and denormals
+ * as IEEE addition gives them.  local, global and sizes are HOST arrays (as flc_delta_flatten's); empty tensors are
+ * allowed; more than 48 tensors chain launches.  FLC_EINVAL (nothing launched): null tables, a negative size, a null
+ * pointer for a non-empty tensor (a null e included). */
+int flc_ef_accumulate(const float* const* local, const float* const* global /* NULL: nothing subtracted */,
+                      const int64_t* sizes, int n_tensors, float* e, void* stream);
+/* The residual of a round's stacked records: for every client c and entry j < k of records[c] (the
+ * flc_stacked_wire_layout(n, k) layout), es[c][idx[j]] -= decode(codes[j]) with the record's norm — the decoders' own
+ * dequantisation.  Bit-identical to flc_stacked_decode_tiled(weight 1, accumulate 0) into a zeroed c_dense followed by
+ * es[c] = es[c] - c_dense: an element no entry names is untouched (x - (+0) == x, a -0 included), a zero code leaves
+ * its element as it is, a norm that is 0, +-inf or NaN turns the elements of nonzero codes into NaN.  One launch for
+ * up to 32 clients (more chain); a record's indices are unique, so nothing is atomic.  An entry whose index lies
+ * outside [0, n) is skipped: a record that a failed encode left behind writes nothing outside its memory.  records and
+ * es are HOST arrays of device pointers.  FLC_EINVAL (nothing launched): n_clients < 0, null tables with n_clients >
+ * 0, a null or not 16-B aligned record, a null memory, the same memory for two clients, n or k >= 2^31, k > n, levels
+ * outside [1, 127].  n_clients == 0 or k == 0: the tables are checked, nothing is launched. */
+int flc_ef_residual_round(const void* const* records, float* const* es, int n_clients, int64_t n, int64_t k,
+                          int levels, void* stream);
+/* e[i] = e[i] - c[i], i < n: the residual of a message that carries its decoded flat vector c (every compressor but
+ * the stacked pipeline).  16-B accesses when both pointers are 16-B aligned, 4-B otherwise; the same bits either way.
+ * FLC_EINVAL: n < 0, a null pointer with n > 0, e == c. */
+int flc_ef_residual_dense(float* e, const float* c, int64_t n, void* stream);
+
 /* ------------------------------------------------------------------ aggregation
  * weighted sum of client tensors into dst, in message order, one fmaf per message per element:
  *   init_mode 0: dst = dst * beta   (avg_parameters' inertia, nodes.py:1158-1159;
