@@ -272,6 +272,43 @@ def topk_status_all(reset: bool = True) -> Dict[Tuple[int, int], int]:
     return res
 
 
+_PLAN_FIELDS = ("S", "rank_lo", "rank_hi", "take_all", "G", "M", "ovf", "list_cap", "compact", "cap", "list_all",
+                "hist_bits", "fast_rank", "chunk", "cus")  # FLC_PLAN_* (include/flcodec.h)
+_SEL_FIELDS = ("call", "err", "C", "fallback", "T", "maxkey", "rounds", "t_lo", "t_hi", "need", "ties", "strict",
+               "sample_path")  # FLC_SEL_*
+
+
+def topk_select_plan(n: int, k: int, clients: int = 0, cus: int = 0) -> dict:
+    """The numbers the select will use for a call over ``n`` elements keeping ``k`` (flc_topk_select_plan): sample
+    size and ranks, blocks and elements per block, overflow slots, list capacities.  ``clients`` = 0: the
+    single-client encoders, >= 1: the batched ones.  ``cus`` = 0 reads the current device's CU count; with
+    ``cus`` > 0 no device is touched."""
+    import ctypes
+
+    out = (ctypes.c_int64 * 16)()
+    call("flc_topk_select_plan", int(n), int(k), int(clients), int(cus), out)
+    return {f: int(out[i]) for i, f in enumerate(_PLAN_FIELDS)}
+
+
+def topk_select_stats(device: Optional[torch.device] = None, kind: str = "topk", client: int = 0) -> dict:
+    """What the last select on the cached ``kind`` workspace ("topk": the single-client encoders, "topk_batch": the
+    batched ones, ``client`` its place in the launch) of ``device``'s current stream did (flc_topk_select_stats):
+    ``sample_path`` (0 fast pick, 1 general pick, 2 take-all), the floor / ceiling keys ``t_lo`` / ``t_hi``, the
+    candidates admitted ``C``, ``fallback``, histogram ``rounds``, the k-th largest key ``T``, ``need`` / ``ties`` /
+    ``strict`` and ``maxkey``.  Synchronises the stream."""
+    import ctypes
+
+    if kind not in _TOPK_KINDS:
+        raise ValueError(f"kind must be one of {_TOPK_KINDS}")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    ws = _WS.get((device.index if device.index is not None else torch.cuda.current_device(), _stream(device), kind))
+    if ws is None:
+        raise RuntimeError(f"no {kind!r} workspace on this device and stream yet: run an encode first")
+    out = (ctypes.c_uint64 * 16)()
+    call("flc_topk_select_stats", _p(ws), ws.numel(), int(client), out, _stream(device))
+    return {f: int(out[i]) for i, f in enumerate(_SEL_FIELDS)}
+
+
 def _after_encode(device: torch.device, kinds: Sequence[str] = _TOPK_KINDS) -> None:
     """FLC_TOPK_CHECK: read the sticky error word of the workspaces ``kinds`` (one host synchronisation) and raise
     if a grid-exchange launch lost co-residency; its output would be wrong."""
@@ -1344,3 +1381,20 @@ def topk_dense_f64(x: torch.Tensor, k: int) -> torch.Tensor:
     call("flc_topk_dense_f64", _p(x), x.numel(), int(k), _p(out), _p(ws), ws.numel(), _stream(x.device))
     _after_encode(x.device, ("f64",))
     return out
+
+
+
+def topk_stats_f64(x: torch.Tensor, k: int) -> dict:
+    """What the last ``topk_dense_f64(x, k)`` on x's workspace did (flc_topk_stats_f64; synchronises the stream):
+    ``fb`` (1: the K-th key came from the exact passes over x), ``err``, ``T``, ``need``, ``ties``, ``ithr``,
+    ``nbin``, and that call's band geometry ``S``, ``r_lo``, ``r_hi``, ``on``, ``sample`` (the sample size cap)."""
+    import ctypes
+
+    x = x.reshape(-1)
+    ws = _ws64(x, k)
+    out = (ctypes.c_int64 * 16)()
+    call("flc_topk_stats_f64", _p(ws), ws.numel(), x.numel(), int(k), out, _stream(x.device))
+    names = ("fb", "err", "nbin", "T", "need", "ties", "ithr", "S", "r_lo", "r_hi", "on", "sample")
+    d = {f: int(out[i]) for i, f in enumerate(names)}
+    d["T"] &= (1 << 64) - 1
+    return d

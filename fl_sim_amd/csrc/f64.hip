@@ -1526,6 +1526,41 @@ int flc_topk_dense_f64(const double* x, int64_t n, int64_t k, double* out, void*
   return FLC_OK;
 }
 
+// the select state of the workspace's last flc_topk_dense_f64(n, k), copied to the host, and that call's band
+// geometry (filt64): words as FLC_STATS64_* in include/flcodec.h
+int flc_topk_stats_f64(const void* ws, size_t ws_bytes, int64_t n, int64_t k, int64_t* out, void* stream) {
+  if (!ws || !out) return fail(FLC_EINVAL, "flc_topk_stats_f64: null workspace or output");
+  if (n <= 0 || k <= 0 || k >= n) return fail(FLC_EINVAL, "flc_topk_stats_f64: need 0 < k < n");
+  const Ws64 w = carve64(const_cast<void*>(ws), ws_bytes, n, k);
+  if (w.need > ws_bytes) return fail(FLC_EWORKSPACE, "flc_topk_stats_f64: workspace %zu < %zu", ws_bytes, w.need);
+  constexpr size_t kFrom = offsetof(Sel64, fb), kTo = offsetof(Sel64, flags);
+  struct {
+    int fb, err;
+    unsigned nbin;
+    unsigned long long T;
+    long long need, ties, ithr;
+  } h;
+  static_assert(sizeof(h) == kTo - kFrom, "the state words of Sel64");
+  hipStream_t st = as_stream(stream);
+  FLC_CHECK_HIP(hipMemcpyAsync(&h, reinterpret_cast<const char*>(w.sel) + kFrom, sizeof(h), hipMemcpyDeviceToHost, st));
+  FLC_CHECK_HIP(hipStreamSynchronize(st));
+  const Filt64 f = filt64(n, k);
+  for (int i = 0; i < FLC_STATS64_WORDS; ++i) out[i] = 0;
+  out[FLC_STATS64_FB] = h.fb;
+  out[FLC_STATS64_ERR] = h.err;
+  out[FLC_STATS64_NBIN] = h.nbin;
+  out[FLC_STATS64_T] = (int64_t)h.T;
+  out[FLC_STATS64_NEED] = h.need;
+  out[FLC_STATS64_TIES] = h.ties;
+  out[FLC_STATS64_ITHR] = h.ithr;
+  out[FLC_STATS64_S] = f.S;
+  out[FLC_STATS64_R_LO] = f.r_lo;
+  out[FLC_STATS64_R_HI] = f.r_hi;
+  out[FLC_STATS64_ON] = f.on ? 1 : 0;
+  out[FLC_STATS64_SAMPLE] = kSample64;
+  return FLC_OK;
+}
+
 int flc_f64_status(void* ws, uint64_t* err_out, int reset, void* stream) {
   if (!ws || !err_out) return fail(FLC_EINVAL, "flc_f64_status: null workspace or output");
   hipStream_t st = as_stream(stream);

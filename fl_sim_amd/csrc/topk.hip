@@ -1615,7 +1615,10 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
     if (tid == 0) s_nl = 0u;
     __syncthreads();
     const unsigned lo0 = cur.lo;
-    const unsigned long long wd0 = cur.width;
+    // (clipped at the ceiling: the band's top bin may reach past t_hi — its width need not be a multiple of the bin
+    // width — and the keys at or above t_hi were counted above the band in round 0, so here they count above the
+    // bin and never enter its list)
+    const unsigned long long wd0 = cur.width < t_hi - lo0 ? cur.width : t_hi - lo0;
     // a block's list slots: 32, or more when the select has few blocks (a batched client's 2-4: its in-bin keys per
     // block are many more, and the gathered list still holds kInbinAll)
     const unsigned cap = (unsigned)max(kInbin, min(kInbinMax, kInbinAll / max(w.nb, 1)));
@@ -2744,6 +2747,66 @@ int flc_ring_selftest(const int32_t* ops, int n_ops, int32_t* out, int n_out) {
     }
   }
   return w;
+}
+
+// the numbers a select of this call shape will use (host only; words as FLC_PLAN_* in include/flcodec.h)
+int flc_topk_select_plan(int64_t n, int64_t k, int clients, int cus, int64_t* out) {
+  if (!out) return fail(FLC_EINVAL, "flc_topk_select_plan: null out");
+  if (n <= 0 || n >= (1ll << 31)) return fail(FLC_EINVAL, "flc_topk_select_plan: need 0 < n < 2^31");
+  if (k <= 0 || k >= n)
+    return fail(FLC_EINVAL, "flc_topk_select_plan: need 0 < k < n (got k=%lld, n=%lld)", (long long)k, (long long)n);
+  if (clients < 0 || cus < 0) return fail(FLC_EINVAL, "flc_topk_select_plan: negative clients or cus");
+  if (cus == 0) cus = current_cus(nullptr);
+  if (cus <= 0) return fail(FLC_EINVAL, "flc_topk_select_plan: no device to read the CU count from");
+  EncGeom g;
+  unsigned ovf = 0;
+  int s_max = kSample, chunk = 1, compact = 0;
+  if (clients == 0) {  // launch_topk
+    (void)enc_var_bytes(n, k, cus, &g, &ovf, nullptr);
+    const SampleSetup s0 = sample_setup(n, k);
+    const bool compact_on = !getenv("FLC_COMPACT_SAMPLE") || atoi(getenv("FLC_COMPACT_SAMPLE")) != 0;
+    compact = (compact_on && !s0.take_all && s0.S == kSample) ? 1 : 0;
+  } else {  // launch_topk_batch
+    const BatchGeom bg = batch_geometry(n, k, clients, cus);
+    g = bg.g;
+    ovf = bg.ovf;
+    chunk = bg.chunk;
+    s_max = batch_sample_cap(n);
+  }
+  const SampleSetup ss = sample_setup(n, k, s_max);
+  // (topk_select_kernel's in-bin list slots per block; tests/test_gpu_select_paths.py case l pins the two together)
+  const int cap = std::max(kInbin, std::min(kInbinMax, kInbinAll / std::max(g.G, 1)));
+  for (int i = 0; i < FLC_PLAN_WORDS; ++i) out[i] = 0;
+  out[FLC_PLAN_S] = ss.S;
+  out[FLC_PLAN_RANK_LO] = ss.rank_lo;
+  out[FLC_PLAN_RANK_HI] = ss.rank_hi;
+  out[FLC_PLAN_TAKE_ALL] = ss.take_all;
+  out[FLC_PLAN_G] = g.G;
+  out[FLC_PLAN_M] = g.M;
+  out[FLC_PLAN_OVF] = ovf;
+  out[FLC_PLAN_LIST_CAP] = cap;
+  out[FLC_PLAN_COMPACT] = compact;
+  out[FLC_PLAN_CAP] = kCap;
+  out[FLC_PLAN_LIST_ALL] = kInbinAll;
+  out[FLC_PLAN_HIST_BITS] = kHistBits;
+  out[FLC_PLAN_FAST_RANK] = kET;
+  out[FLC_PLAN_CHUNK] = chunk;
+  out[FLC_PLAN_CUS] = cus;
+  return FLC_OK;
+}
+
+// select `client`'s EncState (16 words) of the workspace's last call, copied to the host
+int flc_topk_select_stats(const void* ws, size_t ws_bytes, int client, uint64_t* out16, void* stream) {
+  if (!ws || !out16) return fail(FLC_EINVAL, "flc_topk_select_stats: null workspace or output");
+  if (client < 0 || ((size_t)client + 1) * kOffStage > ws_bytes)
+    return fail(FLC_EINVAL, "flc_topk_select_stats: client %d has no header in a workspace of %zu bytes", client,
+                ws_bytes);
+  static_assert(sizeof(EncState) == 16 * sizeof(uint64_t), "EncState is 16 words");
+  hipStream_t st = as_stream(stream);
+  const char* src = static_cast<const char*>(ws) + (size_t)client * kOffStage + kOffSt;
+  FLC_CHECK_HIP(hipMemcpyAsync(out16, src, sizeof(EncState), hipMemcpyDeviceToHost, st));
+  FLC_CHECK_HIP(hipStreamSynchronize(st));
+  return FLC_OK;
 }
 
 int flc_topk_status(void* ws, uint64_t* err_out, int reset, void* stream) {

@@ -148,6 +148,38 @@ int flc_natural_decode(const uint16_t* codes, int64_t n, float weight, int accum
  * have shared the device (fl_sim_amd does when FLC_TOPK_CHECK=1, and the GPU tests after every test). */
 /* *err_out (device uint64) = the workspace's sticky error word; reset != 0 clears it (stream-ordered) */
 int flc_topk_status(void* ws, uint64_t* err_out, int reset, void* stream);
+/* Diagnostics of the select (the result never depends on them; tests use them to assert which path a call took).
+ * flc_topk_select_plan: host only (no device call when cus > 0; cus == 0 reads the current device's CU count).
+ * Fills out[FLC_PLAN_WORDS] with the numbers the select uses for a call over n elements keeping k: clients == 0
+ * for the single-client entry points (flc_topk_encode*, flc_stacked_encode*), clients >= 1 for the batched ones. */
+enum {
+  FLC_PLAN_S = 0,        /* sample keys */
+  FLC_PLAN_RANK_LO = 1,  /* the floor is the sample's rank_lo-th largest key */
+  FLC_PLAN_RANK_HI = 2,  /* the ceiling its rank_hi-th largest (0: no ceiling) */
+  FLC_PLAN_TAKE_ALL = 3, /* 1: no sample, every element is a candidate */
+  FLC_PLAN_G = 4,        /* blocks per select */
+  FLC_PLAN_M = 5,        /* elements per block range */
+  FLC_PLAN_OVF = 6,      /* candidates per block kept in HBM beyond LDS_CAP (0: none) */
+  FLC_PLAN_LIST_CAP = 7, /* in-bin keys a block may publish before the select falls to histogram rounds */
+  FLC_PLAN_COMPACT = 8,  /* 1: the floor / ceiling start from the compact sample */
+  FLC_PLAN_CAP = 9,      /* candidates per block kept in LDS */
+  FLC_PLAN_LIST_ALL = 10,/* in-bin keys of all blocks resolved locally */
+  FLC_PLAN_HIST_BITS = 11, /* log2 of the band histogram's bins */
+  FLC_PLAN_FAST_RANK = 12, /* the fast pick runs while rank_lo <= this */
+  FLC_PLAN_CHUNK = 13,   /* batched: clients per launch (their headers are reused by the next launch) */
+  FLC_PLAN_CUS = 14,     /* the CU count used */
+  FLC_PLAN_WORDS = 16
+};
+int flc_topk_select_plan(int64_t n, int64_t k, int clients, int cus, int64_t* out);
+/* The state words the last call on `ws` left for select `client` (0 for a single-client workspace; the client's
+ * place in its launch for a batched one), copied to the HOST array out16 in the order of FLC_SEL_*; synchronises
+ * the stream once. */
+enum {
+  FLC_SEL_CALL = 0, FLC_SEL_ERR = 1, FLC_SEL_C = 2, FLC_SEL_FALLBACK = 3, FLC_SEL_T = 4, FLC_SEL_MAXKEY = 5,
+  FLC_SEL_ROUNDS = 6, FLC_SEL_T_LO = 7, FLC_SEL_T_HI = 8, FLC_SEL_NEED = 9, FLC_SEL_TIES = 10, FLC_SEL_STRICT = 11,
+  FLC_SEL_SAMPLE_PATH = 12 /* 0 fast pick, 1 general radix pick, 2 take-all */
+};
+int flc_topk_select_stats(const void* ws, size_t ws_bytes, int client, uint64_t* out16, void* stream);
 /* Test hook (host only, no device): the batched encoders' pinned table ring (a ring of 32 host slots whose reuse
  * waits for an event recorded after every 8th slot's use, or drains the device) driven by `n_ops` triples
  * (kind, slot, stream id): kind 0 stages the next slot and writes (slot, wait 0 none / 1 event / 2 drain, event slot)
@@ -409,6 +441,18 @@ int flc_topk_dense_f64(const double* x, int64_t n, int64_t k, double* out, void*
  * i.e. its blocks were not all resident — the output of that call is invalid), as flc_topk_status reports the float32
  * encoders'; copied to *err_out (device uint64), zeroed with reset */
 int flc_f64_status(void* ws, uint64_t* err_out, int reset, void* stream);
+/* the select state the last flc_topk_dense_f64(x, n, k, ...) left in `ws` and that call's band geometry, copied to
+ * the HOST array out[FLC_STATS64_WORDS]; synchronises the stream once (diagnostics, as flc_topk_select_stats) */
+enum {
+  FLC_STATS64_FB = 0,    /* 1: T came from the exact passes over x */
+  FLC_STATS64_ERR = 1, FLC_STATS64_NBIN = 2, FLC_STATS64_T = 3, FLC_STATS64_NEED = 4, FLC_STATS64_TIES = 5,
+  FLC_STATS64_ITHR = 6,
+  FLC_STATS64_S = 7, FLC_STATS64_R_LO = 8, FLC_STATS64_R_HI = 9, /* sample keys, floor / ceiling ranks */
+  FLC_STATS64_ON = 10,   /* 1: the sampled band runs for this (n, k) */
+  FLC_STATS64_SAMPLE = 11, /* the sample size cap */
+  FLC_STATS64_WORDS = 16
+};
+int flc_topk_stats_f64(const void* ws, size_t ws_bytes, int64_t n, int64_t k, int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------ client delta
  * FedOptClient.communicate (_fedopt.py:294-297): delta_t = clone(local_t) then add_(global_t, alpha=-1), i.e.

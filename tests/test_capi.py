@@ -98,6 +98,46 @@ def test_topk_status_plumbing_without_gpu(monkeypatch):
     codec._after_encode(None, ("quant",))
 
 
+def test_select_plan_and_stats_validate_without_gpu():
+    """flc_topk_select_plan is host arithmetic (no device call with cus > 0) and, like flc_topk_select_stats and
+    flc_topk_stats_f64, rejects bad arguments before any HIP call."""
+    from fl_sim_amd import codec
+
+    lib = _lib.load()
+    out = (ctypes.c_int64 * 16)()
+    assert lib.flc_topk_select_plan(1 << 20, 1000, 0, 256, None) == 1  # null out
+    assert "null out" in lib.flc_last_error().decode()
+    assert lib.flc_topk_select_plan(-5, 1, 0, 256, out) == 1  # negative n
+    assert lib.flc_topk_select_plan(100, 100, 0, 256, out) == 1 and "0 < k < n" in lib.flc_last_error().decode()
+    assert lib.flc_topk_select_plan(100, 10, -1, 256, out) == 1
+    assert lib.flc_topk_select_plan(100, 10, 0, -3, out) == 1
+    p = codec.topk_select_plan(25_000_000, 250_000, cus=256)
+    assert (p["S"], p["G"], p["M"], p["take_all"], p["cus"]) == (32768, 255, 98304, 0, 256)  # (254.3 block ranges)
+    assert p["M"] * p["G"] >= 25_000_000 and p["M"] % 16384 == 0 and 0 < p["rank_hi"] < 327 < p["rank_lo"] < p["S"]
+    assert p["compact"] == 1 and p["ovf"] == 0 and p["cap"] == 16384 and p["list_cap"] * p["G"] >= p["list_all"]
+    small = codec.topk_select_plan(1000, 10, cus=256)
+    assert small["S"] == 1000 and small["G"] == 1 and small["compact"] == 0 and small["list_cap"] == 256
+    assert codec.topk_select_plan(1000, 990, cus=256)["take_all"] == 1
+    b = codec.topk_select_plan(70_001, 700, clients=3, cus=256)
+    assert b["S"] == 4096 and b["chunk"] == 3 and b["G"] == 5 and b["compact"] == 0
+    assert codec.topk_select_plan(70_001, 700, clients=300, cus=256)["chunk"] == 256
+    assert codec.topk_select_plan(1 << 24, 1 << 14, clients=2, cus=256)["S"] == 32768  # the full sample from 8 M on
+    half = codec.topk_select_plan(1 << 24, 1 << 14, clients=2, cus=304)  # each client on half of the CUs
+    assert half["G"] <= 152 and half["M"] % 16384 == 0 and (half["G"] - 1) * half["M"] < 1 << 24 <= half["G"] * half["M"]
+    st = (ctypes.c_uint64 * 16)()
+    assert lib.flc_topk_select_stats(None, 1 << 30, 0, st, None) == 1  # no workspace
+    assert lib.flc_topk_select_stats(16, 1 << 30, 0, None, None) == 1  # null out
+    assert lib.flc_topk_select_stats(16, 1 << 30, -1, st, None) == 1  # client out of range
+    assert lib.flc_topk_select_stats(16, 4096, 0, st, None) == 1 and "client" in lib.flc_last_error().decode()
+    assert lib.flc_topk_select_stats(16, 1 << 20, 1 << 20, st, None) == 1
+    assert lib.flc_topk_stats_f64(None, 1 << 30, 1 << 20, 100, out, None) == 1
+    assert lib.flc_topk_stats_f64(16, 1 << 30, 1 << 20, 100, None, None) == 1
+    assert lib.flc_topk_stats_f64(16, 1 << 30, 100, 100, out, None) == 1 and "0 < k < n" in lib.flc_last_error().decode()
+    assert lib.flc_topk_stats_f64(16, 64, 1 << 20, 100, out, None) == 3  # workspace too small: FLC_EWORKSPACE
+    with pytest.raises(ValueError):
+        codec.topk_select_stats(kind="quant")
+
+
 def test_stacked_encode_delta_validates_without_gpu():
     """flc_stacked_encode_delta rejects bad tensor tables before touching the device."""
     from fl_sim_amd import _lib

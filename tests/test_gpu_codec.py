@@ -413,6 +413,11 @@ def test_topk_fallback_when_sample_misses():
     x[g.integers(0, n, 500_000)] = g.random(500_000).astype(np.float32) * 1e-3
     idx, val = _topk_device(x, k)
     _check_topk(x, k, idx, val)
+    # the path the test is named after was taken: the floor admitted fewer than k, the whole-grid pass ran
+    codec = _codec()
+    st = codec.topk_select_stats()
+    assert codec.topk_select_plan(n, k)["S"] == S
+    assert st["fallback"] == 1 and st["C"] < k and st["rounds"] > 1, st
 
 
 def test_topk_skewed_region():
@@ -424,6 +429,21 @@ def test_topk_skewed_region():
     k = 50_000
     idx, val = _topk_device(x, k)
     _check_topk(x, k, idx, val)
+    _assert_xmode(x, k)
+
+
+def _assert_xmode(x, k):
+    """The last select over x re-read at least one block's range (more candidates than its LDS and overflow area
+    hold), by the numpy model of tests/select_cases.py at the kernel's own floor and ceiling and the plan's sizes."""
+    from tests import select_cases as sc
+
+    codec = _codec()
+    st = codec.topk_select_stats()
+    plan = codec.topk_select_plan(x.size, k)
+    assert plan["S"] == min(x.size, 32768) or plan["take_all"], plan
+    facts = sc.path_facts(x, k, plan, st["t_lo"], st["t_hi"])
+    assert st["fallback"] == 0 and st["C"] == facts["C"] and st["T"] == facts["T"], (st, plan)
+    assert facts["xmode"], (st, plan, facts["pred"]["C_b"].max())
 
 
 def test_sparse_decode_and_accumulate():
@@ -681,13 +701,15 @@ def _adversarial(name):
         x = (g.standard_normal(5_000_000) * 1e-4).astype(np.float32)
         x[1_000_000:1_100_000] *= 1000
         return x, 50_000
-    g = np.random.default_rng(4)  # ties: a third of the vector holds the k-th value exactly
+    g = np.random.default_rng(4)  # ties: over a quarter of the vector holds one value, two sigma up
     x = (g.standard_normal(3_000_000) * 1e-3).astype(np.float32)
     x[g.integers(0, x.size, 1_000_000)] = np.float32(2e-3)
-    return x, 30_000
+    # (about 49,000 of the other elements lie above the tie value: at k = 30,000 the k-th value is one of those and
+    # the select stays on its fast path; "ties_kth" cuts through the ties themselves)
+    return x, (100_000 if name == "ties_kth" else 30_000)
 
 
-@pytest.mark.parametrize("name", ["fallback", "skewed", "ties"])
+@pytest.mark.parametrize("name", ["fallback", "skewed", "ties", "ties_kth"])
 def test_stacked_adversarial_matches_oracle_with_tiles(name):
     """The stacked codec off its fast path (fallback pass, x-mode blocks, heavy ties): wire, norm, tile pointers
     and decode equal the oracle's and the index pass's."""
@@ -696,6 +718,23 @@ def test_stacked_adversarial_matches_oracle_with_tiles(name):
     n = x.size
     xd = torch.from_numpy(x).to(DEV)
     pkt = codec.stacked_encode(xd, k, 127, seed=7, counter=3)
+    st = codec.topk_select_stats()
+    if name == "fallback":
+        assert st["fallback"] == 1 and st["C"] < k and st["rounds"] > 1, st
+    elif name == "skewed":
+        _assert_xmode(x, k)
+    else:
+        from tests import select_cases as sc
+
+        tie_key, n_ties = int(sc.order_key(np.float32([2e-3]))[0]), int((x == np.float32(2e-3)).sum())
+        assert st["fallback"] == 0 and st["T"] == sc.kth_key(x, k), st
+        if name == "ties_kth":  # far more ties than the in-bin lists hold: a band one key per bin resolves them
+            plan = codec.topk_select_plan(n, k)  # in round 0 (the sample sees the ties), else histogram rounds do
+            facts = sc.path_facts(x, k, plan, st["t_lo"], st["t_hi"])
+            assert n_ties > plan["list_all"] and st["T"] == tie_key and st["ties"] == n_ties, st
+            assert st["C"] == facts["C"] and (st["rounds"] == 1) == facts["rounds_one"], (st, plan)
+        else:
+            assert st["T"] > tie_key, st
     u_all = ref.philox_uniforms(n, 7, 3)
     exp_out, exp_idx, exp_codes, pn = ref.stacked(x, k, 127, lambda idx: u_all[idx])
     assert np.array_equal(pkt.idx.cpu().numpy().astype(np.int64), exp_idx)

@@ -219,21 +219,28 @@ def test_f64_topk_filter_fallbacks():
     x = np.sort(_x64(n, 4))  # the largest values all in the last chunks
     for K in (n // 100, 12_345):
         exp, _ = ref.topk(x, K)
-        assert g64.same_bits(codec.topk_dense_f64(torch.from_numpy(x).to(DEV), K).cpu().numpy(), exp)
+        xd = torch.from_numpy(x).to(DEV)
+        assert g64.same_bits(codec.topk_dense_f64(xd, K).cpu().numpy(), exp)
+        assert codec.topk_stats_f64(xd, K)["fb"] == 1  # a chunk's segment overflowed
     S = 16384  # f64.hip kSample64
     y = np.full(n, -1.0)
     y[((np.arange(S) + 0.5) * n / S).astype(np.int64)] = 0.0  # the sample positions
     # n / 2, S + 5: the floor admits fewer than k; S - 5: the band resolves T = 0 among S ties (tie-index threshold)
     for K in (n // 2, S + 5, S - 5):
         exp, _ = ref.topk(y, K)
-        assert g64.same_bits(codec.topk_dense_f64(torch.from_numpy(y).to(DEV), K).cpu().numpy(), exp)
+        yd = torch.from_numpy(y).to(DEV)
+        assert g64.same_bits(codec.topk_dense_f64(yd, K).cpu().numpy(), exp)
+        st = codec.topk_stats_f64(yd, K)
+        assert st["sample"] == S and st["fb"] == (0 if K == S - 5 else 1), (K, st)
     # the sample's ceiling too low: k + 100 large values, none at a sample position (more than k keys above the band)
     z = y.copy()
     free = np.setdiff1d(np.arange(n), ((np.arange(S) + 0.5) * n / S).astype(np.int64))
     K = 5000
     z[np.random.default_rng(3).choice(free, K + 100, replace=False)] = 5.0
     exp, _ = ref.topk(z, K)
-    assert g64.same_bits(codec.topk_dense_f64(torch.from_numpy(z).to(DEV), K).cpu().numpy(), exp)
+    zd = torch.from_numpy(z).to(DEV)
+    assert g64.same_bits(codec.topk_dense_f64(zd, K).cpu().numpy(), exp)
+    assert codec.topk_stats_f64(zd, K)["fb"] == 1
 
 
 def test_f64_topk_band_top_bin_past_the_ceiling():
@@ -260,8 +267,11 @@ def test_f64_topk_band_top_bin_past_the_ceiling():
     x[free[na:na + nb]] = B
     K = n // 10  # 100,000 A < K <= 110,000 A + B: the K-th largest is a B
     exp, _ = ref.topk(x, K)
-    got = codec.topk_dense_f64(torch.from_numpy(x).to(DEV), K).cpu().numpy()
+    xd = torch.from_numpy(x).to(DEV)
+    got = codec.topk_dense_f64(xd, K).cpu().numpy()
     assert g64.same_bits(got, exp)
+    st = codec.topk_stats_f64(xd, K)  # the band resolved T itself (the path the bug was on), among B's ties
+    assert (st["fb"], st["r_lo"], st["r_hi"], st["ties"], st["need"]) == (0, 1817, 1460, 10_000, K - 100_000), st
     assert sum(codec.topk_status_all().values()) == 0
 
 
