@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("FLC_LIB") or os.path.join(os.path.dirname(os.path.abs
 FLC_OK = 0
 FLC_Q_STANDARD_DITHER = 0
 FLC_Q_NATURAL_DITHER = 1
+FLC_WIRE_NATURAL = 2  # flc_dense_wire_layout's format for the natural compressor's uint16 codes
 FLC_NORM_INF = 0
 FLC_NORM_L2 = 2
 FLC_OPT = {"avg": 0, "adagrad": 1, "yogi": 2, "adam": 3}
@@ -138,6 +139,21 @@ SIGNATURES = {
     "flc_fold_record_groups": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p],
+    ),
+    "flc_dense_wire_layout": (c_size_t, [c_int64, c_int, c_int, c_void_p]),
+    "flc_fold_dense_wires": (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    ),
+    "flc_fedopt_fold_dense_records": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+         c_float, c_int, c_double, c_double, c_double, c_void_p],
+    ),
+    "flc_fold_dense_record_groups": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+         c_void_p],
     ),
     "flc_comm_id_bytes": (c_size_t, []),
     "flc_comm_rccl_origin": (c_char_p, []),

@@ -401,7 +401,7 @@ def fedopt_update(model_params: Sequence[torch.Tensor], delta_parameters: Sequen
     alpha = (1 - betas[0]) / len(messages) if len(messages) else 0.0
     model_params, delta_parameters = list(model_params), list(delta_parameters)
     vps = None if (v_parameters is None or opt == "avg") else list(v_parameters)
-    recs = compressed.stacked_round(messages)  # a round of packed stacked records (the codec's call site)
+    recs = compressed.record_round(messages)  # a round of packed stacked or dense records (the codec's call site)
     if hoststage.is_host(model_params):
         groups = [model_params, delta_parameters] + ([vps] if vps is not None else [])
         n = len(groups)
@@ -448,12 +448,13 @@ def _add_round(dsts: Sequence[torch.Tensor], messages: Sequence[Mapping], key: s
 
 
 def _fold_groups(groups, records=None) -> List[bool]:
-    """compressed.fold_record_groups over ``groups`` (deltas, weights, dsts): the groups whose records share one
-    (n, k, levels) in one pass (SCAFFOLD's two compressor sets may differ); per group, whether it was folded."""
+    """compressed.fold_record_groups over ``groups`` (deltas, weights, dsts): the groups whose records share one codec
+    and shape (``CompressedDelta.codec_key``: stacked records of one (n, k, levels), dense records of one (n, format,
+    levels, bits)) in one pass (SCAFFOLD's two compressor sets may differ); per group, whether it was folded."""
     done = [False] * len(groups)
     shapes: dict = {}
     for i, (ds, _, _) in enumerate(groups):
-        shapes.setdefault((ds[0].n, ds[0].k, ds[0].levels), []).append(i)
+        shapes.setdefault(ds[0].codec_key, []).append(i)
     for ids in shapes.values():
         ok = compressed.fold_record_groups([groups[i] for i in ids],
                                            None if records is None else [records[i] for i in ids])
@@ -468,7 +469,8 @@ def scaffold_update(model_params: Sequence[torch.Tensor], control_variates: Sequ
     so each tensor's fmaf chain (message order) is the same when folded in one launch per tensor.  A round whose
     ``parameters_delta`` and / or ``control_variates_delta`` are stacked records (the codec's call site,
     compressed.CompressedSCAFFOLDClientMixin) folds those vectors from the records in one grouped pass
-    (flc_fold_record_groups: θ and c are its two groups); the other vector, and any other round, takes the dense
+    (flc_fold_record_groups: θ and c are its two groups; flc_fold_dense_record_groups for a round of the plain
+    quantizers' dense records, compressed.dense_record_round); the other vector, and any other round, takes the dense
     path."""
     if len(messages) == 0:
         raise ZeroDivisionError("division by zero")  # ratio_p = lr / len(messages) in the reference
@@ -476,7 +478,7 @@ def scaffold_update(model_params: Sequence[torch.Tensor], control_variates: Sequ
     ratio_c = 1 / num_clients
     model_params, control_variates = list(model_params), list(control_variates)
     keys = ("parameters_delta", "control_variates_delta")
-    recs = [compressed.stacked_round(messages, key) for key in keys]
+    recs = [compressed.record_round(messages, key) for key in keys]
     n = len(messages)
     if hoststage.is_host(model_params):
         msgs = [[[d.record] for d in r] if r is not None else [m[key] for m in messages] for key, r in zip(keys, recs)]
@@ -518,7 +520,8 @@ def ifca_update(cluster_centers: Mapping[int, dict], messages: Sequence[Mapping]
     their cluster, and each member is appended once more while its delta is folded (the reference's duplicate
     entries are kept, so downstream code sees the same lists).  Each center tensor is folded in one launch; a round
     whose messages are all stacked records of one (n, k, levels) (compressed.CompressedIFCAClientMixin) folds every
-    cluster that has messages in one grouped pass (flc_fold_record_groups: the clusters are its groups)."""
+    cluster that has messages in one grouped pass (flc_fold_record_groups: the clusters are its groups), and so does a
+    round of dense records of one (n, format, levels, bits) (flc_fold_dense_record_groups)."""
     prev = {c: list(v["client_ids"]) for c, v in cluster_centers.items()}
     for v in cluster_centers.values():
         v["client_ids"] = []
@@ -531,7 +534,7 @@ def ifca_update(cluster_centers: Mapping[int, dict], messages: Sequence[Mapping]
     collected = set(i for v in cluster_centers.values() for i in v["client_ids"])
     for c, v in cluster_centers.items():
         v["client_ids"].extend(i for i in prev[c] if i not in collected)
-    if not (compressed.stacked_round(messages) is not None and _ifca_records(cluster_centers, members, sizes)):
+    if not (compressed.record_round(messages) is not None and _ifca_records(cluster_centers, members, sizes)):
         for c, ms in members.items():
             center = list(cluster_centers[c]["center_model_params"])
             if hoststage.is_host(center):
@@ -822,7 +825,7 @@ class FedOptUpdateMixin:
 
     def update(self) -> None:
         adaptive = self.v_parameters is not None and self.config.optimizer.lower() != "avg"
-        recs = compressed.stacked_round(self._received_messages)  # (compressed messages: the fold reads the records)
+        recs = compressed.record_round(self._received_messages)  # (compressed messages: the fold reads the records)
         _adopt([list(self.model.parameters()), self.delta_parameters, self.v_parameters if adaptive else None],
                [[d.record] for d in recs] if recs is not None
                else [m["delta_parameters"] for m in self._received_messages])
@@ -835,8 +838,8 @@ class SCAFFOLDUpdateMixin:
     """Device ``update()`` for the reference's ``SCAFFOLDServer`` (_scaffold.py:158-167)."""
 
     def update(self) -> None:
-        recs = (compressed.stacked_round(self._received_messages, "parameters_delta")
-                or compressed.stacked_round(self._received_messages, "control_variates_delta"))
+        recs = (compressed.record_round(self._received_messages, "parameters_delta")
+                or compressed.record_round(self._received_messages, "control_variates_delta"))
         _adopt([list(self.model.parameters()), self._control_variates],
                [[d.record] for d in recs] if recs is not None
                else [m["parameters_delta"] for m in self._received_messages])
@@ -848,7 +851,7 @@ class IFCAUpdateMixin:
     """Device ``update()`` for the reference's ``IFCAServer`` (_ifca.py:167-195)."""
 
     def update(self) -> None:
-        recs = compressed.stacked_round(self._received_messages)  # (compressed messages: the fold reads the records)
+        recs = compressed.record_round(self._received_messages)  # (compressed messages: the fold reads the records)
         if recs is not None:
             _adopt([v["center_model_params"] for v in self._cluster_centers.values()], [[d.record] for d in recs])
         ifca_update(self._cluster_centers, self._received_messages, self.config.num_clusters)

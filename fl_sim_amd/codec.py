@@ -218,6 +218,73 @@ def natural_decode(codes: torch.Tensor, n: int, out: Optional[torch.Tensor] = No
     return out
 
 
+# ---------------------------------------------------------------------------------------- dense records
+_DENSE_LAYOUT: Dict[tuple, tuple] = {}
+
+
+def dense_wire_layout(n: int, fmt: int, bits: int):
+    """(record bytes, {"norm", "codes"} byte offsets) of a dense record (flc_dense_wire_layout): a dithering
+    quantizer's norm and ``bits``-bit codes (``fmt`` FLC_Q_STANDARD_DITHER / FLC_Q_NATURAL_DITHER, bits 2, 4 or 8), or
+    the natural compressor's uint16 codes (``fmt`` FLC_WIRE_NATURAL, bits 16), as one contiguous record."""
+    import ctypes
+
+    key = (int(n), int(fmt), int(bits))
+    r = _DENSE_LAYOUT.get(key)
+    if r is None:
+        off = (ctypes.c_int64 * 2)()
+        total = _lib.size("flc_dense_wire_layout", key[0], key[1], key[2], ctypes.cast(off, ctypes.c_void_p))
+        if total == 0:
+            raise ValueError(f"bad dense record shape n={n}, format={fmt}, bits={bits}")
+        r = _DENSE_LAYOUT[key] = (int(total), {"norm": int(off[0]), "codes": int(off[1])})
+    return r
+
+
+def dense_wire_views(record: torch.Tensor, n: int, fmt: int, bits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(norm, codes) views into a dense record (a contiguous uint8 HIP tensor of at least
+    ``dense_wire_layout(n, fmt, bits)[0]`` bytes, 16-B aligned): the fp32 norm and the uint8 code stream, or the
+    natural compressor's int16 codes."""
+    stride, off = dense_wire_layout(n, fmt, bits)
+    if record.dtype != torch.uint8 or record.device.type != "cuda" or not record.is_contiguous():
+        raise TypeError("a wire record is a contiguous uint8 HIP tensor")
+    rec = record.reshape(-1)
+    if rec.numel() < stride or rec.data_ptr() % 16 != 0:
+        raise ValueError(f"a dense record needs {stride} bytes, 16-B aligned")
+    norm = rec[off["norm"]:off["norm"] + 4].view(torch.float32)
+    if fmt == _lib.FLC_WIRE_NATURAL:
+        return norm, rec[off["codes"]:off["codes"] + 2 * n].view(torch.int16)
+    return norm, rec[off["codes"]:off["codes"] + (n * bits + 7) // 8]
+
+
+def dense_record_decode(record: torch.Tensor, n: int, fmt: int, levels: int, bits: int,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The decoded flat vector of a dense record (flc_quant_decode / flc_natural_decode on its views)."""
+    norm, codes = dense_wire_views(record, n, fmt, bits)
+    if fmt == _lib.FLC_WIRE_NATURAL:
+        return natural_decode(codes, n, out=out)
+    pkt = QuantPacket(codes, norm, 1, n, fmt, levels, bits)
+    return quant_decode(pkt, out=None if out is None else out.reshape(1, n)).reshape(n)
+
+
+def fold_dense_wires(wires: torch.Tensor, slots: Sequence[int], weights: Sequence[float], n: int, fmt: int,
+                     levels: int, bits: int, out: Optional[torch.Tensor] = None,
+                     accumulate: bool = False) -> torch.Tensor:
+    """``out = (accumulate ? out : 0) + Σ_c weights[c] · decode(wires[slots[c]])`` in client order, one pass
+    (flc_fold_dense_wires).  ``wires``: a [records, stride] uint8 HIP tensor of dense records."""
+    import ctypes
+
+    if wires.dtype != torch.uint8 or wires.dim() != 2 or not wires.is_contiguous() or wires.device.type != "cuda":
+        raise TypeError("wires must be a contiguous [records, stride] uint8 HIP tensor")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs an out tensor")
+        out = torch.empty(n, dtype=torch.float32, device=wires.device)
+    m = len(slots)
+    call("flc_fold_dense_wires", _p(wires), wires.shape[1], (ctypes.c_int32 * m)(*[int(s) for s in slots]),
+         (ctypes.c_float * m)(*[float(w) for w in weights]), m, n, fmt, levels, bits, int(accumulate), _p(out),
+         _stream(wires.device))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ top-k
 # FLC_TOPK_CHECK=1: read the persistent encoder's sticky error word after every top-k / stacked encode
 # (one host synchronisation per call) and raise if a call lost co-residency (include/flcodec.h)
@@ -927,6 +994,22 @@ def _pyrecs():
         except (ImportError, AttributeError):
             _PYRECS.append(None)
     return _PYRECS[0]
+
+
+_PYDRECS: list = []
+
+
+def _pydrecs():
+    """fl_sim_amd._flcfold.fold_dense_records (flc_fedopt_fold_dense_records on Python lists, one C call) when built,
+    else None."""
+    if not _PYDRECS:
+        try:
+            from . import _flcfold
+
+            _PYDRECS.append(_flcfold.fold_dense_records)
+        except (ImportError, AttributeError):
+            _PYDRECS.append(None)
+    return _PYDRECS[0]
 
 
 _PYGROUPS: list = []

@@ -17,13 +17,23 @@ What runs here instead:
   instead of the dense delta; in philox mode the delta is formed inside the encoder's read
   (``flc_stacked_encode_delta``), in compat mode the pipeline is composed from the top-k encode and the dithering
   encode of the kept values with the interpreter's ``random`` stream, exactly as the reference consumes it.  Any other
-  compressor runs through the drop-in ``Compressor`` on the device and the message carries the decoded delta.
+  compressor runs through the drop-in ``Compressor`` on the device and the message carries the decoded delta —
+  unless ``wire_records`` is on (looked up on the client, then on its config; ``wire=True`` on
+  :func:`compress_delta` / :func:`compress_tensors`; off by default) and the compressor list is one float32 standard
+  dithering (identical norm compressor), natural dithering or natural compressor (:func:`dense_wire_codec`): the
+  message then carries the quantizer's own wire as a dense record (``flc_dense_wire_layout``: the fp32 norm and the
+  packed 2-, 4- or 8-bit codes, or one uint16 per element), written by the compressor's encoder straight into the
+  record with nothing decoded, the RNG streams and send statistics advancing as ``compressVector`` advances them.
   Either way ``delta_parameters`` is a :class:`CompressedDelta`: a sequence of per-tensor tensors that decodes itself
   on first access, so any server — the reference's own ``update`` included — reads it unchanged.
 * ``aggregation.fedopt_update`` (and :class:`~fl_sim_amd.aggregation.FedOptUpdateMixin`) recognises a round of stacked
   records and runs :func:`fold_records`: ONE launch per 64 clients decodes every record, folds it into δ in message
   order and applies the server optimiser's step (``flc_fedopt_fold_records``) — the records are read once, δ, θ (and
-  v) read and written once; bit-identical to decoding each record and running the reference's update.
+  v) read and written once; bit-identical to decoding each record and running the reference's update.  A round of
+  dense records of one (n, format, levels, bits) (:func:`dense_record_round`) takes the same functions
+  (``flc_fedopt_fold_dense_records``; for SCAFFOLD and IFCA ``flc_fold_dense_record_groups``): the server reads the
+  codes, 1/4 to 1/16 of the dense bytes.  A mixed round, and the variance-reduced servers' ``gradients``, read each
+  message as its decoded tensors.
 
 The compressors' send statistics advance as ``compressVector`` advances them (``compressors.py:406-408``), per stage.
 
@@ -57,8 +67,8 @@ batch item's flat input (no snapshot), and after the batch's ``flc_stacked_encod
 ``flc_ef_residual_round`` subtracts what the round's records carry at their K kept entries (a batch whose encode raised
 stays pending with its memories holding ``a``; a memory still waiting in a batch when its client communicates again
 has that batch run first).  The immediate stacked paths encode the memory and run the residual with one client; any
-other compressor chain runs on the memory's values, then ``flc_ef_residual_dense``.  ``feedback=None`` is the path
-above, untouched.
+other compressor chain runs on the memory's values, then ``flc_ef_residual_dense`` (with ``wire`` on, on the decoded
+dense record, which the message does not keep).  ``feedback=None`` is the path above, untouched.
 """
 
 from __future__ import annotations
@@ -73,7 +83,7 @@ import numpy as np
 import torch
 
 from . import _lib, codec
-from ._lib import FLC_NORM_INF, FLC_Q_STANDARD_DITHER
+from ._lib import FLC_NORM_INF, FLC_NORM_L2, FLC_Q_NATURAL_DITHER, FLC_Q_STANDARD_DITHER, FLC_WIRE_NATURAL
 from .compressors import Compressor, CompressorType
 from .feedback import ErrorFeedbackClientMixin, ErrorMemory
 
@@ -107,34 +117,49 @@ class CompressedDelta(_abc.Sequence):
     """A client's compressed model delta as its message carries it.
 
     ``kind == "stacked"``: the packed wire record of the stacked codec (top-k ascending int32 indices, 8-bit
-    sign | level codes, the kept set's norm, tile pointers); ``kind == "dense"``: the decoded flat delta.  Indexing
-    gives tensor ``j`` of the model's shapes (the decoded values, one flat decode on first access), so code written for
-    a list of delta tensors reads it unchanged."""
+    sign | level codes, the kept set's norm, tile pointers); ``kind == "quant"`` / ``"natural"`` (``wire=True``): the
+    dense record of a dithering quantizer (its norm and packed ``bits``-bit codes) or of the natural compressor (one
+    uint16 per element), ``format`` being flc_dense_wire_layout's; ``kind == "dense"``: the decoded flat delta.
+    Indexing gives tensor ``j`` of the model's shapes (the decoded values, one flat decode on first access), so code
+    written for a list of delta tensors reads it unchanged."""
 
     def __init__(self, shapes: Sequence[torch.Size], device: torch.device, n: int, *, record=None, k: int = 0,
-                 levels: int = 0, flat: Optional[torch.Tensor] = None, batch: Optional["_Batch"] = None):
+                 levels: int = 0, flat: Optional[torch.Tensor] = None, batch: Optional["_Batch"] = None,
+                 format: Optional[int] = None, bits: int = 0):
         self.shapes = [torch.Size(s) for s in shapes]
         self.device = device
         self.n = int(n)
         self._record, self.k, self.levels = record, int(k), int(levels)
         self._batch = batch  # (a deferred encode: the record is made by the batch's launch on first access)
-        self.kind = "stacked" if record is not None or batch is not None else "dense"
+        self.format, self.bits = format, int(bits)
+        if format is not None:
+            self.kind = "natural" if format == FLC_WIRE_NATURAL else "quant"
+        else:
+            self.kind = "stacked" if record is not None or batch is not None else "dense"
         self._flat = flat
         self._views: Optional[List[torch.Tensor]] = None
 
     @property
     def record(self) -> Optional[torch.Tensor]:
-        """The packed wire record (stacked), or None (dense)."""
+        """The packed wire record (stacked, quant, natural), or None (dense)."""
         if self._batch is not None:
             self._batch.run()
         return self._record
 
+    @property
+    def codec_key(self) -> tuple:
+        """What a round's records must share to be folded together."""
+        return (self.kind, self.n, self.k, self.levels, self.format, self.bits)
+
     def __getstate__(self):
-        """A copied or pickled message carries its record (a deferred encode runs first)."""
+        """A copied or pickled message carries its record (a deferred encode runs first); a dense record travels
+        without the decoded vector, which the copy decodes again when it is read."""
         if self._batch is not None:
             self._batch.run()
         d = self.__dict__.copy()
         d["_batch"] = None
+        if self.kind in ("quant", "natural"):
+            d["_flat"] = d["_views"] = None
         return d
 
     @property
@@ -143,9 +168,13 @@ class CompressedDelta(_abc.Sequence):
         return int(self.record.numel()) if self.record is not None else 4 * self.n
 
     def flat(self) -> torch.Tensor:
-        """The decoded flat delta (stacked: flc_stacked_decode_tiled of the record, once)."""
+        """The decoded flat delta (flc_stacked_decode_tiled, flc_quant_decode or flc_natural_decode of the record,
+        once)."""
         if self._flat is None:
-            self._flat = codec.stacked_decode(codec.wire_packet(self.record, self.n, self.k, self.levels))
+            if self.kind in ("quant", "natural"):
+                self._flat = codec.dense_record_decode(self.record, self.n, self.format, self.levels, self.bits)
+            else:
+                self._flat = codec.stacked_decode(codec.wire_packet(self.record, self.n, self.k, self.levels))
         return self._flat
 
     def tensors(self) -> List[torch.Tensor]:
@@ -211,25 +240,116 @@ def _norm_stage_send(sd: Compressor, norm: torch.Tensor) -> float:
 
 
 def compress_delta(local: Sequence[torch.Tensor], cached: Sequence[torch.Tensor],
-                   compressors: Sequence[Compressor], feedback: Optional[ErrorMemory] = None) -> CompressedDelta:
+                   compressors: Sequence[Compressor], feedback: Optional[ErrorMemory] = None,
+                   wire: bool = False) -> CompressedDelta:
     """The client's compressed delta ``compressors(cat(local − cached))`` (see the module docstring); every compressor's
     RNG stream and send statistics advance as its own ``compressVector`` call would advance them.  ``feedback``: the
     client's :class:`~fl_sim_amd.feedback.ErrorMemory` ``e`` for this vector — the message is then that of the input
-    ``a = e + (local − cached)`` and the memory takes ``a − c`` (error feedback; None: nothing remembered)."""
+    ``a = e + (local − cached)`` and the memory takes ``a − c`` (error feedback; None: nothing remembered).  ``wire``:
+    one float32 dithering quantizer or natural compressor (:func:`dense_wire_codec`) sends its dense record — the norm
+    and the packed codes — instead of the decoded vector; any other compressor list is sent as without it."""
     if feedback is not None:
-        return _compress_feedback(list(local), cached, compressors, feedback)
-    return _compress(list(local), cached, compressors)
+        return _compress_feedback(list(local), cached, compressors, feedback, wire)
+    return _compress(list(local), cached, compressors, wire)
 
 
 def compress_tensors(tensors: Sequence[torch.Tensor], compressors: Sequence[Compressor],
-                     feedback: Optional[ErrorMemory] = None) -> CompressedDelta:
+                     feedback: Optional[ErrorMemory] = None, wire: bool = False) -> CompressedDelta:
     """``compressors(cat(tensors))`` — :func:`compress_delta` with nothing subtracted (a client's gradient list): the
-    stacked pipeline gives a packed record, any other compressor the decoded flat vector; the compressors' RNG streams
+    stacked pipeline gives a packed record, any other compressor the decoded flat vector (``wire``: a dithering
+    quantizer's or the natural compressor's dense record); the compressors' RNG streams
     and send statistics advance alike, and in philox mode a deferred message joins the round's batched encode with the
     flat vector as its snapshot.  ``feedback``: as for :func:`compress_delta` (``a = e + cat(tensors)``)."""
     if feedback is not None:
-        return _compress_feedback(list(tensors), None, compressors, feedback)
-    return _compress(list(tensors), None, compressors)
+        return _compress_feedback(list(tensors), None, compressors, feedback, wire)
+    return _compress(list(tensors), None, compressors, wire)
+
+
+def dense_wire_codec(compressors: Sequence[Compressor]) -> Optional[Tuple[int, int, int]]:
+    """(format, levels, bits) of the dense record ``compressors`` sends with ``wire`` on — one float32 compressor:
+    standard dithering with an identical norm compressor and 1..127 levels, natural dithering with 1..127 levels (the
+    code width is ``codec.code_bits(s)``; any p), or the natural compressor (uint16 codes) — else None."""
+    if len(compressors) != 1 or not isinstance(compressors[0], Compressor):
+        return None
+    c = compressors[0]
+    t = c.compressorType
+    if t == CompressorType.NATURAL_COMPRESSOR_FP32:
+        return FLC_WIRE_NATURAL, 0, 16
+    if t == CompressorType.STANDARD_DITHERING_FP32:
+        if not (_identical(c.vectorNormCompressor) and 1 <= c.s <= 127):
+            return None
+        return FLC_Q_STANDARD_DITHER, int(c.s), codec.code_bits(int(c.s))
+    if t == CompressorType.NATURAL_DITHERING_FP32 and 1 <= c.s <= 127:
+        return FLC_Q_NATURAL_DITHER, int(c.s), codec.code_bits(int(c.s))
+    return None
+
+
+def _dense_record(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[int, int, int], dev) -> CompressedDelta:
+    """The dense record of the flat fp32 vector ``x`` under ``comp``: the codes written straight into the record by the
+    compressor's own encoder, nothing decoded.  The RNG streams and send statistics advance exactly as
+    ``comp.compressVector(x)`` advances them (compressors.py:302-325, 327-404): compat mode draws the interpreter's
+    ``random`` stream for the consuming elements; philox mode takes one ``philox.next()`` and leaves a standard
+    dithering's nonzero count in the compressor's pending slab, so nothing synchronises."""
+    fmt, s, bits = dc
+    x = codec._dev_f32(x).reshape(-1)
+    stride, _ = codec.dense_wire_layout(n, fmt, bits)
+    rec = torch.empty(stride, dtype=torch.uint8, device=dev)
+    norm, codes = codec.dense_wire_views(rec, n, fmt, bits)
+    st = codec._stream(dev)
+    compat = comp.rng_mode == "compat"
+    if fmt == FLC_WIRE_NATURAL:
+        seed, ctr = comp.philox.next()
+        u = None
+        if compat:
+            u = comp._uniforms(int(codec.count_consumers(x.reshape(1, n), None).item()), dev)
+        ws = codec.workspace(dev, codec._ws_size(dev, "flc_natural_workspace_size", n), "natural")
+        _lib.call("flc_natural_encode", x.data_ptr(), n, seed, ctr, codec._p(u), codes.data_ptr(), None, ws.data_ptr(),
+                  ws.numel(), st)
+        comp._finish(n, 9.0 / 32.0 * n)  # compressors.py:325
+        return CompressedDelta(shapes, dev, n, record=rec, levels=0, format=fmt, bits=bits)
+    std = fmt == FLC_Q_STANDARD_DITHER
+    per = (1.0 + np.ceil(math.log2(s))) / 32.0  # compressors.py:365 / 404
+    ws = codec.workspace(dev, codec._ws_size(dev, "flc_quant_workspace_size", 1, n), "quant")
+    host_norm = None
+    if comp._wants_host_norm(device_input=True):  # the reference's np.linalg.norm (compressors.py:332 / 372)
+        host_norm = comp._reference_norm(x.detach().cpu().numpy())
+        norm.copy_(torch.tensor([host_norm], dtype=torch.float32), non_blocking=True)
+    seed, ctr = comp.philox.next()
+    if not compat:
+        cnt = comp._count_slot(dev) if std else None
+        if host_norm is None:  # norm and encode together (the record's norm field is the encode's norms output)
+            pk = FLC_NORM_INF if math.isinf(comp.p) else (FLC_NORM_L2 if comp.p == 2 else None)
+            if pk is None:
+                raise ValueError(f"p must be inf or 2 (got {comp.p})")
+            _lib.call("flc_quant_encode_auto", x.data_ptr(), 1, n, fmt, s, bits, pk, seed, ctr, codes.data_ptr(),
+                      norm.data_ptr(), codec._p(cnt), None, ws.data_ptr(), ws.numel(), st)
+            codec._after_encode(dev, ("quant",))
+        else:
+            _lib.call("flc_quant_encode", x.data_ptr(), 1, n, fmt, s, bits, norm.data_ptr(), seed, ctr, None,
+                      codes.data_ptr(), codec._p(cnt), ws.data_ptr(), ws.numel(), st)
+        if std:
+            comp._finish_pending(n, cnt, _norm_stage_send(comp, None), per)
+        else:
+            comp._finish(n, n * per)
+        return CompressedDelta(shapes, dev, n, record=rec, levels=s, format=fmt, bits=bits)
+    if host_norm is None:
+        pk = FLC_NORM_INF if math.isinf(comp.p) else (FLC_NORM_L2 if comp.p == 2 else None)
+        if pk is None:
+            raise ValueError(f"p must be inf or 2 (got {comp.p})")
+        _lib.call("flc_quant_norm", x.data_ptr(), 1, n, pk, norm.data_ptr(), ws.data_ptr(), ws.numel(), st)
+    consumers = int(codec.count_consumers(x.reshape(1, n), norm).item())
+    comp._check_bracket(float(norm.item()), consumers)
+    u = comp._uniforms(consumers, dev)
+    nnz = torch.empty(1, dtype=torch.int64, device=dev) if std else None
+    _lib.call("flc_quant_encode", x.data_ptr(), 1, n, fmt, s, bits, norm.data_ptr(), seed, ctr, u.data_ptr(),
+              codes.data_ptr(), codec._p(nnz), ws.data_ptr(), ws.numel(), st)
+    if std:
+        base = _norm_stage_send(comp, None)
+        nz = int(nnz.item())
+        comp._finish(n, base + nz * per if nz else base)
+    else:
+        comp._finish(n, n * per)
+    return CompressedDelta(shapes, dev, n, record=rec, levels=s, format=fmt, bits=bits)
 
 
 def _flatten(ts: Sequence[torch.Tensor], dev: torch.device) -> torch.Tensor:
@@ -238,7 +358,7 @@ def _flatten(ts: Sequence[torch.Tensor], dev: torch.device) -> torch.Tensor:
 
 
 def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
-              compressors: Sequence[Compressor]) -> CompressedDelta:
+              compressors: Sequence[Compressor], wire: bool = False) -> CompressedDelta:
     """``compressors(cat(local − cached))``, or (``cached`` None) ``compressors(cat(local))``."""
     dev = local[0].device if local[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
     shapes = [t.shape for t in local]
@@ -277,6 +397,9 @@ def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]
         if pipe is not None and 0 < pipe[0] < n:
             return _stacked(ls, gs, shapes, n, pipe[0], pipe[1], compressors[0], compressors[1], dev, seed_ctr)
         out = codec.delta_flatten(ls, gs)
+    dc = dense_wire_codec(compressors) if wire else None
+    if dc is not None:  # the quantizer's own wire as the message: codes written into the record, nothing decoded
+        return _dense_record(out, shapes, n, compressors[0], dc, dev)
     for comp in compressors:  # the drop-in compressors on the device, in order
         out = comp.compressVector(out)
     return CompressedDelta(shapes, dev, n, flat=out)
@@ -296,7 +419,7 @@ def _accumulate(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tenso
 
 
 def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
-                       compressors: Sequence[Compressor], mem: ErrorMemory) -> CompressedDelta:
+                       compressors: Sequence[Compressor], mem: ErrorMemory, wire: bool = False) -> CompressedDelta:
     """:func:`_compress` of ``a = e + (local − cached)`` with the memory ``e`` of ``mem`` as the encoders' flat input,
     then ``e = a − c`` (fl_sim_amd/feedback.py): the K-entry residual of a stacked record (after the batched encode
     when the message is deferred), the dense one of any other compressor's decoded vector."""
@@ -320,6 +443,11 @@ def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torc
                 return _defer(e, shapes, n, pipe[0], pipe[1], tk, sd, dev, seed_ctr, mem)
         d = _stacked(e, None, shapes, n, pipe[0], pipe[1], tk, sd, dev, seed_ctr)
         codec.ef_residual_round([d._record], [e], n, pipe[0], pipe[1])
+        return d
+    dc = dense_wire_codec(compressors) if wire else None
+    if dc is not None:  # the message carries the record; the memory takes a − decode(record) (these quantizers are
+        d = _dense_record(e, shapes, n, compressors[0], dc, dev)  # unbiased: the plain dense residual)
+        codec.ef_residual_dense(e, codec.dense_record_decode(d._record, n, dc[0], dc[1], dc[2]))
         return d
     out = e
     for comp in compressors:  # the drop-in compressors on the device, in order (each returns a new vector)
@@ -559,6 +687,27 @@ def stacked_round(messages: Sequence, key: str = "delta_parameters") -> Optional
     return ds
 
 
+def dense_record_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
+    """The messages' compressed deltas when every one is a dense record (``kind`` "quant" or "natural") of one
+    (n, format, levels, bits), else None (a mixed round: each message then decodes itself)."""
+    if not messages:
+        return None
+    ds = []
+    for m in messages:
+        d = m.get(key) if isinstance(m, dict) else None
+        if not isinstance(d, CompressedDelta) or d.kind not in ("quant", "natural"):
+            return None
+        ds.append(d)
+    if any(d.codec_key != ds[0].codec_key for d in ds):
+        return None
+    return ds
+
+
+def record_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
+    """:func:`stacked_round` or :func:`dense_record_round`: a round the record folds take, else None."""
+    return stacked_round(messages, key) or dense_record_round(messages, key)
+
+
 def fold_records(deltas: Sequence[CompressedDelta], weights: Sequence[float], delta_params: Sequence[torch.Tensor],
                  theta: Optional[Sequence[torch.Tensor]], v: Optional[Sequence[torch.Tensor]], beta0: float,
                  opt: str = "avg", lr: float = 1.0, beta2: float = 0.0, tau: float = 0.0) -> bool:
@@ -567,10 +716,12 @@ def fold_records(deltas: Sequence[CompressedDelta], weights: Sequence[float], de
     of one HIP device holding the records' element count (the caller then takes the dense path)."""
     dps = list(delta_params)
     d0 = deltas[0]
-    fast = codec._pyrecs()
+    dense = d0.kind != "stacked"  # (a dense_record_round: flc_fedopt_fold_dense_records, the same contract)
+    shape = (d0.n, d0.format, d0.levels, d0.bits) if dense else (d0.n, d0.k, d0.levels)
+    fast = codec._pydrecs() if dense else codec._pyrecs()
     if fast is not None and dps:
         try:  # one C call: every tensor checked in place; TypeError: nothing launched, the checks below decide
-            fast([d.record for d in deltas], [float(w) for w in weights], d0.n, d0.k, d0.levels, dps,
+            fast([d.record for d in deltas], [float(w) for w in weights], *shape, dps,
                  None if theta is None else list(theta), None if v is None else list(v), float(beta0),
                  _lib.FLC_OPT[opt], float(lr), float(beta2), float(tau))
             return True
@@ -590,8 +741,9 @@ def fold_records(deltas: Sequence[CompressedDelta], weights: Sequence[float], de
         return False
     recs = [d.record if d.record.device == dev else d.record.to(dev) for d in deltas]
     m, T = len(recs), len(dps)
-    _lib.call("flc_fedopt_fold_records", _ptrs(recs), (ctypes.c_float * m)(*[float(w) for w in weights]), m, d0.n,
-              d0.k, d0.levels, _ptrs(dps), _ptrs(groups[1]) if theta is not None else None,
+    _lib.call("flc_fedopt_fold_dense_records" if dense else "flc_fedopt_fold_records", _ptrs(recs),
+              (ctypes.c_float * m)(*[float(w) for w in weights]), m, *shape, _ptrs(dps),
+              _ptrs(groups[1]) if theta is not None else None,
               _ptrs(groups[2]) if v is not None else None, (ctypes.c_int64 * T)(*[t.numel() for t in dps]), T,
               float(beta0), _lib.FLC_OPT[opt], float(lr), float(beta2), float(tau), codec._stream(dev))
     return True
@@ -652,11 +804,13 @@ def fold_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequenc
     if not live:
         return True
     d0 = live[0][0][0]
-    if any((d.n, d.k, d.levels) != (d0.n, d0.k, d0.levels) for ds, _, _, _ in live for d in ds):
+    if d0.kind == "dense" or any(d.codec_key != d0.codec_key for ds, _, _, _ in live for d in ds):
         return False
     if any(len(ws) != len(ds) or (rs is not None and len(rs) != len(ds)) for ds, ws, _, rs in live):
         return False
-    fast = codec._pygroups()
+    dense = d0.kind != "stacked"  # (dense records: flc_fold_dense_record_groups through ctypes, the same contract)
+    shape = (d0.n, d0.format, d0.levels, d0.bits) if dense else (d0.n, d0.k, d0.levels)
+    fast = None if dense else codec._pygroups()
     if fast is not None:
         try:  # one C call: every tensor checked in place; TypeError: nothing launched, the checks below decide
             fast([[d.record for d in ds] if rs is None else rs for ds, _, _, rs in live],
@@ -692,8 +846,9 @@ def fold_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequenc
         dsts += dst
     m, T = len(recs), len(sizes)
     with torch.cuda.device(dev):
-        _lib.call("flc_fold_record_groups", _ptrs(recs), (ctypes.c_float * m)(*ws), (ctypes.c_int32 * m)(*gof), m,
-                  d0.n, d0.k, d0.levels, _ptrs(dsts), len(live), (ctypes.c_int64 * T)(*sizes), T, codec._stream(dev))
+        _lib.call("flc_fold_dense_record_groups" if dense else "flc_fold_record_groups", _ptrs(recs),
+                  (ctypes.c_float * m)(*ws), (ctypes.c_int32 * m)(*gof), m, *shape, _ptrs(dsts), len(live),
+                  (ctypes.c_int64 * T)(*sizes), T, codec._stream(dev))
     return True
 
 
@@ -704,6 +859,15 @@ def _compressors_of(node, name: str = "compressors") -> List[Compressor]:
     if cs is None:
         return []
     return [cs] if isinstance(cs, Compressor) else list(cs)
+
+
+def _wire_records(node) -> bool:
+    """``wire_records`` looked up on the client, then on its config (as ``error_feedback`` is); absent or false: the
+    dithering quantizers and the natural compressor send their decoded vectors."""
+    v = getattr(node, "wire_records", None)
+    if v is None:
+        v = getattr(getattr(node, "config", None), "wire_records", None)
+    return bool(v)
 
 
 class CompressedFedOptClientMixin(ErrorFeedbackClientMixin):
@@ -719,7 +883,7 @@ class CompressedFedOptClientMixin(ErrorFeedbackClientMixin):
         # (the parameters as they are: the codec only reads them, and every converting path detaches first)
         params = list(self.model.parameters())
         delta = compress_delta(params, self._cached_parameters, _compressors_of(self),
-                               self._feedback_for("delta_parameters", params))
+                               self._feedback_for("delta_parameters", params), wire=_wire_records(self))
         target._received_messages.append(
             client_message_class()(
                 **{
@@ -749,12 +913,14 @@ class CompressedSCAFFOLDClientMixin(ErrorFeedbackClientMixin):
         cs, ccs = _compressors_of(self), _compressors_of(self, "control_compressors")
         params = list(self.model.parameters())
         if cs:
-            pd = compress_delta(params, self._cached_parameters, cs, self._feedback_for("parameters_delta", params))
+            pd = compress_delta(params, self._cached_parameters, cs, self._feedback_for("parameters_delta", params),
+                                wire=_wire_records(self))
         else:
             pd = [mp.detach().sub(cp) for mp, cp in zip(params, self._cached_parameters)]
         if ccs:
             ucvs = list(self._updated_control_variates)
-            cd = compress_delta(ucvs, self._control_variates, ccs, self._feedback_for("control_variates_delta", ucvs))
+            cd = compress_delta(ucvs, self._control_variates, ccs, self._feedback_for("control_variates_delta", ucvs),
+                                wire=_wire_records(self))
         else:
             cd = [ucv.sub(cv) for ucv, cv in zip(self._updated_control_variates, self._control_variates)]
         target._received_messages.append(
@@ -784,7 +950,7 @@ class CompressedIFCAClientMixin(ErrorFeedbackClientMixin):
     def communicate(self, target) -> None:
         params = list(self.model.parameters())
         delta = compress_delta(params, self._cached_parameters, _compressors_of(self),
-                               self._feedback_for("delta_parameters", params))
+                               self._feedback_for("delta_parameters", params), wire=_wire_records(self))
         target._received_messages.append(
             client_message_class()(
                 **{
@@ -798,7 +964,7 @@ class CompressedIFCAClientMixin(ErrorFeedbackClientMixin):
         )
 
 
-def compress_message_gradients(message, compressors: Sequence[Compressor], feedback=None) -> None:
+def compress_message_gradients(message, compressors: Sequence[Compressor], feedback=None, wire: bool = False) -> None:
     """Replace ``message["gradients"]`` (a list of tensors) with the :class:`CompressedDelta` made from them
     (:func:`compress_tensors`); no compressors, no gradients or gradients already compressed: the message as it is.
     ``feedback``: the client's error memory for the vector, or a callable that makes it from the gradient list (called
@@ -807,7 +973,7 @@ def compress_message_gradients(message, compressors: Sequence[Compressor], feedb
     if not compressors or gs is None or isinstance(gs, CompressedDelta) or len(gs) == 0:
         return
     gs = list(gs)
-    message["gradients"] = compress_tensors(gs, compressors, feedback(gs) if callable(feedback) else feedback)
+    message["gradients"] = compress_tensors(gs, compressors, feedback(gs) if callable(feedback) else feedback, wire)
 
 
 class CompressedGradientsClientMixin(ErrorFeedbackClientMixin):
@@ -832,4 +998,4 @@ class CompressedGradientsClientMixin(ErrorFeedbackClientMixin):
             return
         for m in target._received_messages[before if target._received_messages is received else 0:]:
             if isinstance(m, dict) and "gradients" in m:
-                compress_message_gradients(m, cs, lambda gs: self._feedback_for("gradients", gs))
+                compress_message_gradients(m, cs, lambda gs: self._feedback_for("gradients", gs), _wire_records(self))

@@ -345,6 +345,20 @@ __device__ __forceinline__ int level_lower_bound(float yf, int s, double step) {
   }
 }
 
+// a norm the dithering codecs divide by and scale with: positive and finite (anything else — 0, +-inf, NaN, negative —
+// encodes to code 0 / 1 and decodes to +0 / NaN, as the reference's arithmetic does)
+__device__ __forceinline__ bool norm_regular(float nrm) { return nrm > 0.0f && nrm <= 3.402823466e38f; }
+
+// decoded value of a natural-compressor code (compressors.py:302-325): 0 = zero, 0x7fff = NaN, else
+// sign << 15 | (e + 150) for the power of two 2^e
+__device__ __forceinline__ float natural_value(uint32_t code) {
+  if (code == 0u) return 0.0f;
+  if (code == 0x7fffu) return __uint_as_float(0x7fc00000u);
+  const int e = (int)(code & 0x7fffu) - 150;
+  const float v = ldexpf(1.0f, e);
+  return (code >> 15) ? -v : v;
+}
+
 // decoded value of a stacked-codec code byte (sign << 7 | level) with the kept set's norm (compressors.py:357:
 // fp32(fp32(lv) * sign) * norm); a non-regular norm decodes every nonzero code to NaN
 __device__ __forceinline__ float stacked_dequant(uint32_t code, int levels, double step, float nrm) {

@@ -39,14 +39,6 @@ __device__ __forceinline__ uint32_t natural_code(float xv, double u) {
   return (sign << 15) | (uint32_t)(e + 150);
 }
 
-__device__ __forceinline__ float natural_value(uint32_t code) {
-  if (code == 0u) return 0.0f;
-  if (code == 0x7fffu) return __uint_as_float(0x7fc00000u);
-  const int e = (int)(code & 0x7fffu) - 150;
-  const float v = ldexpf(1.0f, e);
-  return (code >> 15) ? -v : v;
-}
-
 __device__ __forceinline__ void load8(const float* __restrict__ x, int64_t e0, int valid, float v[kGroup]) {
   if (valid == kGroup) {
     const float4 a = *reinterpret_cast<const float4*>(x + e0);

@@ -720,14 +720,10 @@ PyObject* stacked_records_round(PyObject*, PyObject* args) { return stacked_reco
 // not what the pass takes — the server tensors contiguous fp32 HIP tensors of one device summing to n, the records
 // 16-B aligned uint8 tensors of at least the wire layout's bytes on that device — so the caller can take its other
 // path; theta / v None: the fold alone / no second moment.
-PyObject* fold_records(PyObject*, PyObject* args) {
-  PyObject *recs, *weights, *delta, *theta, *v;
-  long long n, k;
-  int levels, opt;
-  double beta0, lr, beta2, tau;
-  if (!PyArg_ParseTuple(args, "OOLLiOOOdiddd", &recs, &weights, &n, &k, &levels, &delta, &theta, &v, &beta0, &opt, &lr,
-                        &beta2, &tau))
-    return nullptr;
+// (format < 0: stacked records of (n, k, levels); else dense records of (n, format, levels, bits))
+PyObject* fold_records_of(PyObject* recs, PyObject* weights, long long n, long long k, int format, int levels, int bits,
+                          PyObject* delta, PyObject* theta, PyObject* v, double beta0, int opt, double lr, double beta2,
+                          double tau) {
   std::vector<PyObject*> keep;
   auto done = [&](PyObject* r) {
     for (PyObject* o : keep) Py_XDECREF(o);
@@ -773,7 +769,7 @@ PyObject* fold_records(PyObject*, PyObject* args) {
     }
   }
   int64_t off[4];
-  const size_t stride = flc_stacked_wire_layout(n, k, off);
+  const size_t stride = format < 0 ? flc_stacked_wire_layout(n, k, off) : flc_dense_wire_layout(n, format, bits, off);
   if (stride == 0) return done(value_error("bad wire shape"));
   std::vector<const void*> rp(nr);
   std::vector<float> w(nr);
@@ -794,16 +790,45 @@ PyObject* fold_records(PyObject*, PyObject* args) {
   int cur = -1;
   (void)hipGetDevice(&cur);
   if (cur != dev) (void)hipSetDevice(dev);
-  rc = flc_fedopt_fold_records(rp.data(), w.data(), (int)nr, n, k, levels, dp.data(), tp.empty() ? nullptr : tp.data(),
-                               vp.empty() ? nullptr : vp.data(), sz.data(), (int)nt, (float)beta0, opt, lr, beta2, tau,
-                               st);
+  if (format < 0)
+    rc = flc_fedopt_fold_records(rp.data(), w.data(), (int)nr, n, k, levels, dp.data(),
+                                 tp.empty() ? nullptr : tp.data(), vp.empty() ? nullptr : vp.data(), sz.data(), (int)nt,
+                                 (float)beta0, opt, lr, beta2, tau, st);
+  else
+    rc = flc_fedopt_fold_dense_records(rp.data(), w.data(), (int)nr, n, format, levels, bits, dp.data(),
+                                       tp.empty() ? nullptr : tp.data(), vp.empty() ? nullptr : vp.data(), sz.data(),
+                                       (int)nt, (float)beta0, opt, lr, beta2, tau, st);
   if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
   Py_END_ALLOW_THREADS
   if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "flc_fedopt_fold_records failed with status %d: %s", rc, flc_last_error());
+    PyErr_Format(PyExc_RuntimeError, "%s failed with status %d: %s",
+                 format < 0 ? "flc_fedopt_fold_records" : "flc_fedopt_fold_dense_records", rc, flc_last_error());
     return done(nullptr);
   }
   return done((Py_INCREF(Py_None), Py_None));
+}
+PyObject* fold_records(PyObject*, PyObject* args) {
+  PyObject *recs, *weights, *delta, *theta, *v;
+  long long n, k;
+  int levels, opt;
+  double beta0, lr, beta2, tau;
+  if (!PyArg_ParseTuple(args, "OOLLiOOOdiddd", &recs, &weights, &n, &k, &levels, &delta, &theta, &v, &beta0, &opt, &lr,
+                        &beta2, &tau))
+    return nullptr;
+  return fold_records_of(recs, weights, n, k, -1, levels, 0, delta, theta, v, beta0, opt, lr, beta2, tau);
+}
+// fold_dense_records(records, weights, n, format, levels, bits, delta, theta, v, beta0, opt, lr, beta2, tau): the same
+// for a round of dense records (flc_fedopt_fold_dense_records; the flc_dense_wire_layout(n, format, bits) layout)
+PyObject* fold_dense_records(PyObject*, PyObject* args) {
+  PyObject *recs, *weights, *delta, *theta, *v;
+  long long n;
+  int format, levels, bits, opt;
+  double beta0, lr, beta2, tau;
+  if (!PyArg_ParseTuple(args, "OOLiiiOOOdiddd", &recs, &weights, &n, &format, &levels, &bits, &delta, &theta, &v, &beta0,
+                        &opt, &lr, &beta2, &tau))
+    return nullptr;
+  if (format < 0) return value_error("bad wire shape");
+  return fold_records_of(recs, weights, n, 0, format, levels, bits, delta, theta, v, beta0, opt, lr, beta2, tau);
 }
 
 // fold_record_groups(records, weights, dsts, n, k, levels): a round whose stacked records fall into groups, each
@@ -1068,6 +1093,9 @@ PyMethodDef kMethods[] = {
     {"fold_records", fold_records, METH_VARARGS,
      "fold_records(records, weights, n, k, levels, delta, theta, v, beta0, opt, lr, beta2, tau): "
      "flc_fedopt_fold_records on Python lists"},
+    {"fold_dense_records", fold_dense_records, METH_VARARGS,
+     "fold_dense_records(records, weights, n, format, levels, bits, delta, theta, v, beta0, opt, lr, beta2, tau): "
+     "flc_fedopt_fold_dense_records on Python lists"},
     {"fold_record_groups", fold_record_groups, METH_VARARGS,
      "fold_record_groups(records, weights, dsts, n, k, levels): flc_fold_record_groups on Python lists (one sequence "
      "per group)"},

@@ -154,8 +154,6 @@ __global__ __launch_bounds__(kWave) void quant_norm_fold_kernel(int parts, Quant
 // ------------------------------------------------------------------------------------------------
 // per-element quantizer
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool norm_regular(float nrm) { return nrm > 0.0f && nrm <= 3.402823466e38f; }
-
 // consumer = the reference draws random.random() for this element (compressors.py:339-354)
 __device__ __forceinline__ bool consumes(float xv, float nrm) {
   if (xv == 0.0f) return false;

@@ -28,6 +28,14 @@
 // optimiser's step) and flc_avg_and_gradient_records (PairIO: a variance-reduced round's gradients from records, the
 // dense parameters folded in the same pass) and flc_fold_record_groups (GroupIO: the launch's records fall into
 // groups, each folded in place into its own model — SCAFFOLD's two vectors, IFCA's clusters).
+//
+// Dense records (flc_dense_wire_layout): the dithering quantizers' and the natural compressor's wire — one fp32 norm
+// and the packed 2-, 4- or 8-bit codes, or one uint16 per element — as the message's record.  Their fold
+// (dense_fold_records_kernel, below the stacked one) shares the IO policies: one wave per tile, the accumulator in
+// registers as IO::load lays it out, every record's code words of the tile loaded before the ordered fma chain, each
+// code decoded as flc_quant_decode / flc_natural_decode decode it.  flc_fold_dense_wires (FlatIO),
+// flc_fedopt_fold_dense_records (ModelIO) and flc_fold_dense_record_groups (GroupIO) are the stacked entry points'
+// counterparts; a variance-reduced round's gradients (PairIO) have none: such messages decode themselves.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -569,6 +577,163 @@ __global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, W
   io.store(t0, lane, acc);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Dense records: the dithering quantizers' and the natural compressor's wire as one record per client
+//   [0, 4)             norm   fp32 (unused by the natural compressor)
+//   [16, 16 + bytes)   codes  `bits` bits per element (2, 4 or 8: sign << (bits-1) | level, element i at bit i * bits),
+//                             or one uint16 per element (the natural compressor); bytes = ceil(n * bits / 8)
+// padded to 256 B.  The fold reads every client's codes of a tile — four elements per lane and float4 group, the
+// accumulator's own layout, so 1/4 .. 1/16 of the dense vector's bytes — and applies the ordered chain
+// a = fmaf(w_c, v_c, a) with v_c the decoders' value of the code (dequant<KIND, BITS> in quant.hip, natural_value).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kFmtNatural = 2;  // FLC_WIRE_NATURAL (0 / 1: FLC_Q_STANDARD_DITHER / FLC_Q_NATURAL_DITHER)
+constexpr long long kDenseNorm = 0, kDenseCodes = 16;
+
+struct DenseCodec {
+  int format, levels, bits;
+  int64_t n;
+};
+
+size_t dense_wire_size(int64_t n, int format, int bits) {
+  const size_t code_bytes = format == kFmtNatural ? 2 * (size_t)n : ((size_t)n * (size_t)bits + 7) / 8;
+  return align_up((size_t)kDenseCodes + code_bytes, 256);
+}
+
+// the codes of four consecutive elements (e % 4 == 0): one aligned word of the code stream.  The word of the last
+// group of a record may reach into the record's padding (the record ends on a 256-B boundary): those elements lie at
+// or beyond n and are never stored.
+template <int BITS>
+struct Quad {
+  typedef uint32_t type;
+};
+template <>
+struct Quad<16> {
+  typedef uint2 type;
+};
+template <int BITS>
+__device__ __forceinline__ typename Quad<BITS>::type load_quad(const uint8_t* __restrict__ codes, int64_t e) {
+  const uint8_t* p = codes + ((e * BITS) >> 3);
+  if constexpr (BITS == 16) return *reinterpret_cast<const uint2*>(p);
+  else if constexpr (BITS == 8) return *reinterpret_cast<const uint32_t*>(p);
+  else if constexpr (BITS == 4) return (uint32_t)*reinterpret_cast<const uint16_t*>(p);
+  else return (uint32_t)*p;
+}
+template <int BITS>
+__device__ __forceinline__ uint32_t quad_code(const typename Quad<BITS>::type& q, int j) {
+  if constexpr (BITS == 16) return ((j < 2 ? q.x : q.y) >> (16 * (j & 1))) & 0xffffu;
+  else return (q >> (j * BITS)) & ((1u << BITS) - 1u);
+}
+
+// KIND 0 / 1: standard / natural dithering with BITS-bit codes; KIND 2: the natural compressor's uint16 codes.
+// One wave per FLC_TILE tile; the launch's records in batches of kBatch: the batch's code words are all issued (four
+// loads per record and lane), then the ordered chain runs over them — a round of up to kBatch clients is one batch.
+// fp32(level value) comes from an LDS table of all 2^(BITS-1) level fields (dequant's (float)level_value, as
+// quant_fused_kernel's s_lvt), so a code decodes exactly as flc_quant_decode decodes it, whatever its level field.
+template <int KIND, int BITS, class IO>
+__global__ __launch_bounds__(kWave) void dense_fold_records_kernel(FoldArgs a, int nw_all, int s, double step,
+                                                                   int64_t n, int64_t tile0, IO io) {
+  typedef typename Quad<BITS>::type Q;
+  constexpr int kLv = KIND == kFmtNatural ? 1 : (1 << (BITS - 1));
+  constexpr int kBatch = BITS == 16 ? 8 : 16;
+  __shared__ float s_lvt[kLv];
+  const int lane = threadIdx.x;
+  if constexpr (KIND != kFmtNatural) {
+    for (int i = lane; i < kLv; i += kWave) s_lvt[i] = (float)level_value<KIND>(i, s, step);
+    __syncthreads();
+  }
+  int nw = nw_all, rec0 = 0;
+  if constexpr (IO::kGrouped) {
+    nw = io.count();
+    rec0 = io.first();
+  }
+  const int64_t t0 = (tile0 + blockIdx.x) * FLC_TILE;
+  float4 acc[4];
+  io.load(t0, lane, acc);
+  for (int c0 = 0; c0 < nw; c0 += kBatch) {
+    Q cw[kBatch][4];
+    float nr[kBatch];
+#pragma unroll
+    for (int i = 0; i < kBatch; ++i) {
+      nr[i] = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) cw[i][u] = Q{};
+      if (c0 + i < nw) {
+        const uint8_t* __restrict__ rc = a.rec[rec0 + c0 + i];
+        if constexpr (KIND != kFmtNatural) nr[i] = *reinterpret_cast<const float*>(rc + kDenseNorm);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int64_t e = t0 + 4 * (int64_t)(lane + u * kWave);
+          if (e < n) cw[i][u] = load_quad<BITS>(rc + kDenseCodes, e);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < kBatch; ++i) {
+      if (c0 + i >= nw) continue;  // (uniform)
+      const float wc = a.w[rec0 + c0 + i];
+      const float nrm = nr[i];
+      const bool regular = norm_regular(nrm);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t code = quad_code<BITS>(cw[i][u], j);
+          if constexpr (KIND == kFmtNatural) {
+            v[j] = natural_value(code);
+          } else if (!regular) {
+            v[j] = code == 0u ? 0.0f : __uint_as_float(0x7fc00000u);
+          } else {
+            const float lv = s_lvt[code & ((1u << (BITS - 1)) - 1u)];
+            const float sv = (code >> (BITS - 1)) ? -lv : lv;  // fp32(lv) * sign, -0 kept
+            v[j] = sv * nrm;                                   // compressors.py:357 (rounded before the fma)
+          }
+        }
+        acc[u] = make_float4(fmaf(wc, v[0], acc[u].x), fmaf(wc, v[1], acc[u].y), fmaf(wc, v[2], acc[u].z),
+                             fmaf(wc, v[3], acc[u].w));
+      }
+    }
+  }
+  io.store(t0, lane, acc);
+}
+
+template <class IO>
+int launch_dense_fold(const char* name, const DenseCodec& cd, dim3 grid, hipStream_t st, const FoldArgs& a, int nw,
+                      int64_t tile0, const IO& io) {
+  const double step = 1.0 / (double)(cd.levels < 1 ? 1 : cd.levels);
+#define FLC_DF(K, B)                                                                                              \
+  do {                                                                                                            \
+    FLC_LAUNCH(name, (dense_fold_records_kernel<K, B, IO>), grid, dim3(kWave), 0, st, a, nw, cd.levels, step, cd.n, \
+               tile0, io);                                                                                        \
+    return FLC_OK;                                                                                                \
+  } while (0)
+  if (cd.format == kFmtNatural) FLC_DF(2, 16);
+  if (cd.format == FLC_Q_STANDARD_DITHER) {
+    if (cd.bits == 8) FLC_DF(0, 8);
+    if (cd.bits == 4) FLC_DF(0, 4);
+    FLC_DF(0, 2);
+  }
+  if (cd.bits == 8) FLC_DF(1, 8);
+  if (cd.bits == 4) FLC_DF(1, 4);
+  FLC_DF(1, 2);
+#undef FLC_DF
+}
+
+// check_quant_args' rule (quant.hip) for a dense record's (format, levels, bits); the natural compressor has 16-bit
+// codes and no levels
+int check_dense_format(const char* fn, int format, int levels, int bits) {
+  if (format == kFmtNatural) {
+    if (bits != 16) return fail(FLC_EINVAL, "%s: the natural compressor's codes have 16 bits (got %d)", fn, bits);
+    return FLC_OK;
+  }
+  if (format != FLC_Q_STANDARD_DITHER && format != FLC_Q_NATURAL_DITHER)
+    return fail(FLC_EINVAL, "%s: unknown format %d", fn, format);
+  if (bits != 2 && bits != 4 && bits != 8) return fail(FLC_EINVAL, "%s: bits must be 2, 4 or 8 (got %d)", fn, bits);
+  if (levels < 1 || levels > (1 << (bits - 1)) - 1)
+    return fail(FLC_EINVAL, "%s: levels %d does not fit %d-bit codes", fn, levels, bits);
+  return FLC_OK;
+}
+
 }  // namespace
 }  // namespace flc
 
@@ -629,37 +794,43 @@ int flc_stacked_fold_wires(const void* wires, int64_t stride, const int32_t* slo
   return FLC_OK;
 }
 
-int flc_fedopt_fold_records(const void* const* records, const float* weights, int n_records, int64_t n, int64_t k,
-                            int levels, float* const* delta, float* const* theta, float* const* v,
-                            const int64_t* sizes, int n_tensors, float beta0, int opt, double lr, double beta2,
-                            double tau, void* stream) {
+// flc_fedopt_fold_records (dense == NULL: stacked records of (n, k, levels)) and flc_fedopt_fold_dense_records (the
+// records of *dense): one argument check, one chain of launches, the kernel by the records' codec.  `fn` names the
+// entry point in messages, `probe` its launches for flc_probe_set.
+static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec* dense, const void* const* records,
+                            const float* weights, int n_records, int64_t n, int64_t k, int levels,
+                            float* const* delta, float* const* theta, float* const* v, const int64_t* sizes,
+                            int n_tensors, float beta0, int opt, double lr, double beta2, double tau, void* stream) {
   if (n_records < 0 || (n_records > 0 && (!records || !weights)) || n <= 0 || k < 0 || n_tensors < 1 || !delta ||
       !sizes)
-    return fail(FLC_EINVAL, "flc_fedopt_fold_records: bad arguments");
-  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "flc_fedopt_fold_records: n and k must be < 2^31");
-  if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "flc_fedopt_fold_records: levels must be in [1, 127]");
+    return fail(FLC_EINVAL, "%s: bad arguments", fn);
+  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
+  if (dense) {
+    if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
+  } else if (levels < 1 || levels > 127) {
+    return fail(FLC_EINVAL, "%s: levels must be in [1, 127]", fn);
+  }
   const bool step_on = theta != nullptr;
   if (step_on && opt != FLC_OPT_AVG && opt != FLC_OPT_ADAGRAD && opt != FLC_OPT_YOGI && opt != FLC_OPT_ADAM)
-    return fail(FLC_EINVAL, "flc_fedopt_fold_records: unknown optimiser %d", opt);
-  if (step_on && opt != FLC_OPT_AVG && !v)
-    return fail(FLC_EINVAL, "flc_fedopt_fold_records: v required for adaptive optimisers");
+    return fail(FLC_EINVAL, "%s: unknown optimiser %d", fn, opt);
+  if (step_on && opt != FLC_OPT_AVG && !v) return fail(FLC_EINVAL, "%s: v required for adaptive optimisers", fn);
   int64_t total = 0;
   for (int t = 0; t < n_tensors; ++t) {
-    if (sizes[t] < 0) return fail(FLC_EINVAL, "flc_fedopt_fold_records: negative size for tensor %d", t);
+    if (sizes[t] < 0) return fail(FLC_EINVAL, "%s: negative size for tensor %d", fn, t);
     if (sizes[t] > 0 && (!delta[t] || (step_on && !theta[t]) || (step_on && opt != FLC_OPT_AVG && !v[t])))
-      return fail(FLC_EINVAL, "flc_fedopt_fold_records: null pointer for tensor %d", t);
+      return fail(FLC_EINVAL, "%s: null pointer for tensor %d", fn, t);
     total += sizes[t];
   }
   if (total != n)
-    return fail(FLC_EINVAL, "flc_fedopt_fold_records: the tensors hold %lld elements, the records %lld",
-                (long long)total, (long long)n);
+    return fail(FLC_EINVAL, "%s: the tensors hold %lld elements, the records %lld", fn, (long long)total,
+                (long long)n);
   for (int c = 0; c < n_records; ++c)
     if (!records[c] || !aligned16(records[c]))
-      return fail(FLC_EINVAL, "flc_fedopt_fold_records: record %d is null or not 16-B aligned", c);
+      return fail(FLC_EINVAL, "%s: record %d is null or not 16-B aligned", fn, c);
   size_t need = 0;
   const WireLayout L = wire_layout(n, k, &need);
   hipStream_t st = as_stream(stream);
-  const double step = 1.0 / (double)levels;
+  const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   const float omb = (float)(1.0 - beta2), nomb = (float)(-(1.0 - beta2));
   // record chunks in order (the chain continues from the stored δ, the step after the last chunk only); within a
   // chunk, one launch per group of <= kRoundT tensors over the tiles their flat range touches
@@ -699,9 +870,15 @@ int flc_fedopt_fold_records(const void* const* records, const float* weights, in
       m.start[m.nt] = off;
       const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
       const dim3 grid((unsigned)(tile_hi - tile_lo));
-#define FLC_FR(O) \
-  FLC_LAUNCH("fedopt_fold_records", (stacked_fold_wires_kernel<false, ModelIO<O>>), grid, dim3(kWave), 0, st, a, L, nw, \
-             levels, step, tile_lo, ModelIO<O>{m}, (unsigned)k)
+#define FLC_FR(O)                                                                                                 \
+  do {                                                                                                            \
+    if (dense) {                                                                                                  \
+      if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, ModelIO<O>{m})) return rc;          \
+    } else {                                                                                                      \
+      FLC_LAUNCH(probe, (stacked_fold_wires_kernel<false, ModelIO<O>>), grid, dim3(kWave), 0, st, a, L, nw, levels, \
+                 step, tile_lo, ModelIO<O>{m}, (unsigned)k);                                                      \
+    }                                                                                                             \
+  } while (0)
       if (!step_on || !last) FLC_FR(-1);
       else if (opt == FLC_OPT_AVG) FLC_FR(FLC_OPT_AVG);
       else if (opt == FLC_OPT_ADAGRAD) FLC_FR(FLC_OPT_ADAGRAD);
@@ -712,6 +889,24 @@ int flc_fedopt_fold_records(const void* const* records, const float* weights, in
     c0 += nw;
   } while (c0 < n_records);
   return FLC_OK;
+}
+
+int flc_fedopt_fold_records(const void* const* records, const float* weights, int n_records, int64_t n, int64_t k,
+                            int levels, float* const* delta, float* const* theta, float* const* v,
+                            const int64_t* sizes, int n_tensors, float beta0, int opt, double lr, double beta2,
+                            double tau, void* stream) {
+  return fedopt_fold_impl("flc_fedopt_fold_records", "fedopt_fold_records", nullptr, records, weights, n_records, n, k,
+                          levels, delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau, stream);
+}
+
+int flc_fedopt_fold_dense_records(const void* const* records, const float* weights, int n_records, int64_t n,
+                                  int format, int levels, int bits, float* const* delta, float* const* theta,
+                                  float* const* v, const int64_t* sizes, int n_tensors, float beta0, int opt,
+                                  double lr, double beta2, double tau, void* stream) {
+  const DenseCodec cd{format, levels, bits, n};
+  return fedopt_fold_impl("flc_fedopt_fold_dense_records", "fedopt_fold_dense_records", &cd, records, weights,
+                          n_records, n, 0, levels, delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau,
+                          stream);
 }
 
 int flc_avg_and_gradient_records(float* const* params, float* const* grads, const float* const* param_srcs,
@@ -806,29 +1001,35 @@ int flc_avg_and_gradient_records(float* const* params, float* const* grads, cons
   return FLC_OK;
 }
 
-int flc_fold_record_groups(const void* const* records, const float* weights, const int32_t* group_of, int n_records,
-                           int64_t n, int64_t k, int levels, float* const* dsts, int n_groups, const int64_t* sizes,
-                           int n_tensors, void* stream) {
+// flc_fold_record_groups (dense == NULL) and flc_fold_dense_record_groups (the records of *dense), as
+// fedopt_fold_impl serves the two FedOpt folds
+static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec* dense, const void* const* records,
+                            const float* weights, const int32_t* group_of, int n_records, int64_t n, int64_t k,
+                            int levels, float* const* dsts, int n_groups, const int64_t* sizes, int n_tensors,
+                            void* stream) {
   if (n_records < 0 || (n_records > 0 && (!records || !weights || !group_of)) || n <= 0 || k < 0 || n_groups < 1 ||
       n_tensors < 1 || !dsts || !sizes)
-    return fail(FLC_EINVAL, "flc_fold_record_groups: bad arguments");
-  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "flc_fold_record_groups: n and k must be < 2^31");
-  if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "flc_fold_record_groups: levels must be in [1, 127]");
+    return fail(FLC_EINVAL, "%s: bad arguments", fn);
+  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
+  if (dense) {
+    if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
+  } else if (levels < 1 || levels > 127) {
+    return fail(FLC_EINVAL, "%s: levels must be in [1, 127]", fn);
+  }
   int64_t total = 0;
   for (int t = 0; t < n_tensors; ++t) {
-    if (sizes[t] < 0) return fail(FLC_EINVAL, "flc_fold_record_groups: negative size for tensor %d", t);
+    if (sizes[t] < 0) return fail(FLC_EINVAL, "%s: negative size for tensor %d", fn, t);
     total += sizes[t];
   }
   if (total != n)
-    return fail(FLC_EINVAL, "flc_fold_record_groups: the tensors hold %lld elements, the records %lld",
-                (long long)total, (long long)n);
+    return fail(FLC_EINVAL, "%s: the tensors hold %lld elements, the records %lld", fn, (long long)total,
+                (long long)n);
   std::vector<int> members(n_groups, 0);
   for (int c = 0; c < n_records; ++c) {
     if (!records[c] || !aligned16(records[c]))
-      return fail(FLC_EINVAL, "flc_fold_record_groups: record %d is null or not 16-B aligned", c);
+      return fail(FLC_EINVAL, "%s: record %d is null or not 16-B aligned", fn, c);
     if (group_of[c] < 0 || group_of[c] >= n_groups)
-      return fail(FLC_EINVAL, "flc_fold_record_groups: record %d names group %d outside [0, %d)", c, (int)group_of[c],
-                  n_groups);
+      return fail(FLC_EINVAL, "%s: record %d names group %d outside [0, %d)", fn, c, (int)group_of[c], n_groups);
     ++members[group_of[c]];
   }
   std::vector<std::pair<uintptr_t, int>> owners;  // (destination, group) of every non-empty tensor
@@ -837,8 +1038,7 @@ int flc_fold_record_groups(const void* const* records, const float* weights, con
       float* d = dsts[(size_t)g * n_tensors + t];
       if (sizes[t] == 0) continue;
       if (!d) {
-        if (members[g] > 0)
-          return fail(FLC_EINVAL, "flc_fold_record_groups: null pointer for tensor %d of group %d", t, g);
+        if (members[g] > 0) return fail(FLC_EINVAL, "%s: null pointer for tensor %d of group %d", fn, t, g);
         continue;
       }
       owners.emplace_back(reinterpret_cast<uintptr_t>(d), g);
@@ -846,13 +1046,13 @@ int flc_fold_record_groups(const void* const* records, const float* weights, con
   std::sort(owners.begin(), owners.end());
   for (size_t i = 1; i < owners.size(); ++i)
     if (owners[i].first == owners[i - 1].first && owners[i].second != owners[i - 1].second)
-      return fail(FLC_EINVAL, "flc_fold_record_groups: groups %d and %d share a destination", owners[i - 1].second,
+      return fail(FLC_EINVAL, "%s: groups %d and %d share a destination", fn, owners[i - 1].second,
                   owners[i].second);
   if (n_records == 0) return FLC_OK;
   size_t need = 0;
   const WireLayout L = wire_layout(n, k, &need);
   hipStream_t st = as_stream(stream);
-  const double step = 1.0 / (double)levels;
+  const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   // the records ordered by group, each group's in message order
   std::vector<int> order(n_records);
   for (int c = 0; c < n_records; ++c) order[c] = c;
@@ -908,14 +1108,74 @@ int flc_fold_record_groups(const void* const* records, const float* weights, con
       m.start[m.nt] = off;
       const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
       const dim3 grid((unsigned)(tile_hi - tile_lo), (unsigned)ng);
-      if (sparse)
-        FLC_LAUNCH("fold_record_groups", (stacked_fold_wires_kernel<true, GroupIO>), grid, dim3(kWave), 0, st, a, L, nw,
-                   levels, step, tile_lo, io, (unsigned)k);
-      else
-        FLC_LAUNCH("fold_record_groups", (stacked_fold_wires_kernel<false, GroupIO>), grid, dim3(kWave), 0, st, a, L,
-                   nw, levels, step, tile_lo, io, (unsigned)k);
+      if (dense) {
+        if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, io)) return rc;
+      } else if (sparse) {
+        FLC_LAUNCH(probe, (stacked_fold_wires_kernel<true, GroupIO>), grid, dim3(kWave), 0, st, a, L, nw, levels, step,
+                   tile_lo, io, (unsigned)k);
+      } else {
+        FLC_LAUNCH(probe, (stacked_fold_wires_kernel<false, GroupIO>), grid, dim3(kWave), 0, st, a, L, nw, levels,
+                   step, tile_lo, io, (unsigned)k);
+      }
     }
     c0 += nw;
+  }
+  return FLC_OK;
+}
+
+int flc_fold_record_groups(const void* const* records, const float* weights, const int32_t* group_of, int n_records,
+                           int64_t n, int64_t k, int levels, float* const* dsts, int n_groups, const int64_t* sizes,
+                           int n_tensors, void* stream) {
+  return fold_groups_impl("flc_fold_record_groups", "fold_record_groups", nullptr, records, weights, group_of,
+                          n_records, n, k, levels, dsts, n_groups, sizes, n_tensors, stream);
+}
+
+int flc_fold_dense_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
+                                 int n_records, int64_t n, int format, int levels, int bits, float* const* dsts,
+                                 int n_groups, const int64_t* sizes, int n_tensors, void* stream) {
+  const DenseCodec cd{format, levels, bits, n};
+  return fold_groups_impl("flc_fold_dense_record_groups", "fold_dense_record_groups", &cd, records, weights, group_of,
+                          n_records, n, 0, levels, dsts, n_groups, sizes, n_tensors, stream);
+}
+
+size_t flc_dense_wire_layout(int64_t n, int format, int bits, int64_t* offsets) {
+  if (n < 1 || n >= (1ll << 31)) return 0;
+  if (format == kFmtNatural ? bits != 16
+                            : ((format != FLC_Q_STANDARD_DITHER && format != FLC_Q_NATURAL_DITHER) ||
+                               (bits != 2 && bits != 4 && bits != 8)))
+    return 0;
+  if (offsets) {
+    offsets[0] = kDenseNorm;
+    offsets[1] = kDenseCodes;
+  }
+  return dense_wire_size(n, format, bits);
+}
+
+int flc_fold_dense_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
+                         int64_t n, int format, int levels, int bits, int accumulate, float* out, void* stream) {
+  const char* fn = "flc_fold_dense_wires";
+  if (!wires || !slots || !weights || !out || n_wires < 1 || n <= 0) return fail(FLC_EINVAL, "%s: bad arguments", fn);
+  if (n >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n must be < 2^31", fn);
+  if (int rc = check_dense_format(fn, format, levels, bits)) return rc;
+  const size_t need = dense_wire_size(n, format, bits);
+  if (stride < (int64_t)need || stride % 16 != 0)
+    return fail(FLC_EINVAL, "%s: stride %lld < record size %zu (or not 16-B aligned)", fn, (long long)stride, need);
+  if (!aligned16(wires) || !aligned16(out)) return fail(FLC_EINVAL, "%s: 16-B aligned buffers required", fn);
+  for (int c = 0; c < n_wires; ++c)
+    if (slots[c] < 0) return fail(FLC_EINVAL, "%s: slot %d is negative", fn, c);
+  hipStream_t st = as_stream(stream);
+  const DenseCodec cd{format, levels, bits, n};
+  const int64_t ntiles = cdiv(n, (int64_t)FLC_TILE);
+  for (int c0 = 0; c0 < n_wires; c0 += kMaxWires) {  // (a chained launch continues from the stored out)
+    const int nw = std::min(kMaxWires, n_wires - c0);
+    FoldArgs a;
+    for (int c = 0; c < kMaxWires; ++c) {
+      a.w[c] = c < nw ? weights[c0 + c] : 0.0f;
+      a.rec[c] = static_cast<const uint8_t*>(wires) + (c < nw ? (int64_t)slots[c0 + c] * stride : 0);
+    }
+    const FlatIO io{out, n, (c0 > 0 || accumulate) ? 1 : 0};
+    if (int rc = launch_dense_fold("fold_dense_wires", cd, dim3((unsigned)ntiles), st, a, nw, (int64_t)0, io))
+      return rc;
   }
   return FLC_OK;
 }

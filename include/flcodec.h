@@ -277,6 +277,52 @@ int flc_fold_record_groups(const void* const* records, const float* weights, con
                            int64_t n, int64_t k, int levels, float* const* dsts /* [n_groups][n_tensors] */,
                            int n_groups, const int64_t* sizes, int n_tensors, void* stream);
 
+/* ------------------------------------------------------------------ dense records (dithering / natural wire)
+ * One client's dithering or natural-compressor wire as ONE contiguous record, the dense quantizers' counterpart of the
+ * stacked record above: what a message carries in place of the decoded vector compressVector returns
+ * (compressors.py:357 / 394 standard / natural dithering, 302-325 the natural compressor).
+ * `format`: FLC_Q_STANDARD_DITHER or FLC_Q_NATURAL_DITHER with bits in {2, 4, 8} (the quantizer codec's code width), or
+ * FLC_WIRE_NATURAL with bits = 16 (the natural compressor's uint16 codes; `levels` is then ignored).
+ * Returns the record size (a multiple of 256 B; 0 for bad arguments: another format, bits that do not match it,
+ * n < 1 or n >= 2^31) and, if offsets != NULL, the byte offsets of offsets[0] the norm (fp32; unused by the natural
+ * compressor) and offsets[1] the codes (16-B aligned; ceil(n * bits / 8) bytes, 2n for the natural compressor).  The
+ * layout depends on (n, format, bits) only, so a [clients, stride] block moves as one piece.  The encoders write a
+ * record when given those pointers inside it: flc_quant_encode (norms = the record's norm field, written by
+ * flc_quant_norm or by the caller), flc_quant_encode_auto with out == NULL, flc_natural_encode. */
+enum flc_dense_wire_format { FLC_WIRE_NATURAL = 2 /* beside FLC_Q_STANDARD_DITHER = 0, FLC_Q_NATURAL_DITHER = 1 */ };
+size_t flc_dense_wire_layout(int64_t n, int format, int bits, int64_t* offsets);
+/* flc_stacked_fold_wires' contract over dense records (the server's weighted aggregation, nodes.py:1165-1180 /
+ * _fedopt.py:202-208, fused with the decode of compressors.py:357 / 394 / 302-325):
+ *   out = (accumulate ? out : +0);  for c = 0 .. n_wires-1:  out = fmaf(weights[c], decode(record slots[c]), out)
+ * elementwise, in that order — bit-identical to n_wires flc_quant_decode(row_weights = w_c, accumulate = 1) calls
+ * (flc_natural_decode(weight = w_c, accumulate = 1) for FLC_WIRE_NATURAL) on a zeroed (or the given) out: a norm that is
+ * 0, +-inf, NaN or negative decodes code 0 to +0 and every other code to NaN, a negative zero level to -0.  One pass
+ * over out; the records' codes are read once (bits / 32 of the dense vectors' bytes).  wires: records of `stride`
+ * bytes (>= flc_dense_wire_layout(n, format, bits), a 16-B multiple), record index slots[c] holds client c; slots and
+ * weights are HOST arrays; more than 64 records chain launches.  FLC_EINVAL (nothing launched): a null pointer,
+ * bits that do not match the format, levels that do not fit bits (1 <= levels < 2^(bits-1)), n >= 2^31, a short or
+ * misaligned stride, a negative slot. */
+int flc_fold_dense_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
+                         int64_t n, int format, int levels, int bits, int accumulate, float* out, void* stream);
+/* flc_fedopt_fold_records' contract over dense records (replaces FedOptServer.update, _fedopt.py:196-240, when each
+ * client message carries its delta as a dense record in place of compressors.py:357 / 394 / 302-325's decoded vector):
+ *   a = delta * beta0;  for c = 0 .. n_records-1:  a = fmaf(weights[c], decode(records[c]), a);  delta = a;
+ *   then, if theta != NULL, the optimiser's step (avg / adagrad / yogi / adam, as flc_model_fold).
+ * Bit-identical to decoding every record densely (flc_quant_decode / flc_natural_decode) and running flc_model_fold
+ * with init_mode 0 and the step.  Arguments as flc_fedopt_fold_records', (format, levels, bits) as above. */
+int flc_fedopt_fold_dense_records(const void* const* records, const float* weights, int n_records, int64_t n,
+                                  int format, int levels, int bits, float* const* delta, float* const* theta,
+                                  float* const* v, const int64_t* sizes, int n_tensors, float beta0, int opt,
+                                  double lr, double beta2, double tau, void* stream);
+/* flc_fold_record_groups' contract over dense records (add_parameters' in-place accumulation per group,
+ * nodes.py:1116-1132, of messages that carry compressors.py:357 / 394 / 302-325's codes): bit-identical to decoding
+ * every record densely and calling flc_weighted_sum(init_mode 2) per group and tensor.  Arguments, chaining and
+ * FLC_EINVAL cases as flc_fold_record_groups', (format, levels, bits) as above. */
+int flc_fold_dense_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
+                                 int n_records, int64_t n, int format, int levels, int bits,
+                                 float* const* dsts /* [n_groups][n_tensors] */, int n_groups, const int64_t* sizes,
+                                 int n_tensors, void* stream);
+
 /* ------------------------------------------------------------------ multi-GPU exchange (RCCL over xGMI)
  * For callers outside torch; one process per GPU.  RCCL is the NCCL API on ROCm, looked
  * up on first use: $FLC_RCCL_LIB if set, else an RCCL already loaded in the process (inside a torch process, torch's
