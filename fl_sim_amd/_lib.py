@@ -50,6 +50,12 @@ SIGNATURES = {
         [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "flc_quant_encode_round_workspace_size": (c_size_t, [c_int64, c_int]),
+    "flc_quant_encode_round": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_size_t, c_void_p],
+    ),
     "flc_quant_decode": (
         c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     ),

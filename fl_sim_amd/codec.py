@@ -265,6 +265,52 @@ def dense_record_decode(record: torch.Tensor, n: int, fmt: int, levels: int, bit
     return quant_decode(pkt, out=None if out is None else out.reshape(1, n)).reshape(n)
 
 
+def quant_encode_round(xs: Sequence[torch.Tensor], kind: int, levels: int, bits: int, norm_p: int,
+                       seeds: Sequence[int], counters: Sequence[int], records, counts=None) -> None:
+    """A round's dithering messages in one call (flc_quant_encode_round, philox mode, norm included): message c — the
+    flat fp32 vector ``xs[c]``, all of one size on one device — is encoded with its own Philox
+    ``(seeds[c], counters[c])`` into the dense record ``records[c]`` (its norm and codes views, dense_wire_views),
+    bit-identical to ``flc_quant_encode_auto`` of that vector alone.  ``records``: a ``[C, >= stride]`` uint8 block
+    or a sequence of C records; ``norm_p``: FLC_NORM_INF or FLC_NORM_L2; ``counts``: None, or one one-element device
+    int64 tensor per message (a contiguous ``[C]`` tensor also) that receives the message's count of nonzero
+    elements."""
+    import ctypes
+
+    C = len(xs)
+    if C == 0:
+        return
+    n, dev = xs[0].numel(), xs[0].device
+    xp = _batch_ptrs(xs, n, dev) if dev.type == "cuda" else None
+    if xp is None:  # (the slow path: checks with messages, copies of misaligned inputs)
+        xs = [_dev_f32(x).reshape(-1) for x in xs]
+        if any(x.numel() != n or x.device != dev for x in xs):
+            raise ValueError("a round encode takes messages of one size on one device")
+        xp = [x.data_ptr() for x in xs]
+    if len(seeds) != C or len(counters) != C:
+        raise ValueError("one seed and one counter per message")
+    if isinstance(records, torch.Tensor) and records.dim() == 2:  # one record block: the rows' views by arithmetic
+        stride, off = dense_wire_layout(n, kind, bits)
+        if records.shape[0] != C or records.shape[1] % 16 or records.device != dev:
+            raise ValueError(f"records must be a [{C}, >= {stride}] uint8 block (16-B rows) on {dev}")
+        dense_wire_views(records[0], n, kind, bits)  # (dtype, size and alignment, checked on one row for all)
+        bases = [records.data_ptr() + c * records.shape[1] for c in range(C)]
+        nps, cps = [b + off["norm"] for b in bases], [b + off["codes"] for b in bases]
+    else:
+        if len(records) != C:
+            raise ValueError("one record per message")
+        views = [dense_wire_views(r, n, kind, bits) for r in records]
+        if any(r.device != dev for r in records):
+            raise ValueError(f"the records must be on {dev}")
+        nps, cps = [v[0].data_ptr() for v in views], [v[1].data_ptr() for v in views]
+    ctr, cnt = _round_args(C, dev, 0, counters, counts)
+    P = ctypes.c_void_p * C
+    vp = lambda a: None if a is None else ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+    ws = workspace(dev, _ws_size(dev, "flc_quant_encode_round_workspace_size", n, C), "quant_round")
+    call("flc_quant_encode_round", vp(P(*xp)), C, n, kind, levels, bits, norm_p,
+         vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), vp(ctr), vp(P(*cps)), vp(P(*nps)), vp(cnt), _p(ws),
+         ws.numel(), _stream(dev))
+
+
 def fold_dense_wires(wires: torch.Tensor, slots: Sequence[int], weights: Sequence[float], n: int, fmt: int,
                      levels: int, bits: int, out: Optional[torch.Tensor] = None,
                      accumulate: bool = False) -> torch.Tensor:

@@ -24,6 +24,9 @@ What runs here instead:
   message then carries the quantizer's own wire as a dense record (``flc_dense_wire_layout``: the fp32 norm and the
   packed 2-, 4- or 8-bit codes, or one uint16 per element), written by the compressor's encoder straight into the
   record with nothing decoded, the RNG streams and send statistics advancing as ``compressVector`` advances them.
+  In philox mode a dithering quantizer's records of up to 2^20 elements (device norm, p = ∞ or 2, no error feedback)
+  are deferred like the stacked ones: the round's messages are encoded by one ``flc_quant_encode_round`` when a record
+  or a statistic is first read (:func:`deferred_dense_stats` counts these batches).
   Either way ``delta_parameters`` is a :class:`CompressedDelta`: a sequence of per-tensor tensors that decodes itself
   on first access, so any server — the reference's own ``update`` included — reads it unchanged.
 * ``aggregation.fedopt_update`` (and :class:`~fl_sim_amd.aggregation.FedOptUpdateMixin`) recognises a round of stacked
@@ -399,6 +402,10 @@ def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]
         out = codec.delta_flatten(ls, gs)
     dc = dense_wire_codec(compressors) if wire else None
     if dc is not None:  # the quantizer's own wire as the message: codes written into the record, nothing decoded
+        if DEFER_ENCODE and n <= _DEFER_DENSE_MAX_N and dc[0] != FLC_WIRE_NATURAL:
+            r = _defer_dense(out, shapes, n, compressors[0], dc, dev)  # (out: a new vector, the snapshot)
+            if r is not None:
+                return r
         return _dense_record(out, shapes, n, compressors[0], dc, dev)
     for comp in compressors:  # the drop-in compressors on the device, in order
         out = comp.compressVector(out)
@@ -487,7 +494,8 @@ def deferred_stats(reset: bool = False) -> dict:
 
 
 class _Batch:
-    """The waiting messages of one (device, n, k, levels)."""
+    """The waiting messages of one (device, n, k, levels): a round's stacked records, encoded together.  The stream
+    handling around the encode is shared with :class:`_DenseBatch`, which replaces :meth:`_encode_rows`."""
 
     def __init__(self, key):
         self.key = key
@@ -509,40 +517,85 @@ class _Batch:
             raise
 
     def _encode(self, items) -> None:
-        di, n, k, levels = self.key
-        dev = torch.device("cuda", di)
+        dev = torch.device("cuda", self.key[0])
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
             ch = cur.cuda_stream
             for st in {it[6]: it[5] for it in items if it[6] != ch}.values():  # (deltas flattened on other streams)
                 cur.wait_stream(st)
-            stride, _ = codec.stacked_wire_layout(n, k)
-            C = len(items)
-            recs = torch.empty(C, stride, dtype=torch.uint8, device=dev)
-            flats = [it[1] for it in items]
-            seeds, ctrs, cnts = [it[2] for it in items], [it[7] for it in items], [it[3] for it in items]
-            fast = codec._pyround()
-            if fast is not None:  # one C call: the encode's launch chain fills the count slots too
-                ws = codec.workspace(dev, codec._ws_size(dev, "flc_stacked_encode_batch_workspace_size", n, k, C),
-                                     "topk_batch")
-                fast(flats, seeds, ctrs, k, levels, recs, cnts, ws)
-            else:
-                codec.stacked_encode_batch(flats, k, levels, seeds=seeds, counters=ctrs, counts=cnts, wires=recs)
-            codec._after_encode(dev)
-            rows = recs.unbind(0)
-            fed = [(r, it[8]) for it, r in zip(items, rows) if it[8] is not None]
-            if fed:  # error feedback: e = a − c at the records' kept entries, one launch for the round (an encode
-                # that raised never gets here: the memories then still hold a, and the retry encodes the same a)
-                codec.ef_residual_round([r for r, _ in fed], [m._e for _, m in fed], n, k, levels)
-            _STATS["batches"] += 1
-            _STATS["messages"] += C
+            rows = self._encode_rows(items, dev)
             for (d, flat, _, _, sd, _, sh, _, mem), r in zip(items, rows):
                 if sh != ch:
                     flat.record_stream(cur)
-                    sd._note_slab_stream(cur)  # (the count was written on this stream, not the slot's own)
+                    if sd is not None:
+                        sd._note_slab_stream(cur)  # (the count was written on this stream, not the slot's own)
                 if mem is not None:
                     mem._written(cur)
                 d._record, d._batch = r, None
+
+    def _encode_rows(self, items, dev):
+        """The items' records, encoded on ``dev``'s current stream: the rows of one ``[C, stride]`` block."""
+        _, n, k, levels = self.key
+        stride, _ = codec.stacked_wire_layout(n, k)
+        C = len(items)
+        recs = torch.empty(C, stride, dtype=torch.uint8, device=dev)
+        flats = [it[1] for it in items]
+        seeds, ctrs, cnts = [it[2] for it in items], [it[7] for it in items], [it[3] for it in items]
+        fast = codec._pyround()
+        if fast is not None:  # one C call: the encode's launch chain fills the count slots too
+            ws = codec.workspace(dev, codec._ws_size(dev, "flc_stacked_encode_batch_workspace_size", n, k, C),
+                                 "topk_batch")
+            fast(flats, seeds, ctrs, k, levels, recs, cnts, ws)
+        else:
+            codec.stacked_encode_batch(flats, k, levels, seeds=seeds, counters=ctrs, counts=cnts, wires=recs)
+        codec._after_encode(dev)
+        rows = recs.unbind(0)
+        fed = [(r, it[8]) for it, r in zip(items, rows) if it[8] is not None]
+        if fed:  # error feedback: e = a − c at the records' kept entries, one launch for the round (an encode
+            # that raised never gets here: the memories then still hold a, and the retry encodes the same a)
+            codec.ef_residual_round([r for r, _ in fed], [m._e for _, m in fed], n, k, levels)
+        _STATS["batches"] += 1
+        _STATS["messages"] += C
+        return rows
+
+
+# Deferred dense records (philox mode, `wire` on, one standard or natural dithering with p = inf or 2 and the device
+# norm, no error feedback).  The per-message flc_quant_encode_auto of a model-sized vector is all fixed latency too, so
+# these messages wait like the stacked ones — the flat delta snapshotted, the Philox (seed, counter) and the count slot
+# fixed at `communicate` — and one flc_quant_encode_round (two launches per 64 messages, each message with its own
+# (seed, counter), record and count slot) writes the round's records, bit-identical to the per-message encodes.
+# The same switch (FLC_DEFER_ENCODE) and pending bounds as the stacked batches, which share _PENDING with these; the
+# size bound is the dense kind's own: measured (profiles/dense_record_defer.json), ten messages' batched encode takes
+# 60 us against 124 us of per-message encodes at 417,482 elements and 95 against 128 us at 1 M, but 157 against 136 us
+# at 2 M and 248 against 137 us for eight messages of 4 M — past ~1.5 M elements the per-message call's one-launch
+# form, which reads the vector once, beats two streaming launches — so larger messages keep the immediate path.
+_DEFER_DENSE_MAX_N = 1 << 20
+_DENSE_STATS = {"batches": 0, "messages": 0}
+
+
+def deferred_dense_stats(reset: bool = False) -> dict:
+    """:func:`deferred_stats` for the dense records' batched encodes (flc_quant_encode_round), counted apart."""
+    out = dict(_DENSE_STATS)
+    if reset:
+        _DENSE_STATS.update(batches=0, messages=0)
+    return out
+
+
+class _DenseBatch(_Batch):
+    """The waiting dense-record messages of one (device, "quant", n, format, levels, bits, norm_p); an item's count
+    slot and compressor are None for natural dithering, whose send count does not depend on the data."""
+
+    def _encode_rows(self, items, dev):
+        _, _, n, fmt, levels, bits, pk = self.key
+        stride, _ = codec.dense_wire_layout(n, fmt, bits)
+        C = len(items)
+        recs = torch.empty(C, stride, dtype=torch.uint8, device=dev)
+        codec.quant_encode_round([it[1] for it in items], fmt, levels, bits, pk, [it[2] for it in items],
+                                 [it[7] for it in items], recs,
+                                 [it[3] for it in items] if fmt == FLC_Q_STANDARD_DITHER else None)
+        _DENSE_STATS["batches"] += 1
+        _DENSE_STATS["messages"] += C
+        return recs.unbind(0)
 
 
 _PENDING: dict = {}
@@ -589,6 +642,41 @@ def _defer(flat: torch.Tensor, shapes, n: int, K: int, s: int, tk: Compressor, s
     tk._finish(n, tk.K)
     base = _norm_stage_send(sd, None)
     sd._finish_pending(n, cnt, base, (1.0 + np.ceil(math.log2(sd.s))) / 32.0)  # compressors.py:365
+    if len(b.items) >= _DEFER_MAX_PENDING:
+        b.run()
+    elif len(_PENDING) > _DEFER_MAX_BATCHES:  # (messages nobody reads: the waiting deltas stay bounded)
+        _run_pending()
+    return d
+
+
+def _defer_dense(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[int, int, int],
+                 dev) -> Optional[CompressedDelta]:
+    """The dense-record message of the flat vector ``x`` (a snapshot) joins the round's batched quantizer encode; the
+    Philox stream and the send statistics advance here exactly as :func:`_dense_record` advances them.  None (nothing
+    advanced: the immediate path takes the message) outside philox mode with the device norm of p = inf or 2 on a
+    float32 vector."""
+    fmt, s, bits = dc
+    if comp.rng_mode != "philox" or comp._wants_host_norm(device_input=True):
+        return None
+    pk = FLC_NORM_INF if math.isinf(comp.p) else (FLC_NORM_L2 if comp.p == 2 else None)
+    if pk is None or x.dtype != torch.float32 or x.device != dev:
+        return None
+    x = codec._dev_f32(x).reshape(-1)
+    std = fmt == FLC_Q_STANDARD_DITHER
+    st = torch.cuda.current_stream(dev)
+    cnt = comp._count_slot(dev, st) if std else None  # (before the batch is looked up, as in _defer)
+    key = (dev.index, "quant", n, fmt, s, bits, pk)
+    b = _PENDING.get(key)
+    if b is None:
+        b = _PENDING[key] = _DenseBatch(key)
+    seed, ctr = comp.philox.next()
+    d = CompressedDelta(shapes, dev, n, levels=s, batch=b, format=fmt, bits=bits)
+    b.items.append((d, x, seed, cnt, comp if std else None, st, st.cuda_stream, ctr, None))
+    per = (1.0 + np.ceil(math.log2(s))) / 32.0  # compressors.py:365 / 404
+    if std:
+        comp._finish_pending(n, cnt, _norm_stage_send(comp, None), per)
+    else:
+        comp._finish(n, n * per)
     if len(b.items) >= _DEFER_MAX_PENDING:
         b.run()
     elif len(_PENDING) > _DEFER_MAX_BATCHES:  # (messages nobody reads: the waiting deltas stay bounded)

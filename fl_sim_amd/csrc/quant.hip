@@ -12,6 +12,8 @@
 //   quant_encode   per element: y = fp32(|x| / norm), bracket [lv(s), lv(s+1)] found in fp64,
 //                  p_down = (y - lv(s+1)) / (lv(s) - lv(s+1)) in fp64, level = u < p_down ? s : s+1.
 //                  algorithmic bytes: 4 read + BITS/8 written per element.
+//   quant_round_*  a round's messages (each its own vector, Philox (seed, counter), record and count slot) in two
+//                  launches: norm partials over (part, message), encode over (block, message); flc_quant_encode_round.
 //   quant_decode   v = fp32(fp32(lv) * sign) * norm, optionally fmaf-accumulated with a row weight.
 //                  algorithmic bytes: BITS/8 read + 4 written (+4 read when accumulating).
 // Each thread owns GROUP = 8 consecutive elements (two 16-B loads, one 2..8-B code store): a wave
@@ -79,16 +81,12 @@ __device__ __forceinline__ float fold_row(int parts, const QuantWs& ws, int64_t 
   return (float)sqrt(wave_sum(acc));
 }
 
+// One block's norm partial of x[lo, hi) of the row xr (flc_quant_norm's traversal: the partials' bits depend on it, so
+// every norm kernel shares this body): the max |x| bits, or the fp64 sum of squares' bits.  flat_lo: the element's
+// index in the flat batch (the 16-B head); every thread of the block gets the result.
 template <int NORM>
-__global__ __launch_bounds__(kThreads) void quant_norm_kernel(const float* __restrict__ x, int64_t d,
-                                                              int parts, int64_t chunk, int vec_ok,
-                                                              QuantWs ws) {
-  __shared__ unsigned long long s_red[kNW];
-  const int row = blockIdx.y, part = blockIdx.x;
-  const float* xr = x + (int64_t)row * d;
-  const int64_t lo = (int64_t)part * chunk;
-  const int64_t hi = lo + chunk < d ? lo + chunk : d;
-
+__device__ __forceinline__ unsigned long long norm_part(const float* __restrict__ xr, int64_t flat_lo, int64_t lo,
+                                                        int64_t hi, int vec_ok, unsigned long long (&s_red)[kNW]) {
   uint32_t mx = 0;
   double ss = 0.0;
   auto take = [&](float v) {
@@ -102,7 +100,6 @@ __global__ __launch_bounds__(kThreads) void quant_norm_kernel(const float* __res
   };
   if (vec_ok) {
     // x is 16-B aligned: a scalar head up to the next 16-B boundary of the flat batch, float4 body, scalar tail
-    const int64_t flat_lo = (int64_t)row * d + lo;
     const int64_t head = std::min<int64_t>((4 - (flat_lo & 3)) & 3, hi - lo);
     if (threadIdx.x < head) take(xr[lo + threadIdx.x]);
     const float4* x4 = reinterpret_cast<const float4*>(xr + lo + head);
@@ -116,7 +113,6 @@ __global__ __launch_bounds__(kThreads) void quant_norm_kernel(const float* __res
     for (int64_t i = lo + threadIdx.x; i < hi; i += kThreads) take(xr[i]);
   }
 
-  unsigned long long part_bits;
   if (NORM == FLC_NORM_INF) {
     uint32_t m = wave_max_u32(mx);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = m;
@@ -127,20 +123,30 @@ __global__ __launch_bounds__(kThreads) void quant_norm_kernel(const float* __res
       s_red[0] = r;
     }
     __syncthreads();
-    part_bits = s_red[0];
-  } else {
-    double s = wave_sum(ss);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = __double_as_longlong(s);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double r = 0.0;
-      for (int w = 0; w < kNW; ++w) r += __longlong_as_double(s_red[w]);
-      s_red[0] = __double_as_longlong(r);
-    }
-    __syncthreads();
-    part_bits = s_red[0];
+    return s_red[0];
   }
+  double s = wave_sum(ss);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = __double_as_longlong(s);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r = 0.0;
+    for (int w = 0; w < kNW; ++w) r += __longlong_as_double(s_red[w]);
+    s_red[0] = __double_as_longlong(r);
+  }
+  __syncthreads();
+  return s_red[0];
+}
 
+template <int NORM>
+__global__ __launch_bounds__(kThreads) void quant_norm_kernel(const float* __restrict__ x, int64_t d,
+                                                              int parts, int64_t chunk, int vec_ok,
+                                                              QuantWs ws) {
+  __shared__ unsigned long long s_red[kNW];
+  const int row = blockIdx.y, part = blockIdx.x;
+  const int64_t lo = (int64_t)part * chunk;
+  const int64_t hi = lo + chunk < d ? lo + chunk : d;
+  const unsigned long long part_bits =
+      norm_part<NORM>(x + (int64_t)row * d, (int64_t)row * d + lo, lo, hi, vec_ok, s_red);
   if (threadIdx.x == 0) ws.partials[(int64_t)row * kNormMaxParts + part] = part_bits;
 }
 
@@ -536,6 +542,79 @@ __global__ __launch_bounds__(kThreads) void quant_encode_philox_kernel(
     __syncthreads();
     if (threadIdx.x < kRowSlots && s_nnz[threadIdx.x] != 0)
       atomicAdd(reinterpret_cast<unsigned long long*>(&nnz[row_base + threadIdx.x]), s_nnz[threadIdx.x]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// A round's messages in two launches (flc_quant_encode_round): message c is its own flat vector of n elements with its
+// own Philox (seed, counter), code stream, norm and count slot, the element index restarting at 0 — rows = 1 of the
+// kernels above, once per message.  The message table travels in the kernel arguments (48 B per message, 64 per
+// launch: 3 KB of the 4 KB kernarg segment), so nothing is copied from the host arrays and the call can be captured.
+// Ordinary grids, no block waits for another: the norm partials over (part, message) — flc_quant_norm's partition and
+// traversal per message, so a p = 2 sum keeps its bits — then the encode over (block, message), every block folding
+// its message's partials (fold_row) and block 0 of a message writing its norm.  Partials are per message: one
+// message's NaN or inf stays its own.
+// ------------------------------------------------------------------------------------------------
+constexpr int kRoundMsgs = 64;
+
+struct RoundMsg {
+  const float* x;
+  uint8_t* codes;
+  float* norm;
+  unsigned long long* count;  // nonzero elements (nullptr: not counted)
+  uint64_t seed, counter;
+};
+struct RoundTable {
+  RoundMsg m[kRoundMsgs];
+};
+
+// grid (parts, messages); msg0: the table's first message (its partials' row in the workspace)
+template <int NORM>
+__global__ __launch_bounds__(kThreads) void quant_round_norm_kernel(RoundTable tab, int64_t n, int64_t chunk, QuantWs ws,
+                                                                    int msg0) {
+  __shared__ unsigned long long s_red[kNW];
+  const RoundMsg& m = tab.m[blockIdx.y];
+  const int part = blockIdx.x;
+  const int64_t lo = (int64_t)part * chunk;
+  const int64_t hi = lo + chunk < n ? lo + chunk : n;
+  const unsigned long long part_bits = norm_part<NORM>(m.x, lo, lo, hi, 1, s_red);
+  if (threadIdx.x == 0) {
+    ws.partials[(int64_t)(msg0 + blockIdx.y) * kNormMaxParts + part] = part_bits;
+    if (part == 0 && m.count) *m.count = 0ull;  // (the encode launch, next in the stream, adds to it)
+  }
+}
+
+// grid (blocks of kThreads groups, messages)
+template <int KIND, int BITS, int NORM>
+__global__ __launch_bounds__(kThreads) void quant_round_encode_kernel(RoundTable tab, int64_t n, int s, double step,
+                                                                      QuantWs ws, int parts, int msg0) {
+  __shared__ unsigned long long s_nnz;
+  __shared__ float s_norm;
+  const RoundMsg& m = tab.m[blockIdx.y];
+  if (threadIdx.x == 0) s_nnz = 0ull;
+  if (threadIdx.x < kWave) {
+    const float v = fold_row<NORM>(parts, ws, msg0 + blockIdx.y);
+    if (threadIdx.x == 0) {
+      s_norm = v;
+      if (blockIdx.x == 0) *m.norm = v;
+    }
+  }
+  __syncthreads();
+  const bool count = m.count != nullptr;
+  const int64_t e0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * kGroup;
+  if (e0 < n) {
+    const int valid = n - e0 < kGroup ? (int)(n - e0) : kGroup;
+    float v[kGroup];
+    load_group(m.x, e0, valid, v);
+    uint32_t wd[kGroup];
+    group_words(e0, m.seed, m.counter, wd);
+    philox_group_encode<KIND, BITS, false>(
+        v, wd, e0, valid, n, s, step, m.codes, nullptr, count, [&](int64_t) { return s_norm; },
+        [&](int64_t, int cnt) { atomicAdd(&s_nnz, (unsigned long long)cnt); });
+  }
+  if (count) {  // (uniform: the message's)
+    __syncthreads();
+    if (threadIdx.x == 0 && s_nnz != 0) atomicAdd(m.count, s_nnz);
   }
 }
 
@@ -940,6 +1019,35 @@ int launch_auto(const float* x, int64_t rows, int64_t d, int levels, int norm_p,
   return FLC_OK;
 }
 
+// the round's two launches per table of up to kRoundMsgs messages, chained on the stream
+template <int KIND, int BITS>
+int launch_round(const float* const* xs, int n_msgs, int64_t n, int levels, int norm_p, const uint64_t* seeds,
+                 const uint64_t* counters, uint8_t* const* codes, float* const* norms, int64_t* const* counts,
+                 const QuantWs& w, int64_t parts, int64_t chunk, hipStream_t st) {
+  const double step = level_step(levels);
+  const unsigned nb1 = (unsigned)cdiv(n, (int64_t)kGroup * kThreads);
+  for (int c0 = 0; c0 < n_msgs; c0 += kRoundMsgs) {
+    const int m = std::min(n_msgs - c0, kRoundMsgs);
+    RoundTable tab{};
+    for (int i = 0; i < m; ++i)
+      tab.m[i] = RoundMsg{xs[c0 + i], codes[c0 + i], norms[c0 + i],
+                          counts ? reinterpret_cast<unsigned long long*>(counts[c0 + i]) : nullptr, seeds[c0 + i],
+                          counters[c0 + i]};
+    if (norm_p == FLC_NORM_INF) {
+      FLC_LAUNCH("quant_round_norm", quant_round_norm_kernel<FLC_NORM_INF>, dim3((unsigned)parts, (unsigned)m),
+                 dim3(kThreads), 0, st, tab, n, chunk, w, c0);
+      FLC_LAUNCH("quant_round_encode", (quant_round_encode_kernel<KIND, BITS, FLC_NORM_INF>), dim3(nb1, (unsigned)m),
+                 dim3(kThreads), 0, st, tab, n, levels, step, w, (int)parts, c0);
+    } else {
+      FLC_LAUNCH("quant_round_norm", quant_round_norm_kernel<FLC_NORM_L2>, dim3((unsigned)parts, (unsigned)m),
+                 dim3(kThreads), 0, st, tab, n, chunk, w, c0);
+      FLC_LAUNCH("quant_round_encode", (quant_round_encode_kernel<KIND, BITS, FLC_NORM_L2>), dim3(nb1, (unsigned)m),
+                 dim3(kThreads), 0, st, tab, n, levels, step, w, (int)parts, c0);
+    }
+  }
+  return FLC_OK;
+}
+
 }  // namespace
 }  // namespace flc
 
@@ -972,6 +1080,51 @@ int flc_quant_encode_auto(const float* x, int64_t rows, int64_t d, int kind, int
     FLC_AUTO(1, 2);
   }
 #undef FLC_AUTO
+}
+
+size_t flc_quant_encode_round_workspace_size(int64_t n, int n_msgs) {
+  (void)n;  // (the partials' rows are kNormMaxParts wide whatever n)
+  Carver c(nullptr, 0);
+  (void)c.take<unsigned long long>((size_t)(n_msgs < 1 ? 1 : n_msgs) * kNormMaxParts);
+  return c.off;
+}
+
+int flc_quant_encode_round(const float* const* xs, int n_msgs, int64_t n, int kind, int levels, int bits, int norm_p,
+                           const uint64_t* seeds, const uint64_t* counters, uint8_t* const* codes,
+                           float* const* norms, int64_t* const* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (!xs || !seeds || !counters || !codes || !norms) return fail(FLC_EINVAL, "flc_quant_encode_round: null table");
+  if (n_msgs < 1) return fail(FLC_EINVAL, "flc_quant_encode_round: n_msgs %d < 1", n_msgs);
+  if (n < 1 || n >= (int64_t)1 << 31) return fail(FLC_EINVAL, "flc_quant_encode_round: n must be in [1, 2^31)");
+  if (norm_p != FLC_NORM_INF && norm_p != FLC_NORM_L2)
+    return fail(FLC_EINVAL, "flc_quant_encode_round: p must be inf(0) or 2");
+  if (int rc = check_quant_args(kind, levels, bits)) return rc;
+  for (int c = 0; c < n_msgs; ++c) {
+    if (!xs[c] || !codes[c] || !norms[c] || (counts && !counts[c]))
+      return fail(FLC_EINVAL, "flc_quant_encode_round: null entry for message %d", c);
+    if (!aligned16(xs[c]) || !aligned16(codes[c]))
+      return fail(FLC_EINVAL, "flc_quant_encode_round: xs[%d] and codes[%d] must be 16-B aligned", c, c);
+  }
+  const size_t need = flc_quant_encode_round_workspace_size(n, n_msgs);
+  if (need > ws_bytes || !ws) return fail(FLC_EWORKSPACE, "flc_quant_encode_round: workspace %zu < %zu", ws_bytes, need);
+  QuantWs w{};
+  w.partials = Carver(ws, ws_bytes).take<unsigned long long>((size_t)n_msgs * kNormMaxParts);
+  // flc_quant_norm's partition of one row of n elements
+  int64_t parts = std::min<int64_t>(cdiv(n, kNormChunk), kNormMaxParts);
+  const int64_t chunk = align_up((size_t)cdiv(n, parts), 4);
+  parts = cdiv(n, chunk);
+  hipStream_t st = as_stream(stream);
+#define FLC_ROUND(K, B) \
+  return launch_round<K, B>(xs, n_msgs, n, levels, norm_p, seeds, counters, codes, norms, counts, w, parts, chunk, st)
+  if (kind == FLC_Q_STANDARD_DITHER) {
+    if (bits == 8) FLC_ROUND(0, 8);
+    if (bits == 4) FLC_ROUND(0, 4);
+    FLC_ROUND(0, 2);
+  } else {
+    if (bits == 8) FLC_ROUND(1, 8);
+    if (bits == 4) FLC_ROUND(1, 4);
+    FLC_ROUND(1, 2);
+  }
+#undef FLC_ROUND
 }
 
 int flc_quant_encode(const float* x, int64_t rows, int64_t d, int kind, int levels, int bits, const float* norms,

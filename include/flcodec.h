@@ -108,6 +108,22 @@ int flc_quant_encode_decode(const float* x, int64_t rows, int64_t d, int kind, i
 int flc_quant_encode_auto(const float* x, int64_t rows, int64_t d, int kind, int levels, int bits, int norm_p,
                           uint64_t seed, uint64_t counter, uint8_t* codes, float* norms, int64_t* nnz, float* out,
                           void* ws, size_t ws_bytes, void* stream);
+/* a round's messages in one call (philox mode, norm included): message c is the flat vector xs[c] of n elements with
+ * its own Philox (seeds[c], counters[c]), its own code stream codes[c] (ceil(n * bits / 8) bytes), norm *norms[c]
+ * and, with counts != NULL, nonzero count *counts[c] (device int64, zeroed in the stream by the call); the element
+ * index restarts at 0 in every message.  Every output is bit-identical to flc_quant_encode_auto(xs[c], 1, n, ...,
+ * seeds[c], counters[c], codes[c], norms[c], counts[c], NULL, ...), whichever launch form that call takes (p = 2
+ * keeps flc_quant_norm's partition and traversal per message).  Two ordinary launches per 64 messages for any n — the
+ * norm partials over (part, message), the encode over (block, message), each block folding its message's partials —
+ * with the message table in the kernel arguments: no grid-wide wait, no status word, nothing copied from the host
+ * arrays, capturable into a graph; more than 64 messages chain launches.  xs, seeds, counters, codes, norms and counts
+ * are HOST arrays of n_msgs entries.  FLC_EINVAL (nothing launched): a null table or entry (counts itself may be
+ * NULL), n_msgs < 1, n < 1 or n >= 2^31, levels not fitting bits, norm_p other than 0 or 2, an xs[c] or codes[c] not
+ * 16-B aligned.  FLC_EWORKSPACE: ws_bytes < flc_quant_encode_round_workspace_size(n, n_msgs). */
+size_t flc_quant_encode_round_workspace_size(int64_t n, int n_msgs);
+int flc_quant_encode_round(const float* const* xs, int n_msgs, int64_t n, int kind, int levels, int bits, int norm_p,
+                           const uint64_t* seeds, const uint64_t* counters, uint8_t* const* codes,
+                           float* const* norms, int64_t* const* counts, void* ws, size_t ws_bytes, void* stream);
 /* the quantizer workspace's sticky error word (4: a one-launch encode's grid exchange timed out, i.e. its blocks were
  * not all resident — the outputs of that call are invalid); copied to *err_out (device uint64), zeroed with reset */
 int flc_quant_status(void* ws, uint64_t* err_out, int reset, void* stream);
@@ -288,7 +304,8 @@ int flc_fold_record_groups(const void* const* records, const float* weights, con
  * compressor) and offsets[1] the codes (16-B aligned; ceil(n * bits / 8) bytes, 2n for the natural compressor).  The
  * layout depends on (n, format, bits) only, so a [clients, stride] block moves as one piece.  The encoders write a
  * record when given those pointers inside it: flc_quant_encode (norms = the record's norm field, written by
- * flc_quant_norm or by the caller), flc_quant_encode_auto with out == NULL, flc_natural_encode. */
+ * flc_quant_norm or by the caller), flc_quant_encode_auto with out == NULL, flc_quant_encode_round (a round's records
+ * in one call), flc_natural_encode. */
 enum flc_dense_wire_format { FLC_WIRE_NATURAL = 2 /* beside FLC_Q_STANDARD_DITHER = 0, FLC_Q_NATURAL_DITHER = 1 */ };
 size_t flc_dense_wire_layout(int64_t n, int format, int bits, int64_t* offsets);
 /* flc_stacked_fold_wires' contract over dense records (the server's weighted aggregation, nodes.py:1165-1180 /
