@@ -976,172 +976,89 @@ def _model_fold_op():
     return _MODEL_FOLD_OP[0]
 
 
+def _flcfold_entry(cell: list, name: str):
+    """fl_sim_amd._flcfold.<name> (csrc/pyfold.cpp: the C-ABI call on Python lists of tensors, no dispatcher boxing)
+    when built, else None (the ctypes path); a missing module and a missing entry both count as not built.  Looked up
+    once: ``cell`` is the entry's module-level one-element cache, empty until then.  The cells stay module attributes
+    because the tests force the ctypes path by replacing one (``monkeypatch.setattr(codec, "_PYFOLD", [None])``)."""
+    if not cell:
+        try:
+            from . import _flcfold
+
+            cell.append(getattr(_flcfold, name))
+        except (ImportError, AttributeError):
+            cell.append(None)
+    return cell[0]
+
+
 _PYFOLD: list = []
+_PYSRV: list = []
+_PYPAIR: list = []
+_PYRECS: list = []
+_PYDRECS: list = []
+_PYGROUPS: list = []
+_PYGRECS: list = []
+_PYFLAT: list = []
+_PYROUND: list = []
+_PYDELTA: list = []
+_PYEF: list = []
 
 
 def _pyfold():
-    """fl_sim_amd._flcfold.model_fold (csrc/pyfold.cpp: the fold on Python lists of tensors, no dispatcher boxing,
-    more than 16 messages in chained launches) when built, else None."""
-    if not _PYFOLD:
-        try:
-            from . import _flcfold
-
-            _PYFOLD.append(_flcfold.model_fold)
-        except ImportError:
-            _PYFOLD.append(None)
-    return _PYFOLD[0]
-
-
-_PYSRV: list = []
+    """_flcfold.model_fold (the fold on lists of tensors, more than 16 messages in chained launches), or None."""
+    return _flcfold_entry(_PYFOLD, "model_fold")
 
 
 def _pysrv():
-    """fl_sim_amd._flcfold.server_fold (csrc/pyfold.cpp: flc_model_fold_server on Python lists of tensors, at most 16
-    messages) when built, else None."""
-    if not _PYSRV:
-        try:
-            from . import _flcfold
-
-            _PYSRV.append(_flcfold.server_fold)
-        except (ImportError, AttributeError):
-            _PYSRV.append(None)
-    return _PYSRV[0]
-
-
-_PYPAIR: list = []
+    """_flcfold.server_fold (flc_model_fold_server on lists of tensors, at most 16 messages), or None."""
+    return _flcfold_entry(_PYSRV, "server_fold")
 
 
 def _pypair():
-    """fl_sim_amd._flcfold.avg_and_gradients (csrc/pyfold.cpp: flc_avg_and_gradients on Python lists of tensors and
-    message mappings) when built, else None."""
-    if not _PYPAIR:
-        try:
-            from . import _flcfold
-
-            _PYPAIR.append(_flcfold.avg_and_gradients)
-        except (ImportError, AttributeError):
-            _PYPAIR.append(None)
-    return _PYPAIR[0]
-
-
-_PYDELTA: list = []
-_PYFLAT: list = []
-_PYBATCH: list = []
-_PYRECS: list = []
+    """_flcfold.avg_and_gradients (flc_avg_and_gradients on lists of tensors and message mappings), or None."""
+    return _flcfold_entry(_PYPAIR, "avg_and_gradients")
 
 
 def _pyrecs():
-    """fl_sim_amd._flcfold.fold_records (flc_fedopt_fold_records on Python lists, one C call) when built, else None."""
-    if not _PYRECS:
-        try:
-            from . import _flcfold
-
-            _PYRECS.append(_flcfold.fold_records)
-        except (ImportError, AttributeError):
-            _PYRECS.append(None)
-    return _PYRECS[0]
-
-
-_PYDRECS: list = []
+    """_flcfold.fold_records (flc_fedopt_fold_records on lists, one C call), or None."""
+    return _flcfold_entry(_PYRECS, "fold_records")
 
 
 def _pydrecs():
-    """fl_sim_amd._flcfold.fold_dense_records (flc_fedopt_fold_dense_records on Python lists, one C call) when built,
-    else None."""
-    if not _PYDRECS:
-        try:
-            from . import _flcfold
-
-            _PYDRECS.append(_flcfold.fold_dense_records)
-        except (ImportError, AttributeError):
-            _PYDRECS.append(None)
-    return _PYDRECS[0]
-
-
-_PYGROUPS: list = []
+    """_flcfold.fold_dense_records (flc_fedopt_fold_dense_records on lists, one C call), or None."""
+    return _flcfold_entry(_PYDRECS, "fold_dense_records")
 
 
 def _pygroups():
-    """fl_sim_amd._flcfold.fold_record_groups (flc_fold_record_groups on Python lists, one C call) when built, else
-    None."""
-    if not _PYGROUPS:
-        try:
-            from . import _flcfold
-
-            _PYGROUPS.append(_flcfold.fold_record_groups)
-        except (ImportError, AttributeError):
-            _PYGROUPS.append(None)
-    return _PYGROUPS[0]
-
-
-_PYGRECS: list = []
+    """_flcfold.fold_record_groups (flc_fold_record_groups on lists, one C call), or None."""
+    return _flcfold_entry(_PYGROUPS, "fold_record_groups")
 
 
 def _pygrecs():
-    """fl_sim_amd._flcfold.avg_and_gradient_records (flc_avg_and_gradient_records on Python lists, one C call) when
-    built, else None."""
-    if not _PYGRECS:
-        try:
-            from . import _flcfold
-
-            _PYGRECS.append(_flcfold.avg_and_gradient_records)
-        except (ImportError, AttributeError):
-            _PYGRECS.append(None)
-    return _PYGRECS[0]
+    """_flcfold.avg_and_gradient_records (flc_avg_and_gradient_records on lists, one C call), or None."""
+    return _flcfold_entry(_PYGRECS, "avg_and_gradient_records")
 
 
 def _pyflat():
-    """fl_sim_amd._flcfold.delta_flat (a new flat delta, flc_delta_flatten, one C call) when built, else None."""
-    if not _PYFLAT:
-        try:
-            from . import _flcfold
-
-            _PYFLAT.append(_flcfold.delta_flat)
-        except (ImportError, AttributeError):
-            _PYFLAT.append(None)
-    return _PYFLAT[0]
-
-
-def _pybatch():
-    """fl_sim_amd._flcfold.stacked_records_batch (the batched stacked encode into a record block and the batched
-    send counts, one C call) when built, else None."""
-    if not _PYBATCH:
-        try:
-            from . import _flcfold
-
-            _PYBATCH.append(_flcfold.stacked_records_batch)
-        except (ImportError, AttributeError):
-            _PYBATCH.append(None)
-    return _PYBATCH[0]
-
-
-_PYROUND: list = []
+    """_flcfold.delta_flat (a new flat delta, flc_delta_flatten, one C call), or None."""
+    return _flcfold_entry(_PYFLAT, "delta_flat")
 
 
 def _pyround():
-    """fl_sim_amd._flcfold.stacked_records_round (the round's stacked encode into a record block, one Philox counter
-    per message, the send counts made by the encode; one C call) when built, else None."""
-    if not _PYROUND:
-        try:
-            from . import _flcfold
-
-            _PYROUND.append(_flcfold.stacked_records_round)
-        except (ImportError, AttributeError):
-            _PYROUND.append(None)
-    return _PYROUND[0]
+    """_flcfold.stacked_records_round (the round's stacked encode into a record block, one Philox counter per
+    message, the send counts made by the encode; one C call), or None."""
+    return _flcfold_entry(_PYROUND, "stacked_records_round")
 
 
 def _pydelta():
-    """fl_sim_amd._flcfold.stacked_delta_record (csrc/pyfold.cpp: the delta-fused stacked encode into a wire record and
-    the send count, one C call on Python lists of tensors) when built, else None."""
-    if not _PYDELTA:
-        try:
-            from . import _flcfold
+    """_flcfold.stacked_delta_record (the delta-fused stacked encode into a wire record and the send count, one C
+    call), or None."""
+    return _flcfold_entry(_PYDELTA, "stacked_delta_record")
 
-            _PYDELTA.append(_flcfold.stacked_delta_record)
-        except (ImportError, AttributeError):
-            _PYDELTA.append(None)
-    return _PYDELTA[0]
+
+def _pyef():
+    """_flcfold.ef_accumulate (flc_ef_accumulate on lists of tensors, one C call), or None."""
+    return _flcfold_entry(_PYEF, "ef_accumulate")
 
 
 def model_fold_server(theta: Sequence[torch.Tensor], aux: Sequence[torch.Tensor],
@@ -1379,22 +1296,6 @@ def ef_residual_dense(e: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(e.device):
         call("flc_ef_residual_dense", _p(e), _p(c), e.numel(), _stream(e.device))
     return e
-
-
-_PYEF: list = []
-
-
-def _pyef():
-    """fl_sim_amd._flcfold.ef_accumulate (flc_ef_accumulate on Python lists of tensors, one C call) when built, else
-    None."""
-    if not _PYEF:
-        try:
-            from . import _flcfold
-
-            _PYEF.append(_flcfold.ef_accumulate)
-        except (ImportError, AttributeError):
-            _PYEF.append(None)
-    return _PYEF[0]
 
 
 # ---------------------------------------------------------------------------------------- float64 inputs

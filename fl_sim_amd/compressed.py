@@ -78,9 +78,10 @@ from __future__ import annotations
 
 import collections.abc as _abc
 import ctypes
+import functools
 import math
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -231,6 +232,19 @@ def _fp32_on(ts: Sequence[torch.Tensor], dev: torch.device) -> List[torch.Tensor
     return out
 
 
+def _norm_kind(p) -> Optional[int]:
+    """The device norm of a dithering compressor's ``p``: FLC_NORM_INF, FLC_NORM_L2, or None (any other p)."""
+    return FLC_NORM_INF if math.isinf(p) else (FLC_NORM_L2 if p == 2 else None)
+
+
+@functools.lru_cache(maxsize=None)
+def _code_fraction(s: int):
+    """What one dithered element adds to the send count, in fp32 elements: its sign and one of ``s`` levels in
+    1 + ceil(log2 s) of 32 bits (compressors.py:365 / 404).  Remembered per ``s``: it is asked once per message, and
+    numpy's ceil of a scalar costs more than the rest of the enqueue."""
+    return (1.0 + np.ceil(math.log2(s))) / 32.0
+
+
 def _norm_stage_send(sd: Compressor, norm: torch.Tensor) -> float:
     """The norm compressor's pass over the one-element norm vector (compressors.py:334-337) and the send count it
     contributes; an identical norm compressor (the reference's usual one) is advanced without reading the norm back."""
@@ -311,7 +325,7 @@ def _dense_record(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[i
         comp._finish(n, 9.0 / 32.0 * n)  # compressors.py:325
         return CompressedDelta(shapes, dev, n, record=rec, levels=0, format=fmt, bits=bits)
     std = fmt == FLC_Q_STANDARD_DITHER
-    per = (1.0 + np.ceil(math.log2(s))) / 32.0  # compressors.py:365 / 404
+    per = _code_fraction(s)
     ws = codec.workspace(dev, codec._ws_size(dev, "flc_quant_workspace_size", 1, n), "quant")
     host_norm = None
     if comp._wants_host_norm(device_input=True):  # the reference's np.linalg.norm (compressors.py:332 / 372)
@@ -321,7 +335,7 @@ def _dense_record(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[i
     if not compat:
         cnt = comp._count_slot(dev) if std else None
         if host_norm is None:  # norm and encode together (the record's norm field is the encode's norms output)
-            pk = FLC_NORM_INF if math.isinf(comp.p) else (FLC_NORM_L2 if comp.p == 2 else None)
+            pk = _norm_kind(comp.p)
             if pk is None:
                 raise ValueError(f"p must be inf or 2 (got {comp.p})")
             _lib.call("flc_quant_encode_auto", x.data_ptr(), 1, n, fmt, s, bits, pk, seed, ctr, codes.data_ptr(),
@@ -336,7 +350,7 @@ def _dense_record(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[i
             comp._finish(n, n * per)
         return CompressedDelta(shapes, dev, n, record=rec, levels=s, format=fmt, bits=bits)
     if host_norm is None:
-        pk = FLC_NORM_INF if math.isinf(comp.p) else (FLC_NORM_L2 if comp.p == 2 else None)
+        pk = _norm_kind(comp.p)
         if pk is None:
             raise ValueError(f"p must be inf or 2 (got {comp.p})")
         _lib.call("flc_quant_norm", x.data_ptr(), 1, n, pk, norm.data_ptr(), ws.data_ptr(), ws.numel(), st)
@@ -482,26 +496,50 @@ _DEFER_MAX_BATCHES = 16
 
 
 _STATS = {"batches": 0, "messages": 0}
+_DENSE_STATS = {"batches": 0, "messages": 0}
+
+
+def _read_stats(stats: dict, reset: bool) -> dict:
+    out = dict(stats)
+    if reset:
+        stats.update(batches=0, messages=0)
+    return out
 
 
 def deferred_stats(reset: bool = False) -> dict:
     """``{"batches": batched encodes run, "messages": messages they encoded}`` since import or since the last
     ``deferred_stats(reset=True)`` (which returns the figures up to then)."""
-    out = dict(_STATS)
-    if reset:
-        _STATS.update(batches=0, messages=0)
-    return out
+    return _read_stats(_STATS, reset)
+
+
+def deferred_dense_stats(reset: bool = False) -> dict:
+    """:func:`deferred_stats` for the dense records' batched encodes (flc_quant_encode_round), counted apart."""
+    return _read_stats(_DENSE_STATS, reset)
+
+
+class _Item(NamedTuple):
+    """One waiting message of a batch."""
+
+    delta: "CompressedDelta"  # the message's delta, which takes its record when the batch has encoded
+    flat: torch.Tensor  # the encoder's input: a snapshot of the flat vector, or the error memory's tensor
+    seed: int  # the message's Philox seed ...
+    counter: int  # ... and counter
+    count: Optional[torch.Tensor]  # the send-count slot the encode writes (None: the count does not depend on the data)
+    comp: Optional[Compressor]  # the compressor owning that slot
+    stream: torch.cuda.Stream  # the stream the flat vector was written on ...
+    handle: int  # ... and its handle
+    mem: Optional[ErrorMemory]  # the error memory whose tensor ``flat`` is, or None
 
 
 class _Batch:
     """The waiting messages of one (device, n, k, levels): a round's stacked records, encoded together.  The stream
     handling around the encode is shared with :class:`_DenseBatch`, which replaces :meth:`_encode_rows`."""
 
+    stats = _STATS
+
     def __init__(self, key):
         self.key = key
-        # (CompressedDelta, flat delta, seed, count slot, dithering compressor, stream, its handle, counter,
-        #  ErrorMemory whose tensor the flat delta is, or None)
-        self.items = []
+        self.items: List[_Item] = []
 
     def run(self) -> None:
         if _PENDING.get(self.key) is self:
@@ -521,17 +559,19 @@ class _Batch:
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
             ch = cur.cuda_stream
-            for st in {it[6]: it[5] for it in items if it[6] != ch}.values():  # (deltas flattened on other streams)
+            for st in {it.handle: it.stream for it in items if it.handle != ch}.values():  # (other streams' deltas)
                 cur.wait_stream(st)
             rows = self._encode_rows(items, dev)
-            for (d, flat, _, _, sd, _, sh, _, mem), r in zip(items, rows):
-                if sh != ch:
-                    flat.record_stream(cur)
-                    if sd is not None:
-                        sd._note_slab_stream(cur)  # (the count was written on this stream, not the slot's own)
-                if mem is not None:
-                    mem._written(cur)
-                d._record, d._batch = r, None
+            self.stats["batches"] += 1
+            self.stats["messages"] += len(items)
+            for it, r in zip(items, rows):
+                if it.handle != ch:
+                    it.flat.record_stream(cur)
+                    if it.comp is not None:
+                        it.comp._note_slab_stream(cur)  # (the count was written on this stream, not the slot's own)
+                if it.mem is not None:
+                    it.mem._written(cur)
+                it.delta._record, it.delta._batch = r, None
 
     def _encode_rows(self, items, dev):
         """The items' records, encoded on ``dev``'s current stream: the rows of one ``[C, stride]`` block."""
@@ -539,8 +579,8 @@ class _Batch:
         stride, _ = codec.stacked_wire_layout(n, k)
         C = len(items)
         recs = torch.empty(C, stride, dtype=torch.uint8, device=dev)
-        flats = [it[1] for it in items]
-        seeds, ctrs, cnts = [it[2] for it in items], [it[7] for it in items], [it[3] for it in items]
+        flats = [it.flat for it in items]
+        seeds, ctrs, cnts = [it.seed for it in items], [it.counter for it in items], [it.count for it in items]
         fast = codec._pyround()
         if fast is not None:  # one C call: the encode's launch chain fills the count slots too
             ws = codec.workspace(dev, codec._ws_size(dev, "flc_stacked_encode_batch_workspace_size", n, k, C),
@@ -550,12 +590,10 @@ class _Batch:
             codec.stacked_encode_batch(flats, k, levels, seeds=seeds, counters=ctrs, counts=cnts, wires=recs)
         codec._after_encode(dev)
         rows = recs.unbind(0)
-        fed = [(r, it[8]) for it, r in zip(items, rows) if it[8] is not None]
+        fed = [(r, it.mem) for it, r in zip(items, rows) if it.mem is not None]
         if fed:  # error feedback: e = a − c at the records' kept entries, one launch for the round (an encode
             # that raised never gets here: the memories then still hold a, and the retry encodes the same a)
             codec.ef_residual_round([r for r, _ in fed], [m._e for _, m in fed], n, k, levels)
-        _STATS["batches"] += 1
-        _STATS["messages"] += C
         return rows
 
 
@@ -570,31 +608,21 @@ class _Batch:
 # at 2 M and 248 against 137 us for eight messages of 4 M — past ~1.5 M elements the per-message call's one-launch
 # form, which reads the vector once, beats two streaming launches — so larger messages keep the immediate path.
 _DEFER_DENSE_MAX_N = 1 << 20
-_DENSE_STATS = {"batches": 0, "messages": 0}
-
-
-def deferred_dense_stats(reset: bool = False) -> dict:
-    """:func:`deferred_stats` for the dense records' batched encodes (flc_quant_encode_round), counted apart."""
-    out = dict(_DENSE_STATS)
-    if reset:
-        _DENSE_STATS.update(batches=0, messages=0)
-    return out
 
 
 class _DenseBatch(_Batch):
     """The waiting dense-record messages of one (device, "quant", n, format, levels, bits, norm_p); an item's count
     slot and compressor are None for natural dithering, whose send count does not depend on the data."""
 
+    stats = _DENSE_STATS
+
     def _encode_rows(self, items, dev):
         _, _, n, fmt, levels, bits, pk = self.key
         stride, _ = codec.dense_wire_layout(n, fmt, bits)
-        C = len(items)
-        recs = torch.empty(C, stride, dtype=torch.uint8, device=dev)
-        codec.quant_encode_round([it[1] for it in items], fmt, levels, bits, pk, [it[2] for it in items],
-                                 [it[7] for it in items], recs,
-                                 [it[3] for it in items] if fmt == FLC_Q_STANDARD_DITHER else None)
-        _DENSE_STATS["batches"] += 1
-        _DENSE_STATS["messages"] += C
+        recs = torch.empty(len(items), stride, dtype=torch.uint8, device=dev)
+        codec.quant_encode_round([it.flat for it in items], fmt, levels, bits, pk, [it.seed for it in items],
+                                 [it.counter for it in items], recs,
+                                 [it.count for it in items] if fmt == FLC_Q_STANDARD_DITHER else None)
         return recs.unbind(0)
 
 
@@ -625,28 +653,41 @@ def _deferred(local, cached, shapes, n: int, K: int, s: int, tk: Compressor, sd:
     return _defer(flat, shapes, n, K, s, tk, sd, dev, seed_ctr, None)
 
 
+def _waiting(cls, key) -> "_Batch":
+    """The waiting batch under ``key``, made (of class ``cls``) when there is none."""
+    b = _PENDING.get(key)
+    if b is None:
+        b = _PENDING[key] = cls(key)
+    return b
+
+
+def _enqueue(b: "_Batch", item: _Item) -> CompressedDelta:
+    """``item`` joins the waiting batch ``b``; its delta.  A full batch is encoded at once, and with too many batches
+    waiting all of them are."""
+    b.items.append(item)
+    if item.mem is not None:
+        item.mem._batch = b
+    if len(b.items) >= _DEFER_MAX_PENDING:
+        b.run()
+    elif len(_PENDING) > _DEFER_MAX_BATCHES:  # (messages nobody reads: the waiting deltas stay bounded)
+        _run_pending()
+    return item.delta
+
+
 def _defer(flat: torch.Tensor, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compressor, dev, seed_ctr,
            mem: Optional[ErrorMemory]) -> CompressedDelta:
     """The message of the flat vector ``flat`` joins the round's batched encode (``mem``: ``flat`` is that error
     memory's tensor, which takes the residual once the batch has encoded)."""
     st = torch.cuda.current_stream(dev)
-    cnt = sd._count_slot(dev, st)  # (before the batch is looked up: a full slab is read back, running the batches)
-    key = (dev.index, n, K, s)
-    b = _PENDING.get(key)
-    if b is None:
-        b = _PENDING[key] = _Batch(key)
+    # the slot before the batch is looked up: a full slab is read back, running the batches.  With the slot in hand the
+    # compressors' pending lists have room, so the _finish calls below read nothing back and run no batch: they come
+    # before the item is appended only so that the append and the bounds sit in one place (_enqueue)
+    cnt = sd._count_slot(dev, st)
+    b = _waiting(_Batch, (dev.index, n, K, s))
     d = CompressedDelta(shapes, dev, n, k=K, levels=s, batch=b)
-    b.items.append((d, flat, seed_ctr[0], cnt, sd, st, st.cuda_stream, seed_ctr[1], mem))
-    if mem is not None:
-        mem._batch = b
     tk._finish(n, tk.K)
-    base = _norm_stage_send(sd, None)
-    sd._finish_pending(n, cnt, base, (1.0 + np.ceil(math.log2(sd.s))) / 32.0)  # compressors.py:365
-    if len(b.items) >= _DEFER_MAX_PENDING:
-        b.run()
-    elif len(_PENDING) > _DEFER_MAX_BATCHES:  # (messages nobody reads: the waiting deltas stay bounded)
-        _run_pending()
-    return d
+    sd._finish_pending(n, cnt, _norm_stage_send(sd, None), _code_fraction(sd.s))
+    return _enqueue(b, _Item(d, flat, seed_ctr[0], seed_ctr[1], cnt, sd, st, st.cuda_stream, mem))
 
 
 def _defer_dense(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[int, int, int],
@@ -658,30 +699,21 @@ def _defer_dense(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[in
     fmt, s, bits = dc
     if comp.rng_mode != "philox" or comp._wants_host_norm(device_input=True):
         return None
-    pk = FLC_NORM_INF if math.isinf(comp.p) else (FLC_NORM_L2 if comp.p == 2 else None)
+    pk = _norm_kind(comp.p)
     if pk is None or x.dtype != torch.float32 or x.device != dev:
         return None
     x = codec._dev_f32(x).reshape(-1)
     std = fmt == FLC_Q_STANDARD_DITHER
     st = torch.cuda.current_stream(dev)
-    cnt = comp._count_slot(dev, st) if std else None  # (before the batch is looked up, as in _defer)
-    key = (dev.index, "quant", n, fmt, s, bits, pk)
-    b = _PENDING.get(key)
-    if b is None:
-        b = _PENDING[key] = _DenseBatch(key)
+    cnt = comp._count_slot(dev, st) if std else None  # (before the batch is looked up and the _finish calls, as in _defer)
+    b = _waiting(_DenseBatch, (dev.index, "quant", n, fmt, s, bits, pk))
     seed, ctr = comp.philox.next()
     d = CompressedDelta(shapes, dev, n, levels=s, batch=b, format=fmt, bits=bits)
-    b.items.append((d, x, seed, cnt, comp if std else None, st, st.cuda_stream, ctr, None))
-    per = (1.0 + np.ceil(math.log2(s))) / 32.0  # compressors.py:365 / 404
     if std:
-        comp._finish_pending(n, cnt, _norm_stage_send(comp, None), per)
+        comp._finish_pending(n, cnt, _norm_stage_send(comp, None), _code_fraction(s))
     else:
-        comp._finish(n, n * per)
-    if len(b.items) >= _DEFER_MAX_PENDING:
-        b.run()
-    elif len(_PENDING) > _DEFER_MAX_BATCHES:  # (messages nobody reads: the waiting deltas stay bounded)
-        _run_pending()
-    return d
+        comp._finish(n, n * _code_fraction(s))
+    return _enqueue(b, _Item(d, x, seed, ctr, cnt, comp if std else None, st, st.cuda_stream, None))
 
 
 def _stacked_fast(local, cached, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compressor, dev,
@@ -702,7 +734,7 @@ def _stacked_fast(local, cached, shapes, n: int, K: int, s: int, tk: Compressor,
     tk._finish(n, tk.K)
     nc = sd.vectorNormCompressor
     base = _norm_stage_send(sd, None if _identical(nc) else codec.wire_packet(rec, n, K, s).norm)
-    sd._finish_pending(n, cnt, base, (1.0 + np.ceil(math.log2(sd.s))) / 32.0)  # compressors.py:365
+    sd._finish_pending(n, cnt, base, _code_fraction(sd.s))
     return CompressedDelta(shapes, dev, n, record=rec, k=K, levels=s)
 
 
@@ -716,7 +748,7 @@ def _stacked(ls, gs, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compres
     stride, _ = codec.stacked_wire_layout(n, K)
     rec = torch.empty(stride, dtype=torch.uint8, device=dev)
     pk = codec.wire_packet(rec, n, K, s)
-    per = (1.0 + np.ceil(math.log2(sd.s))) / 32.0  # compressors.py:365
+    per = _code_fraction(sd.s)
     seed, ctr = seed_ctr if seed_ctr is not None else sd.philox.next()
     if sd.rng_mode == "philox":
         # the delta formed inside the encoder's read; the dithering stage's nonzero count stays on the device
@@ -759,16 +791,25 @@ def _stacked(ls, gs, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compres
     return CompressedDelta(shapes, dev, n, record=rec, k=K, levels=s)
 
 
-def stacked_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
-    """The messages' compressed deltas when every one is a stacked record of one (n, k, levels), else None."""
+def _round_deltas(messages: Sequence, key: str, kinds: Tuple[str, ...]) -> Optional[List[CompressedDelta]]:
+    """The messages' compressed deltas under ``key`` when there are messages and every one carries a
+    :class:`CompressedDelta` of one of ``kinds``, else None."""
     if not messages:
         return None
     ds = []
     for m in messages:
         d = m.get(key) if isinstance(m, dict) else None
-        if not isinstance(d, CompressedDelta) or d.kind != "stacked":
+        if not isinstance(d, CompressedDelta) or d.kind not in kinds:
             return None
         ds.append(d)
+    return ds
+
+
+def stacked_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
+    """The messages' compressed deltas when every one is a stacked record of one (n, k, levels), else None."""
+    ds = _round_deltas(messages, key, ("stacked",))
+    if ds is None:
+        return None
     d0 = ds[0]
     if any((d.n, d.k, d.levels) != (d0.n, d0.k, d0.levels) for d in ds):
         return None
@@ -778,15 +819,11 @@ def stacked_round(messages: Sequence, key: str = "delta_parameters") -> Optional
 def dense_record_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
     """The messages' compressed deltas when every one is a dense record (``kind`` "quant" or "natural") of one
     (n, format, levels, bits), else None (a mixed round: each message then decodes itself)."""
-    if not messages:
+    ds = _round_deltas(messages, key, ("quant", "natural"))
+    if ds is None:
         return None
-    ds = []
-    for m in messages:
-        d = m.get(key) if isinstance(m, dict) else None
-        if not isinstance(d, CompressedDelta) or d.kind not in ("quant", "natural"):
-            return None
-        ds.append(d)
-    if any(d.codec_key != ds[0].codec_key for d in ds):
+    key0 = ds[0].codec_key
+    if any(d.codec_key != key0 for d in ds):
         return None
     return ds
 

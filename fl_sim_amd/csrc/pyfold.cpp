@@ -1,20 +1,36 @@
-// pyfold.cpp — `fl_sim_amd._flcfold.model_fold`: the server's whole-model fold (flc_model_fold) called straight from
-// Python lists of tensors, for the per-round host path of FedOptServer.update / avg_parameters / add_parameters /
-// update_gradients (_fedopt.py:196-240, nodes.py:1116-1180); `server_fold`, the same for FedDyn's and pFedMe's server
-// updates (flc_model_fold_server); `avg_and_gradients`, the variance-reduced servers' avg_parameters + update_gradients
-// (flc_avg_and_gradients), and `avg_and_gradient_records`, the same over compressed gradients
-// (flc_avg_and_gradient_records); `fold_record_groups`, a round of records folded into several models
-// (flc_fold_record_groups); `stacked_delta_record`, a client's compressed message (flc_stacked_encode_delta into a wire
-// record + flc_delta_count_nonzero_at).
+// pyfold.cpp — `fl_sim_amd._flcfold`: the C ABI of include/flcodec.h called straight from Python lists of tensors, for
+// the per-round host path of every server update and every compressed message.  The entries:
+//   model_fold                flc_model_fold: FedOptServer.update / avg_parameters / add_parameters / update_gradients
+//                             (_fedopt.py:196-240, nodes.py:1116-1180)
+//   server_fold               flc_model_fold_server: FedDyn's and pFedMe's server updates
+//   avg_and_gradients         flc_avg_and_gradients: the variance-reduced servers' avg_parameters + update_gradients
+//   avg_and_gradient_records  flc_avg_and_gradient_records: the same over compressed gradients
+//   fold_records              flc_fedopt_fold_records: the server update of a round of stacked records
+//   fold_dense_records        flc_fedopt_fold_dense_records: the same for dense records
+//   fold_record_groups        flc_fold_record_groups: a round of records folded into several models
+//   stacked_delta_record      flc_stacked_encode_delta into a wire record + flc_delta_count_nonzero_at
+//   stacked_records_round     flc_stacked_encode_round into the rows of a record block
+//   delta_flat                flc_delta_flatten into a new flat tensor
+//   ef_accumulate             flc_ef_accumulate into a client's error memory
+//   alias                     a HIP-device tensor over a pinned host tensor's memory
 //
 // At configs[0] (cnn_femmist_tiny: 8 tensors, 10 clients) the kernel takes ~9 us, but going through the dispatcher
 // (torch.ops.flcodec.model_fold_) cost ~14 us of host time: every tensor of the 96 in the call is boxed into an IValue
 // list and unboxed again.  Here each Python tensor object is unpacked in place (THPVariable_Unpack, no refcount or
-// IValue traffic), checked (HIP device, fp32, contiguous, sizes) and its pointer written into the table the C ABI
-// takes; more than 16 messages are folded in chained launches (init mode 2 after the first launch, the optimizer
-// step fused into the last one — the same fmaf chain as one launch).  Nothing is launched before every tensor of
-// the call has passed its checks.  Errors: TypeError for a tensor the fold does not take (the caller then moves
-// messages or folds per tensor), ValueError for mismatched sizes or counts.
+// IValue traffic), checked (HIP device, dtype, contiguous, sizes) and its pointer written into the table the C ABI
+// takes.  Nothing is allocated or launched before every tensor of the call has passed its checks.
+//
+// The entries share one layer of helpers (the anonymous namespace's first part): `Refs` owns the references an entry
+// makes (fast sequences, mapping items) and releases them when the entry returns; `take` / `tensor_row` /
+// `message_row` / `record_ptr` / `as_f32` check one tensor, one list of tensors, one message, one wire record, one
+// weight and fill the pointer tables, reporting what they found as a `Bad` without raising, because the exception is
+// the entry's own: TypeError is the Python callers' cue that nothing ran and their other path is open (move the
+// messages, fold per tensor, decode densely), ValueError a mistake of theirs — and for the same finding (a list of
+// the wrong length, a tensor of the wrong size) the older entries raise ValueError where the record entries raise
+// TypeError.  Each entry keeps its own order of checks: which error wins when two inputs are wrong is part of its
+// contract (tests/test_pyfold_contract.py, tests/test_gpu_pyfold_contract.py).  `run_on` / `on_device` make the C
+// call: GIL released, the tensors' device current, a RuntimeError naming the call on a bad status; `new_flat` /
+// `gradient_views` / `views_result` are the new flat gradient buffer and its per-parameter views.
 //
 // `alias(host_tensor, device_index)`: a HIP-device tensor over the same memory as a pinned host tensor, for the host
 // server's zero-copy staging (hoststage.py): pinned host memory is mapped into every device's address space at the
@@ -42,20 +58,245 @@ PyObject* value_error(const char* msg) {
   return nullptr;
 }
 
-// a contiguous fp32 tensor on HIP device `dev` (-1: any HIP device, returned in *dev); nullptr if not one
-const at::Tensor* usable(PyObject* o, int* dev) {
+// ------------------------------------------------------------------------------------------------ the helper layer
+// The new references of one entry-point call, released when it returns (by any path).
+struct Refs {
+  std::vector<PyObject*> owned;
+  Refs() { owned.reserve(8); }
+  Refs(const Refs&) = delete;
+  Refs& operator=(const Refs&) = delete;
+  ~Refs() {
+    for (PyObject* o : owned) Py_DECREF(o);
+  }
+  // PySequence_Fast(o): the fast sequence (read with len / items), or nullptr with TypeError(msg) set
+  PyObject* fast(PyObject* o, const char* msg) {
+    PyObject* f = PySequence_Fast(o, msg);
+    if (f) owned.push_back(f);
+    return f;
+  }
+  // o[key], or nullptr with the lookup's error set
+  PyObject* item(PyObject* o, PyObject* key) {
+    PyObject* v = PyObject_GetItem(o, key);
+    if (v) owned.push_back(v);
+    return v;
+  }
+};
+inline Py_ssize_t len(PyObject* fast) { return PySequence_Fast_GET_SIZE(fast); }
+inline PyObject** items(PyObject* fast) { return PySequence_Fast_ITEMS(fast); }
+
+// a contiguous HIP tensor of `dt` on device `*dev` (-1: any HIP device, returned in *dev); nullptr if not one
+const at::Tensor* usable_as(PyObject* o, at::ScalarType dt, int* dev) {
   if (!THPVariable_Check(o)) return nullptr;
   const at::Tensor& t = THPVariable_Unpack(o);
-  if (!t.is_cuda() || t.scalar_type() != at::kFloat || !t.is_contiguous()) return nullptr;
+  if (!t.is_cuda() || t.scalar_type() != dt || !t.is_contiguous()) return nullptr;
   const int d = t.get_device();
   if (*dev < 0) *dev = d;
   else if (d != *dev) return nullptr;
   return &t;
 }
 
+// What a table builder found; nothing is raised except for kRaised (a Python call failed: its error is set).
+enum Bad { kOk = 0, kRaised, kBadCount, kBadTensor, kBadSize };
+
+// One fp32 tensor: its pointer into *out; its element count defines *size (`define`) or must equal it.
+template <class P>
+inline Bad take(PyObject* o, int* dev, int64_t* size, bool define, P* out, const at::Tensor** tensor = nullptr) {
+  const at::Tensor* a = usable_as(o, at::kFloat, dev);
+  if (!a) return kBadTensor;
+  if (define) *size = a->numel();
+  else if (a->numel() != *size) return kBadSize;
+  *out = a->data_ptr<float>();
+  if (tensor) *tensor = a;
+  return kOk;
+}
+
+// A sequence of nt fp32 tensors into out[0..nt): the first one's finding, tensor by tensor (sizes as take's).
+template <class P>
+inline Bad tensor_row(PyObject** it, Py_ssize_t nt, int* dev, int64_t* sz, bool define, P* out,
+                      const at::Tensor** tensors = nullptr) {
+  for (Py_ssize_t t = 0; t < nt; ++t)
+    if (Bad b = take(it[t], dev, sz + t, define, out + t, tensors ? tensors + t : nullptr)) return b;
+  return kOk;
+}
+
+// One message's tensor list — the message itself, or message[key] — of the model's nt sizes into row[0..nt).
+Bad message_row(Refs& refs, PyObject* msg, PyObject* key /* nullptr: no lookup */, const char* not_a_sequence,
+                Py_ssize_t nt, int* dev, int64_t* sz, const float** row) {
+  if (key && !(msg = refs.item(msg, key))) return kRaised;
+  PyObject* f = refs.fast(msg, not_a_sequence);
+  if (!f) return kRaised;
+  if (len(f) != nt) return kBadCount;
+  return tensor_row(items(f), nt, dev, sz, false, row);
+}
+// message_row's finding as the entry's exception: the fold entries' (a wrong count or size is the caller's mistake,
+// ValueError), or the record entries' (`all_type`: every finding is the cue for the other path, TypeError)
+PyObject* message_error(Bad b, bool all_type) {
+  if (b == kRaised) return nullptr;
+  if (b == kBadCount) return (all_type ? type_error : value_error)("every message has one tensor per model tensor");
+  if (all_type) return type_error("message tensors must be contiguous fp32 HIP tensors of the model's sizes and device");
+  if (b == kBadTensor) return type_error("message tensors must be contiguous fp32 HIP tensors on the model's device");
+  return value_error("message tensors must match the model tensors' sizes");
+}
+
+// theta / v (either may be None: its table stays empty) of the model's nt sizes; false with the error set.  The fold
+// entries raise ValueError for a wrong count or size, the record entries (`all_type`) TypeError.
+bool optimizer_rows(Refs& refs, PyObject* theta, PyObject* v, Py_ssize_t nt, int* dev, int64_t* sz, bool all_type,
+                    std::vector<float*>* tp, std::vector<float*>* vp) {
+  for (int which = 0; which < 2; ++which) {
+    PyObject* src = which == 0 ? theta : v;
+    if (src == Py_None) continue;
+    PyObject* f = refs.fast(src, "theta / v must be sequences of tensors");
+    if (!f) return false;
+    if (len(f) != nt) {
+      if (all_type) type_error("theta / v need one tensor per server tensor");
+      else value_error("theta / v need one tensor per model tensor");
+      return false;
+    }
+    std::vector<float*>& out = which == 0 ? *tp : *vp;
+    out.resize(nt);
+    if (Bad b = tensor_row(items(f), nt, dev, sz, false, out.data())) {
+      if (all_type) type_error("theta / v must match the server tensors");
+      else if (b == kBadTensor) type_error("theta / v tensors must be contiguous fp32 HIP tensors on the model's device");
+      else value_error("theta / v must match the model tensors' sizes");
+      return false;
+    }
+  }
+  return true;
+}
+
+// A weight as fp32 (rounded at the boundary, as torch's add_(alpha=...) does); false with the error set.
+inline bool as_f32(PyObject* o, float* out) {
+  const double d = PyFloat_AsDouble(o);
+  if (d == -1.0 && PyErr_Occurred()) return false;
+  *out = (float)d;
+  return true;
+}
+
+// A wire record — a contiguous uint8 tensor on `*dev` of at least `stride` bytes, 16-B aligned: its pointer, or
+// nullptr (nothing raised).
+inline const void* record_ptr(PyObject* o, size_t stride, int* dev) {
+  const at::Tensor* r = usable_as(o, at::kByte, dev);
+  if (!r || (size_t)r->numel() < stride || reinterpret_cast<uintptr_t>(r->data_ptr()) % 16 != 0) return nullptr;
+  return r->data_ptr();
+}
+
+// local / global (global nullptr: nothing subtracted) — a client's tensors and the cached model's, pair by pair of
+// one size — into lp / gp / sz, their element count into *n; false with the error set (`global_not_a_sequence`,
+// `bad_tensor`: the entry's TypeError texts).
+bool delta_tables(Refs& refs, PyObject* loc, PyObject* glo, const char* global_not_a_sequence, const char* bad_tensor,
+                  int* dev, std::vector<const float*>* lp, std::vector<const float*>* gp,
+                  std::vector<int64_t>* sz, int64_t* n) {
+  PyObject* fl = refs.fast(loc, "local must be a sequence of tensors");
+  if (!fl) return false;
+  PyObject* fg = nullptr;
+  if (glo && !(fg = refs.fast(glo, global_not_a_sequence))) return false;
+  const Py_ssize_t m = len(fl);
+  if (m < 1 || (fg && len(fg) != m)) {
+    value_error("one global tensor per local tensor, at least one");
+    return false;
+  }
+  lp->resize(m);
+  gp->resize(fg ? m : 0);
+  sz->resize(m);
+  *n = 0;
+  for (Py_ssize_t t = 0; t < m; ++t) {
+    Bad b = take(items(fl)[t], dev, &(*sz)[t], true, &(*lp)[t]);
+    if (!b && fg) b = take(items(fg)[t], dev, &(*sz)[t], false, &(*gp)[t]);
+    if (b) {
+      if (b == kBadTensor) type_error(bad_tensor);
+      else value_error("local and global tensors must have matching sizes");
+      return false;
+    }
+    *n += (*sz)[t];
+  }
+  return true;
+}
+
+// The C calls of an entry: `call(stream)` — returning the flc_* status — with the GIL released and device `dev`
+// current (the current device is put back after it), on the current stream of `dev`; that status.
+template <class F>
+inline int run_on(int dev, F&& call) {
+  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
+  int rc = FLC_OK;
+  Py_BEGIN_ALLOW_THREADS
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  if (cur != dev) (void)hipSetDevice(dev);
+  rc = call(st);
+  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
+  Py_END_ALLOW_THREADS
+  return rc;
+}
+// RuntimeError "<what> failed with status <rc>: <flc_last_error()>" for the C function `what`
+PyObject* failed(const char* what, int rc) {
+  PyErr_Format(PyExc_RuntimeError, "%s failed with status %d: %s", what, rc, flc_last_error());
+  return nullptr;
+}
+// run_on for an entry that calls the one C function `what`: false with that RuntimeError set on a bad status
+template <class F>
+inline bool on_device(int dev, const char* what, F&& call) {
+  const int rc = run_on(dev, call);
+  if (rc != FLC_OK) failed(what, rc);
+  return rc == FLC_OK;
+}
+
+// A new flat fp32 tensor of max(n, 1) elements on device `dev`; false with RuntimeError set.
+bool new_flat(int64_t n, int dev, at::Tensor* flat) {
+  try {
+    *flat = at::empty({n > 0 ? n : 1}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, dev));
+  } catch (const std::exception& e) {
+    PyErr_SetString(PyExc_RuntimeError, e.what());
+    return false;
+  }
+  return true;
+}
+
+// The gradient buffer of a model: one new flat tensor holding the parameters' sz[t] elements back to back, gv[t] its
+// view shaped like parameter pt[t], gp[t] that view's pointer; false with RuntimeError set.
+bool gradient_views(const std::vector<const at::Tensor*>& pt, const std::vector<int64_t>& sz, int dev, at::Tensor* flat,
+                    std::vector<at::Tensor>* gv, float** gp) {
+  int64_t total = 0;
+  for (int64_t s : sz) total += s;
+  if (!new_flat(total, dev, flat)) return false;
+  gv->reserve(pt.size());
+  int64_t off = 0;
+  for (size_t t = 0; t < pt.size(); ++t) {
+    gv->push_back(flat->narrow(0, off, sz[t]).view(pt[t]->sizes()));
+    gp[t] = flat->data_ptr<float>() + off;
+    off += sz[t];
+  }
+  return true;
+}
+// (list of the views, flat buffer) as the entry's result; with `set_grad` each parameter's `.grad` is set to its view
+// (update_gradients' `mp.grad = ...`: same device, dtype, sizes)
+PyObject* views_result(const std::vector<const at::Tensor*>& pt, const std::vector<at::Tensor>& gv,
+                       const at::Tensor& flat, bool set_grad) {
+  PyObject* lst = PyList_New((Py_ssize_t)gv.size());
+  if (!lst) return nullptr;
+  for (size_t t = 0; t < gv.size(); ++t) {
+    if (set_grad) pt[t]->mutable_grad() = gv[t];
+    PyObject* w = THPVariable_Wrap(gv[t]);
+    if (!w) {
+      Py_DECREF(lst);
+      return nullptr;
+    }
+    PyList_SET_ITEM(lst, (Py_ssize_t)t, w);
+  }
+  PyObject* fl = THPVariable_Wrap(flat);
+  if (!fl) {
+    Py_DECREF(lst);
+    return nullptr;
+  }
+  return Py_BuildValue("(NN)", lst, fl);
+}
+
+// ------------------------------------------------------------------------------------------------ the entry points
 // model_fold(dsts, msgs, key, weights, init_mode, beta, theta, v, opt, lr, beta2, tau)
 //   dsts: sequence of model tensors (accumulators); msgs: sequence of messages, each a sequence of tensors or (key
-//   not None) a mapping holding one under `key`; weights: one float per message; theta / v: sequences or None
+//   not None) a mapping holding one under `key`; weights: one float per message; theta / v: sequences or None.
+//   More than 16 messages are folded in chained launches (init mode 2 after the first launch, the optimizer step fused
+//   into the last one — the same fmaf chain as one launch).  Errors: TypeError for a tensor the fold does not take (the
+//   caller then moves messages or folds per tensor), ValueError for mismatched sizes or counts.
 PyObject* model_fold(PyObject*, PyObject* args) {
   PyObject *dsts, *msgs, *key, *weights, *theta, *v;
   int init_mode, opt;
@@ -63,102 +304,45 @@ PyObject* model_fold(PyObject*, PyObject* args) {
   if (!PyArg_ParseTuple(args, "OOOOidOOiddd", &dsts, &msgs, &key, &weights, &init_mode, &beta, &theta, &v, &opt, &lr,
                         &beta2, &tau))
     return nullptr;
-  PyObject* fd = PySequence_Fast(dsts, "dsts must be a sequence of tensors");
+  Refs refs;
+  PyObject* fd = refs.fast(dsts, "dsts must be a sequence of tensors");
   if (!fd) return nullptr;
-  PyObject* fm = PySequence_Fast(msgs, "messages must be a sequence");
-  if (!fm) {
-    Py_DECREF(fd);
-    return nullptr;
-  }
-  PyObject* fw = PySequence_Fast(weights, "weights must be a sequence of floats");
-  if (!fw) {
-    Py_DECREF(fd);
-    Py_DECREF(fm);
-    return nullptr;
-  }
-  std::vector<PyObject*> keep = {fd, fm, fw};
-  auto done = [&](PyObject* r) {
-    for (PyObject* o : keep) Py_XDECREF(o);
-    return r;
-  };
-  const Py_ssize_t nt = PySequence_Fast_GET_SIZE(fd), ns = PySequence_Fast_GET_SIZE(fm);
-  if (PySequence_Fast_GET_SIZE(fw) != ns) return done(value_error("one weight per message"));
-  if (nt == 0) return done((Py_INCREF(Py_None), Py_None));
+  PyObject* fm = refs.fast(msgs, "messages must be a sequence");
+  if (!fm) return nullptr;
+  PyObject* fw = refs.fast(weights, "weights must be a sequence of floats");
+  if (!fw) return nullptr;
+  const Py_ssize_t nt = len(fd), ns = len(fm);
+  if (len(fw) != ns) return value_error("one weight per message");
+  if (nt == 0) Py_RETURN_NONE;
   int dev = -1;
   std::vector<float*> dp(nt), tp, vp;
   std::vector<int64_t> sz(nt);
-  PyObject** di = PySequence_Fast_ITEMS(fd);
-  for (Py_ssize_t t = 0; t < nt; ++t) {
-    const at::Tensor* a = usable(di[t], &dev);
-    if (!a) return done(type_error("model tensors must be contiguous fp32 HIP tensors on one device"));
-    dp[t] = a->data_ptr<float>();
-    sz[t] = a->numel();
-  }
-  for (int which = 0; which < 2; ++which) {  // theta, v
-    PyObject* src = which == 0 ? theta : v;
-    if (src == Py_None) continue;
-    PyObject* f = PySequence_Fast(src, "theta / v must be sequences of tensors");
-    if (!f) return done(nullptr);
-    keep.push_back(f);
-    if (PySequence_Fast_GET_SIZE(f) != nt) return done(value_error("theta / v need one tensor per model tensor"));
-    std::vector<float*>& out = which == 0 ? tp : vp;
-    out.resize(nt);
-    PyObject** it = PySequence_Fast_ITEMS(f);
-    for (Py_ssize_t t = 0; t < nt; ++t) {
-      const at::Tensor* a = usable(it[t], &dev);
-      if (!a) return done(type_error("theta / v tensors must be contiguous fp32 HIP tensors on the model's device"));
-      if (a->numel() != sz[t]) return done(value_error("theta / v must match the model tensors' sizes"));
-      out[t] = a->data_ptr<float>();
-    }
-  }
+  if (tensor_row(items(fd), nt, &dev, sz.data(), true, dp.data()))
+    return type_error("model tensors must be contiguous fp32 HIP tensors on one device");
+  if (!optimizer_rows(refs, theta, v, nt, &dev, sz.data(), false, &tp, &vp)) return nullptr;
   std::vector<const float*> sp((size_t)ns * nt);
   std::vector<float> w(ns);
-  PyObject** mi = PySequence_Fast_ITEMS(fm);
-  PyObject** wi = PySequence_Fast_ITEMS(fw);
   for (Py_ssize_t m = 0; m < ns; ++m) {
-    const double wd = PyFloat_AsDouble(wi[m]);
-    if (wd == -1.0 && PyErr_Occurred()) return done(nullptr);
-    w[m] = (float)wd;  // (rounded to fp32 at the boundary, as torch's add_(alpha=...) does)
-    PyObject* msg = mi[m];
-    if (key != Py_None) {
-      msg = PyObject_GetItem(msg, key);  // (new reference)
-      if (!msg) return done(nullptr);
-      keep.push_back(msg);
-    }
-    PyObject* f = PySequence_Fast(msg, "a message is a sequence of tensors");
-    if (!f) return done(nullptr);
-    keep.push_back(f);
-    if (PySequence_Fast_GET_SIZE(f) != nt) return done(value_error("every message has one tensor per model tensor"));
-    PyObject** it = PySequence_Fast_ITEMS(f);
-    for (Py_ssize_t t = 0; t < nt; ++t) {
-      const at::Tensor* a = usable(it[t], &dev);
-      if (!a) return done(type_error("message tensors must be contiguous fp32 HIP tensors on the model's device"));
-      if (a->numel() != sz[t]) return done(value_error("message tensors must match the model tensors' sizes"));
-      sp[(size_t)m * nt + t] = a->data_ptr<float>();
-    }
+    if (!as_f32(items(fw)[m], &w[m])) return nullptr;
+    if (Bad b = message_row(refs, items(fm)[m], key == Py_None ? nullptr : key, "a message is a sequence of tensors", nt,
+                            &dev, sz.data(), &sp[(size_t)m * nt]))
+      return message_error(b, false);
   }
-  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
-  int rc = FLC_OK;
-  Py_BEGIN_ALLOW_THREADS
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  if (cur != dev) (void)hipSetDevice(dev);
-  Py_ssize_t m0 = 0;
-  do {  // chained launches of <= 16 messages: the optimizer step with the last one only
-    const Py_ssize_t cnt = ns - m0 < kMaxSrc ? ns - m0 : kMaxSrc;
-    const bool last = m0 + cnt >= ns;
-    rc = flc_model_fold(dp.data(), sp.data() + (size_t)m0 * nt, w.data() + m0, (int)cnt, sz.data(), (int)nt,
-                        m0 == 0 ? init_mode : 2, (float)beta, last && !tp.empty() ? tp.data() : nullptr,
-                        last && !vp.empty() ? vp.data() : nullptr, last ? opt : FLC_OPT_AVG, lr, beta2, tau, st);
-    m0 += cnt;
-  } while (rc == FLC_OK && m0 < ns);
-  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
-  Py_END_ALLOW_THREADS
-  if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "flc_model_fold failed with status %d: %s", rc, flc_last_error());
-    return done(nullptr);
-  }
-  return done((Py_INCREF(Py_None), Py_None));
+  if (!on_device(dev, "flc_model_fold", [&](void* st) {
+        int rc = FLC_OK;
+        Py_ssize_t m0 = 0;
+        do {  // chained launches of <= 16 messages: the optimizer step with the last one only
+          const Py_ssize_t cnt = ns - m0 < kMaxSrc ? ns - m0 : kMaxSrc;
+          const bool last = m0 + cnt >= ns;
+          rc = flc_model_fold(dp.data(), sp.data() + (size_t)m0 * nt, w.data() + m0, (int)cnt, sz.data(), (int)nt,
+                              m0 == 0 ? init_mode : 2, (float)beta, last && !tp.empty() ? tp.data() : nullptr,
+                              last && !vp.empty() ? vp.data() : nullptr, last ? opt : FLC_OPT_AVG, lr, beta2, tau, st);
+          m0 += cnt;
+        } while (rc == FLC_OK && m0 < ns);
+        return rc;
+      }))
+    return nullptr;
+  Py_RETURN_NONE;
 }
 
 // server_fold(theta, aux, msgs, key, weights, kind, fold, init_mode, inertia, c): flc_model_fold_server (FedDyn's h
@@ -171,84 +355,44 @@ PyObject* server_fold(PyObject*, PyObject* args) {
   if (!PyArg_ParseTuple(args, "OOOOOiiidd", &theta, &aux, &msgs, &key, &weights, &kind, &fold, &init_mode, &inertia,
                         &c))
     return nullptr;
-  std::vector<PyObject*> keep;
-  auto done = [&](PyObject* r) {
-    for (PyObject* o : keep) Py_XDECREF(o);
-    return r;
-  };
-  PyObject* ft = PySequence_Fast(theta, "theta must be a sequence of tensors");
+  Refs refs;
+  PyObject* ft = refs.fast(theta, "theta must be a sequence of tensors");
   if (!ft) return nullptr;
-  keep.push_back(ft);
-  PyObject* fa = PySequence_Fast(aux, "aux must be a sequence of tensors");
-  if (!fa) return done(nullptr);
-  keep.push_back(fa);
-  PyObject* fm = PySequence_Fast(msgs, "messages must be a sequence");
-  if (!fm) return done(nullptr);
-  keep.push_back(fm);
-  PyObject* fw = PySequence_Fast(weights, "weights must be a sequence of floats");
-  if (!fw) return done(nullptr);
-  keep.push_back(fw);
-  const Py_ssize_t nt = PySequence_Fast_GET_SIZE(ft), ns = PySequence_Fast_GET_SIZE(fm);
-  if (PySequence_Fast_GET_SIZE(fw) != ns) return done(value_error("one weight per message"));
-  if (PySequence_Fast_GET_SIZE(fa) != nt) return done(value_error("one aux tensor per model tensor"));
-  if (ns > kMaxSrc) return done(value_error("server_fold takes at most 16 messages"));
-  if (nt == 0) return done((Py_INCREF(Py_None), Py_None));
+  PyObject* fa = refs.fast(aux, "aux must be a sequence of tensors");
+  if (!fa) return nullptr;
+  PyObject* fm = refs.fast(msgs, "messages must be a sequence");
+  if (!fm) return nullptr;
+  PyObject* fw = refs.fast(weights, "weights must be a sequence of floats");
+  if (!fw) return nullptr;
+  const Py_ssize_t nt = len(ft), ns = len(fm);
+  if (len(fw) != ns) return value_error("one weight per message");
+  if (len(fa) != nt) return value_error("one aux tensor per model tensor");
+  if (ns > kMaxSrc) return value_error("server_fold takes at most 16 messages");
+  if (nt == 0) Py_RETURN_NONE;
   int dev = -1;
   std::vector<float*> tp(nt), ap(nt);
   std::vector<int64_t> sz(nt);
-  PyObject** ti = PySequence_Fast_ITEMS(ft);
-  PyObject** ai = PySequence_Fast_ITEMS(fa);
-  for (Py_ssize_t t = 0; t < nt; ++t) {
-    const at::Tensor* a = usable(ti[t], &dev);
-    if (!a) return done(type_error("model tensors must be contiguous fp32 HIP tensors on one device"));
-    tp[t] = a->data_ptr<float>();
-    sz[t] = a->numel();
-    const at::Tensor* b = usable(ai[t], &dev);
-    if (!b) return done(type_error("aux tensors must be contiguous fp32 HIP tensors on the model's device"));
-    if (b->numel() != sz[t]) return done(value_error("aux tensors must match the model tensors' sizes"));
-    ap[t] = b->data_ptr<float>();
+  for (Py_ssize_t t = 0; t < nt; ++t) {  // (theta and aux side by side: the first finding in that order)
+    if (take(items(ft)[t], &dev, &sz[t], true, &tp[t]))
+      return type_error("model tensors must be contiguous fp32 HIP tensors on one device");
+    if (Bad b = take(items(fa)[t], &dev, &sz[t], false, &ap[t]))
+      return b == kBadTensor ? type_error("aux tensors must be contiguous fp32 HIP tensors on the model's device")
+                             : value_error("aux tensors must match the model tensors' sizes");
   }
   std::vector<const float*> sp((size_t)(ns > 0 ? ns : 1) * nt);
   std::vector<float> w(ns > 0 ? ns : 1);
-  PyObject** mi = PySequence_Fast_ITEMS(fm);
-  PyObject** wi = PySequence_Fast_ITEMS(fw);
   for (Py_ssize_t m = 0; m < ns; ++m) {
-    const double wd = PyFloat_AsDouble(wi[m]);
-    if (wd == -1.0 && PyErr_Occurred()) return done(nullptr);
-    w[m] = (float)wd;
-    PyObject* msg = mi[m];
-    if (key != Py_None) {
-      msg = PyObject_GetItem(msg, key);
-      if (!msg) return done(nullptr);
-      keep.push_back(msg);
-    }
-    PyObject* f = PySequence_Fast(msg, "a message is a sequence of tensors");
-    if (!f) return done(nullptr);
-    keep.push_back(f);
-    if (PySequence_Fast_GET_SIZE(f) != nt) return done(value_error("every message has one tensor per model tensor"));
-    PyObject** it = PySequence_Fast_ITEMS(f);
-    for (Py_ssize_t t = 0; t < nt; ++t) {
-      const at::Tensor* a = usable(it[t], &dev);
-      if (!a) return done(type_error("message tensors must be contiguous fp32 HIP tensors on the model's device"));
-      if (a->numel() != sz[t]) return done(value_error("message tensors must match the model tensors' sizes"));
-      sp[(size_t)m * nt + t] = a->data_ptr<float>();
-    }
+    if (!as_f32(items(fw)[m], &w[m])) return nullptr;
+    if (Bad b = message_row(refs, items(fm)[m], key == Py_None ? nullptr : key, "a message is a sequence of tensors", nt,
+                            &dev, sz.data(), &sp[(size_t)m * nt]))
+      return message_error(b, false);
   }
-  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
-  int rc = FLC_OK;
-  Py_BEGIN_ALLOW_THREADS
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  if (cur != dev) (void)hipSetDevice(dev);
-  rc = flc_model_fold_server(tp.data(), ap.data(), sp.data(), w.data(), (int)ns, sz.data(), (int)nt, kind, fold,
-                             init_mode, (float)inertia, c, st);
-  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
-  Py_END_ALLOW_THREADS
-  if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "flc_model_fold_server failed with status %d: %s", rc, flc_last_error());
-    return done(nullptr);
-  }
-  return done((Py_INCREF(Py_None), Py_None));
+  if (!on_device(dev, "flc_model_fold_server", [&](void* st) {
+        return flc_model_fold_server(tp.data(), ap.data(), sp.data(), w.data(), (int)ns, sz.data(), (int)nt, kind, fold,
+                                     init_mode, (float)inertia, c, st);
+      }))
+    return nullptr;
+  Py_RETURN_NONE;
 }
 
 // avg_and_gradients(params, grads, msgs, w_params, w_grads, inertia[, set_grad]): flc_avg_and_gradients
@@ -264,135 +408,50 @@ PyObject* avg_and_gradients(PyObject*, PyObject* args) {
   double inertia;
   int set_grad = 0;
   if (!PyArg_ParseTuple(args, "OOOOOd|p", &params, &grads, &msgs, &wpar, &wgrd, &inertia, &set_grad)) return nullptr;
-  std::vector<PyObject*> keep;
-  auto done = [&](PyObject* r) {
-    for (PyObject* o : keep) Py_XDECREF(o);
-    return r;
-  };
+  Refs refs;
   const bool alloc = grads == Py_None;
   PyObject* seqs[5] = {params, alloc ? params : grads, msgs, wpar, wgrd};
   PyObject* f[5];
-  for (int i = 0; i < 5; ++i) {
-    f[i] = PySequence_Fast(seqs[i], "avg_and_gradients takes sequences");
-    if (!f[i]) return done(nullptr);
-    keep.push_back(f[i]);
-  }
-  const Py_ssize_t nt = PySequence_Fast_GET_SIZE(f[0]), ns = PySequence_Fast_GET_SIZE(f[2]);
-  if (PySequence_Fast_GET_SIZE(f[1]) != nt) return done(value_error("one gradient buffer per parameter"));
-  if (PySequence_Fast_GET_SIZE(f[3]) != ns || PySequence_Fast_GET_SIZE(f[4]) != ns)
-    return done(value_error("one weight of each kind per message"));
-  if (ns == 0) return done(value_error("avg_and_gradients needs at least one message"));
-  if (nt == 0) return done((Py_INCREF(Py_None), Py_None));
+  for (int i = 0; i < 5; ++i)
+    if (!(f[i] = refs.fast(seqs[i], "avg_and_gradients takes sequences"))) return nullptr;
+  const Py_ssize_t nt = len(f[0]), ns = len(f[2]);
+  if (len(f[1]) != nt) return value_error("one gradient buffer per parameter");
+  if (len(f[3]) != ns || len(f[4]) != ns) return value_error("one weight of each kind per message");
+  if (ns == 0) return value_error("avg_and_gradients needs at least one message");
+  if (nt == 0) Py_RETURN_NONE;
   int dev = -1;
   std::vector<float*> pp(nt), gp(nt);
   std::vector<int64_t> sz(nt);
   std::vector<const at::Tensor*> pt(nt);
-  PyObject** pi = PySequence_Fast_ITEMS(f[0]);
-  PyObject** gi = PySequence_Fast_ITEMS(f[1]);
-  for (Py_ssize_t t = 0; t < nt; ++t) {
-    const at::Tensor* a = usable(pi[t], &dev);
-    if (!a) return done(type_error("model tensors must be contiguous fp32 HIP tensors on one device"));
-    pt[t] = a;
-    pp[t] = a->data_ptr<float>();
-    sz[t] = a->numel();
+  for (Py_ssize_t t = 0; t < nt; ++t) {  // (a parameter and its buffer side by side)
+    if (take(items(f[0])[t], &dev, &sz[t], true, &pp[t], &pt[t]))
+      return type_error("model tensors must be contiguous fp32 HIP tensors on one device");
     if (alloc) continue;
-    const at::Tensor* b = usable(gi[t], &dev);
-    if (!b) return done(type_error("gradient buffers must be contiguous fp32 HIP tensors on the model's device"));
-    if (b->numel() != sz[t]) return done(value_error("gradient buffers must match the model tensors' sizes"));
-    gp[t] = b->data_ptr<float>();
+    if (Bad b = take(items(f[1])[t], &dev, &sz[t], false, &gp[t]))
+      return b == kBadTensor ? type_error("gradient buffers must be contiguous fp32 HIP tensors on the model's device")
+                             : value_error("gradient buffers must match the model tensors' sizes");
   }
   std::vector<const float*> ps((size_t)ns * nt), gs((size_t)ns * nt);
   std::vector<float> wp(ns), wg(ns);
-  PyObject** mi = PySequence_Fast_ITEMS(f[2]);
-  PyObject** wpi = PySequence_Fast_ITEMS(f[3]);
-  PyObject** wgi = PySequence_Fast_ITEMS(f[4]);
   static PyObject* const keys[2] = {PyUnicode_InternFromString("parameters"), PyUnicode_InternFromString("gradients")};
   for (Py_ssize_t m = 0; m < ns; ++m) {
-    const double a = PyFloat_AsDouble(wpi[m]), b = PyFloat_AsDouble(wgi[m]);
-    if (PyErr_Occurred()) return done(nullptr);
-    wp[m] = (float)a;
-    wg[m] = (float)b;
-    for (int k = 0; k < 2; ++k) {
-      PyObject* v = PyObject_GetItem(mi[m], keys[k]);
-      if (!v) return done(nullptr);
-      keep.push_back(v);
-      PyObject* fv = PySequence_Fast(v, "a message's parameters / gradients are sequences of tensors");
-      if (!fv) return done(nullptr);
-      keep.push_back(fv);
-      if (PySequence_Fast_GET_SIZE(fv) != nt) return done(value_error("every message has one tensor per model tensor"));
-      PyObject** it = PySequence_Fast_ITEMS(fv);
-      std::vector<const float*>& out = k == 0 ? ps : gs;
-      for (Py_ssize_t t = 0; t < nt; ++t) {
-        const at::Tensor* s = usable(it[t], &dev);
-        if (!s) return done(type_error("message tensors must be contiguous fp32 HIP tensors on the model's device"));
-        if (s->numel() != sz[t]) return done(value_error("message tensors must match the model tensors' sizes"));
-        out[(size_t)m * nt + t] = s->data_ptr<float>();
-      }
-    }
+    if (!as_f32(items(f[3])[m], &wp[m]) || !as_f32(items(f[4])[m], &wg[m])) return nullptr;
+    for (int k = 0; k < 2; ++k)
+      if (Bad b = message_row(refs, items(f[2])[m], keys[k], "a message's parameters / gradients are sequences of tensors",
+                              nt, &dev, sz.data(), &(k == 0 ? ps : gs)[(size_t)m * nt]))
+        return message_error(b, false);
   }
   // (every tensor checked: the gradient buffer, when asked for, is allocated now)
   at::Tensor flat;
   std::vector<at::Tensor> gv;
-  if (alloc) {
-    int64_t total = 0;
-    for (Py_ssize_t t = 0; t < nt; ++t) total += sz[t];
-    try {
-      flat = at::empty({total > 0 ? total : 1}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, dev));
-    } catch (const std::exception& e) {
-      PyErr_SetString(PyExc_RuntimeError, e.what());
-      return done(nullptr);
-    }
-    gv.reserve(nt);
-    int64_t off = 0;
-    for (Py_ssize_t t = 0; t < nt; ++t) {
-      gv.push_back(flat.narrow(0, off, sz[t]).view(pt[t]->sizes()));
-      gp[t] = flat.data_ptr<float>() + off;
-      off += sz[t];
-    }
-  }
-  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
-  int rc = FLC_OK;
-  Py_BEGIN_ALLOW_THREADS
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  if (cur != dev) (void)hipSetDevice(dev);
-  rc = flc_avg_and_gradients(pp.data(), gp.data(), ps.data(), gs.data(), wp.data(), wg.data(), (int)ns, sz.data(),
-                             (int)nt, (float)inertia, st);
-  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
-  Py_END_ALLOW_THREADS
-  if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "flc_avg_and_gradients failed with status %d: %s", rc, flc_last_error());
-    return done(nullptr);
-  }
-  if (!alloc) return done((Py_INCREF(Py_None), Py_None));
-  PyObject* lst = PyList_New(nt);
-  if (!lst) return done(nullptr);
-  for (Py_ssize_t t = 0; t < nt; ++t) {
-    if (set_grad) pt[t]->mutable_grad() = gv[t];  // (update_gradients' `mp.grad = ...`: same device, dtype, sizes)
-    PyObject* w = THPVariable_Wrap(gv[t]);
-    if (!w) {
-      Py_DECREF(lst);
-      return done(nullptr);
-    }
-    PyList_SET_ITEM(lst, t, w);
-  }
-  PyObject* fl = THPVariable_Wrap(flat);
-  if (!fl) {
-    Py_DECREF(lst);
-    return done(nullptr);
-  }
-  return done(Py_BuildValue("(NN)", lst, fl));
-}
-
-// a contiguous HIP tensor of `dt` on device `dev` (-1: any, returned); nullptr if not one
-const at::Tensor* usable_as(PyObject* o, at::ScalarType dt, int* dev) {
-  if (!THPVariable_Check(o)) return nullptr;
-  const at::Tensor& t = THPVariable_Unpack(o);
-  if (!t.is_cuda() || t.scalar_type() != dt || !t.is_contiguous()) return nullptr;
-  const int d = t.get_device();
-  if (*dev < 0) *dev = d;
-  else if (d != *dev) return nullptr;
-  return &t;
+  if (alloc && !gradient_views(pt, sz, dev, &flat, &gv, gp.data())) return nullptr;
+  if (!on_device(dev, "flc_avg_and_gradients", [&](void* st) {
+        return flc_avg_and_gradients(pp.data(), gp.data(), ps.data(), gs.data(), wp.data(), wg.data(), (int)ns, sz.data(),
+                                     (int)nt, (float)inertia, st);
+      }))
+    return nullptr;
+  if (!alloc) Py_RETURN_NONE;
+  return views_result(pt, gv, flat, set_grad != 0);
 }
 
 // stacked_delta_record(local, global, k, levels, seed, counter, record, count, ws): FedOptClient.communicate's delta
@@ -409,72 +468,44 @@ PyObject* stacked_delta_record(PyObject*, PyObject* args) {
   unsigned long long seed, counter;
   if (!PyArg_ParseTuple(args, "OOLiKKOOO", &loc, &glo, &k, &levels, &seed, &counter, &record, &count, &wso))
     return nullptr;
-  std::vector<PyObject*> keep;
-  auto done = [&](PyObject* r) {
-    for (PyObject* o : keep) Py_XDECREF(o);
-    return r;
-  };
-  PyObject* fl = PySequence_Fast(loc, "local must be a sequence of tensors");
-  if (!fl) return nullptr;
-  keep.push_back(fl);
-  PyObject* fg = PySequence_Fast(glo, "global must be a sequence of tensors");
-  if (!fg) return done(nullptr);
-  keep.push_back(fg);
-  const Py_ssize_t m = PySequence_Fast_GET_SIZE(fl);
-  if (m < 1 || PySequence_Fast_GET_SIZE(fg) != m) return done(value_error("one global tensor per local tensor, at least one"));
+  Refs refs;
   int dev = -1;
-  std::vector<const float*> lp(m), gp(m);
-  std::vector<int64_t> sz(m);
-  PyObject** li = PySequence_Fast_ITEMS(fl);
-  PyObject** gi = PySequence_Fast_ITEMS(fg);
+  std::vector<const float*> lp, gp;
+  std::vector<int64_t> sz;
   int64_t n = 0;
-  for (Py_ssize_t t = 0; t < m; ++t) {
-    const at::Tensor* a = usable(li[t], &dev);
-    const at::Tensor* b = usable(gi[t], &dev);
-    if (!a || !b) return done(type_error("local / global tensors must be contiguous fp32 HIP tensors on one device"));
-    if (a->numel() != b->numel()) return done(value_error("local and global tensors must have matching sizes"));
-    lp[t] = a->data_ptr<float>();
-    gp[t] = b->data_ptr<float>();
-    sz[t] = a->numel();
-    n += sz[t];
-  }
+  if (!delta_tables(refs, loc, glo, "global must be a sequence of tensors",
+                    "local / global tensors must be contiguous fp32 HIP tensors on one device", &dev, &lp, &gp, &sz, &n))
+    return nullptr;
+  const int m = (int)sz.size();
   const at::Tensor* rec = usable_as(record, at::kByte, &dev);
-  if (!rec) return done(type_error("the record must be a contiguous uint8 HIP tensor on the tensors' device"));
+  if (!rec) return type_error("the record must be a contiguous uint8 HIP tensor on the tensors' device");
   int64_t off[4] = {0, 0, 0, 0};  // norm, idx, codes, tiles
   const size_t stride = flc_stacked_wire_layout(n, k, off);
   uint8_t* rp = rec->data_ptr<uint8_t>();
   if (stride == 0 || (size_t)rec->numel() < stride || reinterpret_cast<uintptr_t>(rp) % 16 != 0)
-    return done(value_error("the record is smaller than the wire layout or not 16-B aligned"));
+    return value_error("the record is smaller than the wire layout or not 16-B aligned");
   int64_t* cp = nullptr;
   if (count != Py_None) {
     const at::Tensor* c = usable_as(count, at::kLong, &dev);
-    if (!c || c->numel() < 1) return done(type_error("count must be an int64 HIP tensor on the tensors' device"));
+    if (!c || c->numel() < 1) return type_error("count must be an int64 HIP tensor on the tensors' device");
     cp = c->data_ptr<int64_t>();
   }
   const at::Tensor* ws = usable_as(wso, at::kByte, &dev);
-  if (!ws) return done(type_error("ws must be a contiguous uint8 HIP tensor on the tensors' device"));
-  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
+  if (!ws) return type_error("ws must be a contiguous uint8 HIP tensor on the tensors' device");
   int32_t* idx = reinterpret_cast<int32_t*>(rp + off[1]);
-  int rc = FLC_OK;
-  const char* what = "flc_stacked_encode_delta";
-  Py_BEGIN_ALLOW_THREADS
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  if (cur != dev) (void)hipSetDevice(dev);
-  rc = flc_stacked_encode_delta(lp.data(), gp.data(), sz.data(), (int)m, k, levels, seed, counter, idx, rp + off[2],
-                                reinterpret_cast<float*>(rp + off[0]), reinterpret_cast<uint32_t*>(rp + off[3]),
-                                ws->data_ptr(), (size_t)ws->numel(), st);
-  if (rc == FLC_OK && cp) {
-    what = "flc_delta_count_nonzero_at";
-    rc = flc_delta_count_nonzero_at(lp.data(), gp.data(), sz.data(), (int)m, idx, k, cp, st);
-  }
-  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
-  Py_END_ALLOW_THREADS
-  if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "%s failed with status %d: %s", what, rc, flc_last_error());
-    return done(nullptr);
-  }
-  return done((Py_INCREF(Py_None), Py_None));
+  const char* what = "flc_stacked_encode_delta";  // (two calls: the one that failed is named)
+  const int rc = run_on(dev, [&](void* st) {
+    int r = flc_stacked_encode_delta(lp.data(), gp.data(), sz.data(), m, k, levels, seed, counter, idx, rp + off[2],
+                                     reinterpret_cast<float*>(rp + off[0]), reinterpret_cast<uint32_t*>(rp + off[3]),
+                                     ws->data_ptr(), (size_t)ws->numel(), st);
+    if (r == FLC_OK && cp) {
+      what = "flc_delta_count_nonzero_at";
+      r = flc_delta_count_nonzero_at(lp.data(), gp.data(), sz.data(), m, idx, k, cp, st);
+    }
+    return r;
+  });
+  if (rc != FLC_OK) return failed(what, rc);
+  Py_RETURN_NONE;
 }
 
 // delta_flat(local, global): a new flat fp32 tensor = cat(local_t - global_t) (flc_delta_flatten) on the tensors'
@@ -483,58 +514,23 @@ PyObject* stacked_delta_record(PyObject*, PyObject* args) {
 PyObject* delta_flat(PyObject*, PyObject* args) {
   PyObject *loc, *glo;
   if (!PyArg_ParseTuple(args, "OO", &loc, &glo)) return nullptr;
-  std::vector<PyObject*> keep;
-  auto done = [&](PyObject* r) {
-    for (PyObject* o : keep) Py_XDECREF(o);
-    return r;
-  };
-  PyObject* fl = PySequence_Fast(loc, "local must be a sequence of tensors");
-  if (!fl) return nullptr;
-  keep.push_back(fl);
-  PyObject* fg = PySequence_Fast(glo, "global must be a sequence of tensors");
-  if (!fg) return done(nullptr);
-  keep.push_back(fg);
-  const Py_ssize_t m = PySequence_Fast_GET_SIZE(fl);
-  if (m < 1 || PySequence_Fast_GET_SIZE(fg) != m) return done(value_error("one global tensor per local tensor, at least one"));
+  Refs refs;
   int dev = -1;
-  std::vector<const float*> lp(m), gp(m);
-  std::vector<int64_t> sz(m);
-  PyObject** li = PySequence_Fast_ITEMS(fl);
-  PyObject** gi = PySequence_Fast_ITEMS(fg);
+  std::vector<const float*> lp, gp;
+  std::vector<int64_t> sz;
   int64_t n = 0;
-  for (Py_ssize_t t = 0; t < m; ++t) {
-    const at::Tensor* a = usable(li[t], &dev);
-    const at::Tensor* b = usable(gi[t], &dev);
-    if (!a || !b) return done(type_error("local / global tensors must be contiguous fp32 HIP tensors on one device"));
-    if (a->numel() != b->numel()) return done(value_error("local and global tensors must have matching sizes"));
-    lp[t] = a->data_ptr<float>();
-    gp[t] = b->data_ptr<float>();
-    sz[t] = a->numel();
-    n += sz[t];
-  }
+  if (!delta_tables(refs, loc, glo, "global must be a sequence of tensors",
+                    "local / global tensors must be contiguous fp32 HIP tensors on one device", &dev, &lp, &gp, &sz, &n))
+    return nullptr;
   at::Tensor out;
-  try {
-    out = at::empty({n > 0 ? n : 1}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, dev));
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
-    return done(nullptr);
-  }
+  if (!new_flat(n, dev, &out)) return nullptr;
   if (n == 0) out = out.narrow(0, 0, 0);
-  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
-  int rc = FLC_OK;
   float* op = out.data_ptr<float>();
-  Py_BEGIN_ALLOW_THREADS
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  if (cur != dev) (void)hipSetDevice(dev);
-  rc = flc_delta_flatten(lp.data(), gp.data(), sz.data(), (int)m, op, st);
-  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
-  Py_END_ALLOW_THREADS
-  if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "flc_delta_flatten failed with status %d: %s", rc, flc_last_error());
-    return done(nullptr);
-  }
-  return done(THPVariable_Wrap(out));
+  if (!on_device(dev, "flc_delta_flatten", [&](void* st) {
+        return flc_delta_flatten(lp.data(), gp.data(), sz.data(), (int)sz.size(), op, st);
+      }))
+    return nullptr;
+  return THPVariable_Wrap(out);
 }
 
 // ef_accumulate(local, global_or_None, e): e += cat(local_t - global_t) in place (flc_ef_accumulate; None: e +=
@@ -544,176 +540,98 @@ PyObject* delta_flat(PyObject*, PyObject* args) {
 PyObject* ef_accumulate(PyObject*, PyObject* args) {
   PyObject *loc, *glo, *mem;
   if (!PyArg_ParseTuple(args, "OOO", &loc, &glo, &mem)) return nullptr;
-  std::vector<PyObject*> keep;
-  auto done = [&](PyObject* r) {
-    for (PyObject* o : keep) Py_XDECREF(o);
-    return r;
-  };
+  Refs refs;
   int dev = -1;
-  const at::Tensor* et = usable(mem, &dev);
+  const at::Tensor* et = usable_as(mem, at::kFloat, &dev);
   if (!et) return type_error("the memory must be a contiguous fp32 HIP tensor");
-  PyObject* fl = PySequence_Fast(loc, "local must be a sequence of tensors");
-  if (!fl) return nullptr;
-  keep.push_back(fl);
-  PyObject* fg = nullptr;
-  if (glo != Py_None) {
-    fg = PySequence_Fast(glo, "global must be a sequence of tensors or None");
-    if (!fg) return done(nullptr);
-    keep.push_back(fg);
-  }
-  const Py_ssize_t m = PySequence_Fast_GET_SIZE(fl);
-  if (m < 1 || (fg && PySequence_Fast_GET_SIZE(fg) != m))
-    return done(value_error("one global tensor per local tensor, at least one"));
-  std::vector<const float*> lp(m), gp(fg ? m : 0);
-  std::vector<int64_t> sz(m);
-  PyObject** li = PySequence_Fast_ITEMS(fl);
-  PyObject** gi = fg ? PySequence_Fast_ITEMS(fg) : nullptr;
+  const bool sub = glo != Py_None;
+  std::vector<const float*> lp, gp;
+  std::vector<int64_t> sz;
   int64_t n = 0;
-  for (Py_ssize_t t = 0; t < m; ++t) {
-    const at::Tensor* a = usable(li[t], &dev);
-    const at::Tensor* b = fg ? usable(gi[t], &dev) : nullptr;
-    if (!a || (fg && !b))
-      return done(type_error("local / global tensors must be contiguous fp32 HIP tensors on the memory's device"));
-    if (fg && a->numel() != b->numel()) return done(value_error("local and global tensors must have matching sizes"));
-    lp[t] = a->data_ptr<float>();
-    if (fg) gp[t] = b->data_ptr<float>();
-    sz[t] = a->numel();
-    n += sz[t];
-  }
-  if (et->numel() != n) return done(value_error("the memory must hold the tensors' element count"));
-  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
-  int rc = FLC_OK;
+  if (!delta_tables(refs, loc, sub ? glo : nullptr, "global must be a sequence of tensors or None",
+                    "local / global tensors must be contiguous fp32 HIP tensors on the memory's device", &dev, &lp, &gp,
+                    &sz, &n))
+    return nullptr;
+  if (et->numel() != n) return value_error("the memory must hold the tensors' element count");
   float* ep = et->data_ptr<float>();
-  Py_BEGIN_ALLOW_THREADS
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  if (cur != dev) (void)hipSetDevice(dev);
-  rc = flc_ef_accumulate(lp.data(), fg ? gp.data() : nullptr, sz.data(), (int)m, ep, st);
-  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
-  Py_END_ALLOW_THREADS
-  if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "flc_ef_accumulate failed with status %d: %s", rc, flc_last_error());
-    return done(nullptr);
-  }
-  return done((Py_INCREF(Py_None), Py_None));
+  if (!on_device(dev, "flc_ef_accumulate", [&](void* st) {
+        return flc_ef_accumulate(lp.data(), sub ? gp.data() : nullptr, sz.data(), (int)sz.size(), ep, st);
+      }))
+    return nullptr;
+  Py_RETURN_NONE;
 }
 
-// stacked_records_batch(flats, seeds, counter, k, levels, records, counts, ws): the deferred messages of a round in
-// one C call — flc_stacked_encode_batch of the flat deltas into rows of the [C, >= stride] record block (row c equals
-// client c's one-message record), then flc_count_nonzero_at_batch of each delta at its kept indices into counts[c].
-//
-// stacked_records_round(flats, seeds, counters, k, levels, records, counts, ws): the same with one Philox counter per
-// message (a sequence), in one C call and one encode launch chain — flc_stacked_encode_round, whose select writes
-// counts[c] itself (no count launches).
-PyObject* stacked_records(PyObject* args, const bool round) {
-  PyObject *flats, *seeds, *recs, *counts, *wso, *ctrs = nullptr;
-  unsigned long long counter = 0;
+// stacked_records_round(flats, seeds, counters, k, levels, records, counts, ws): the deferred messages of a round in
+// one C call and one encode launch chain — flc_stacked_encode_round of the flat deltas, one Philox (seed, counter) per
+// message, into the rows of the [C, >= stride] record block (row c equals client c's one-message record); its select
+// writes the send counts counts[c] itself (no count launches).
+PyObject* stacked_records_round(PyObject*, PyObject* args) {
+  PyObject *flats, *seeds, *recs, *counts, *wso, *ctrs;
   long long k;
   int levels;
-  if (round ? !PyArg_ParseTuple(args, "OOOLiOOO", &flats, &seeds, &ctrs, &k, &levels, &recs, &counts, &wso)
-            : !PyArg_ParseTuple(args, "OOKLiOOO", &flats, &seeds, &counter, &k, &levels, &recs, &counts, &wso))
-    return nullptr;
-  std::vector<PyObject*> keep;
-  auto done = [&](PyObject* r) {
-    for (PyObject* o : keep) Py_XDECREF(o);
-    return r;
-  };
+  if (!PyArg_ParseTuple(args, "OOOLiOOO", &flats, &seeds, &ctrs, &k, &levels, &recs, &counts, &wso)) return nullptr;
+  Refs refs;
   PyObject* seqs[3] = {flats, seeds, counts};
   PyObject* f[3];
-  for (int i = 0; i < 3; ++i) {
-    f[i] = PySequence_Fast(seqs[i], "stacked_records_batch takes sequences");
-    if (!f[i]) return done(nullptr);
-    keep.push_back(f[i]);
-  }
-  const Py_ssize_t C = PySequence_Fast_GET_SIZE(f[0]);
-  if (C < 1 || PySequence_Fast_GET_SIZE(f[1]) != C || PySequence_Fast_GET_SIZE(f[2]) != C)
-    return done(value_error("one seed and one count per client, at least one client"));
-  std::vector<uint64_t> ct64;
-  if (round) {
-    PyObject* fc = PySequence_Fast(ctrs, "stacked_records_round takes a sequence of counters");
-    if (!fc) return done(nullptr);
-    keep.push_back(fc);
-    if (PySequence_Fast_GET_SIZE(fc) != C) return done(value_error("one counter per client"));
-    ct64.resize(C);
-    for (Py_ssize_t c = 0; c < C; ++c) {
-      ct64[c] = (uint64_t)PyLong_AsUnsignedLongLongMask(PySequence_Fast_ITEMS(fc)[c]);
-      if (PyErr_Occurred()) return done(nullptr);
-    }
+  for (int i = 0; i < 3; ++i)
+    if (!(f[i] = refs.fast(seqs[i], "stacked_records_round takes sequences"))) return nullptr;
+  const Py_ssize_t C = len(f[0]);
+  if (C < 1 || len(f[1]) != C || len(f[2]) != C)
+    return value_error("one seed and one count per client, at least one client");
+  PyObject* fc = refs.fast(ctrs, "stacked_records_round takes a sequence of counters");
+  if (!fc) return nullptr;
+  if (len(fc) != C) return value_error("one counter per client");
+  std::vector<uint64_t> ct64(C);
+  for (Py_ssize_t c = 0; c < C; ++c) {
+    ct64[c] = (uint64_t)PyLong_AsUnsignedLongLongMask(items(fc)[c]);
+    if (PyErr_Occurred()) return nullptr;
   }
   int dev = -1;
   int64_t n = -1;
   std::vector<const float*> xp(C);
   std::vector<uint64_t> sd(C);
   std::vector<int64_t*> cp(C);
-  PyObject** xi = PySequence_Fast_ITEMS(f[0]);
-  PyObject** si = PySequence_Fast_ITEMS(f[1]);
-  PyObject** ci = PySequence_Fast_ITEMS(f[2]);
   for (Py_ssize_t c = 0; c < C; ++c) {
-    const at::Tensor* x = usable(xi[c], &dev);
-    if (!x) return done(type_error("flat deltas must be contiguous fp32 HIP tensors on one device"));
-    if (n < 0) n = x->numel();
-    if (x->numel() != n) return done(value_error("flat deltas must all have one size"));
-    xp[c] = x->data_ptr<float>();
-    sd[c] = (uint64_t)PyLong_AsUnsignedLongLongMask(si[c]);
-    if (PyErr_Occurred()) return done(nullptr);
-    const at::Tensor* ct = usable_as(ci[c], at::kLong, &dev);
-    if (!ct || ct->numel() < 1) return done(type_error("counts must be int64 HIP tensors on the deltas' device"));
+    if (Bad b = take(items(f[0])[c], &dev, &n, c == 0, &xp[c]))
+      return b == kBadTensor ? type_error("flat deltas must be contiguous fp32 HIP tensors on one device")
+                             : value_error("flat deltas must all have one size");
+    sd[c] = (uint64_t)PyLong_AsUnsignedLongLongMask(items(f[1])[c]);
+    if (PyErr_Occurred()) return nullptr;
+    const at::Tensor* ct = usable_as(items(f[2])[c], at::kLong, &dev);
+    if (!ct || ct->numel() < 1) return type_error("counts must be int64 HIP tensors on the deltas' device");
     cp[c] = ct->data_ptr<int64_t>();
   }
   int64_t off[4] = {0, 0, 0, 0};  // norm, idx, codes, tiles
   const size_t stride = flc_stacked_wire_layout(n, k, off);
-  if (stride == 0) return done(value_error("bad wire shape"));
-  if (!THPVariable_Check(recs)) return done(type_error("records must be a uint8 HIP tensor"));
+  if (stride == 0) return value_error("bad wire shape");
+  if (!THPVariable_Check(recs)) return type_error("records must be a uint8 HIP tensor");
   const at::Tensor& rb = THPVariable_Unpack(recs);
   if (!rb.is_cuda() || rb.get_device() != dev || rb.scalar_type() != at::kByte || rb.dim() != 2 || !rb.is_contiguous() ||
       rb.size(0) != C || rb.size(1) < (int64_t)stride || rb.size(1) % 16 != 0 ||
       reinterpret_cast<uintptr_t>(rb.data_ptr()) % 16 != 0)
-    return done(value_error("records must be a contiguous [clients, >= stride] uint8 block (16-B rows) on the device"));
+    return value_error("records must be a contiguous [clients, >= stride] uint8 block (16-B rows) on the device");
   const at::Tensor* ws = usable_as(wso, at::kByte, &dev);
-  if (!ws) return done(type_error("ws must be a contiguous uint8 HIP tensor on the deltas' device"));
+  if (!ws) return type_error("ws must be a contiguous uint8 HIP tensor on the deltas' device");
   uint8_t* base = rb.data_ptr<uint8_t>();
   const int64_t rs = rb.size(1);
   std::vector<int32_t*> ip(C);
   std::vector<uint8_t*> kp(C);
   std::vector<float*> np(C);
   std::vector<uint32_t*> tp(C);
-  std::vector<const int32_t*> cip(C);
   for (Py_ssize_t c = 0; c < C; ++c) {
     uint8_t* r = base + c * rs;
     np[c] = reinterpret_cast<float*>(r + off[0]);
     ip[c] = reinterpret_cast<int32_t*>(r + off[1]);
-    cip[c] = ip[c];
     kp[c] = r + off[2];
     tp[c] = reinterpret_cast<uint32_t*>(r + off[3]);
   }
-  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
-  int rc = FLC_OK;
-  const char* what = round ? "flc_stacked_encode_round" : "flc_stacked_encode_batch";
-  Py_BEGIN_ALLOW_THREADS
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  if (cur != dev) (void)hipSetDevice(dev);
-  if (round) {
-    rc = flc_stacked_encode_round(xp.data(), (int)C, n, k, levels, sd.data(), ct64.data(), ip.data(), kp.data(),
-                                  np.data(), tp.data(), cp.data(), ws->data_ptr(), (size_t)ws->numel(), st);
-  } else {
-    rc = flc_stacked_encode_batch(xp.data(), (int)C, n, k, levels, sd.data(), counter, ip.data(), kp.data(), np.data(),
-                                  tp.data(), ws->data_ptr(), (size_t)ws->numel(), st);
-    if (rc == FLC_OK) {
-      what = "flc_count_nonzero_at_batch";
-      rc = flc_count_nonzero_at_batch(xp.data(), cip.data(), (int)C, n, k, cp.data(), st);
-    }
-  }
-  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
-  Py_END_ALLOW_THREADS
-  if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "%s failed with status %d: %s", what, rc, flc_last_error());
-    return done(nullptr);
-  }
-  return done((Py_INCREF(Py_None), Py_None));
+  if (!on_device(dev, "flc_stacked_encode_round", [&](void* st) {
+        return flc_stacked_encode_round(xp.data(), (int)C, n, k, levels, sd.data(), ct64.data(), ip.data(), kp.data(),
+                                        np.data(), tp.data(), cp.data(), ws->data_ptr(), (size_t)ws->numel(), st);
+      }))
+    return nullptr;
+  Py_RETURN_NONE;
 }
-PyObject* stacked_records_batch(PyObject*, PyObject* args) { return stacked_records(args, false); }
-PyObject* stacked_records_round(PyObject*, PyObject* args) { return stacked_records(args, true); }
 
 // fold_records(records, weights, n, k, levels, delta, theta, v, beta0, opt, lr, beta2, tau): the server update of a
 // round of stacked records (flc_fedopt_fold_records) on Python lists.  TypeError (nothing launched) when a tensor is
@@ -724,88 +642,44 @@ PyObject* stacked_records_round(PyObject*, PyObject* args) { return stacked_reco
 PyObject* fold_records_of(PyObject* recs, PyObject* weights, long long n, long long k, int format, int levels, int bits,
                           PyObject* delta, PyObject* theta, PyObject* v, double beta0, int opt, double lr, double beta2,
                           double tau) {
-  std::vector<PyObject*> keep;
-  auto done = [&](PyObject* r) {
-    for (PyObject* o : keep) Py_XDECREF(o);
-    return r;
-  };
+  Refs refs;
   PyObject* seqs[3] = {recs, weights, delta};
   PyObject* f[3];
-  for (int i = 0; i < 3; ++i) {
-    f[i] = PySequence_Fast(seqs[i], "fold_records takes sequences");
-    if (!f[i]) return done(nullptr);
-    keep.push_back(f[i]);
-  }
-  const Py_ssize_t nr = PySequence_Fast_GET_SIZE(f[0]), nt = PySequence_Fast_GET_SIZE(f[2]);
-  if (PySequence_Fast_GET_SIZE(f[1]) != nr) return done(value_error("one weight per record"));
-  if (nr < 1 || nt < 1) return done(type_error("fold_records needs records and server tensors"));
+  for (int i = 0; i < 3; ++i)
+    if (!(f[i] = refs.fast(seqs[i], "fold_records takes sequences"))) return nullptr;
+  const Py_ssize_t nr = len(f[0]), nt = len(f[2]);
+  if (len(f[1]) != nr) return value_error("one weight per record");
+  if (nr < 1 || nt < 1) return type_error("fold_records needs records and server tensors");
   int dev = -1;
   std::vector<float*> dp(nt), tp, vp;
   std::vector<int64_t> sz(nt);
+  if (tensor_row(items(f[2]), nt, &dev, sz.data(), true, dp.data()))
+    return type_error("server tensors must be contiguous fp32 HIP tensors on one device");
   int64_t total = 0;
-  PyObject** di = PySequence_Fast_ITEMS(f[2]);
-  for (Py_ssize_t t = 0; t < nt; ++t) {
-    const at::Tensor* a = usable(di[t], &dev);
-    if (!a) return done(type_error("server tensors must be contiguous fp32 HIP tensors on one device"));
-    dp[t] = a->data_ptr<float>();
-    sz[t] = a->numel();
-    total += sz[t];
-  }
-  if (total != n) return done(type_error("the server tensors do not hold the records' element count"));
-  for (int which = 0; which < 2; ++which) {
-    PyObject* src = which == 0 ? theta : v;
-    if (src == Py_None) continue;
-    PyObject* fs = PySequence_Fast(src, "theta / v must be sequences of tensors");
-    if (!fs) return done(nullptr);
-    keep.push_back(fs);
-    if (PySequence_Fast_GET_SIZE(fs) != nt) return done(type_error("theta / v need one tensor per server tensor"));
-    std::vector<float*>& out = which == 0 ? tp : vp;
-    out.resize(nt);
-    PyObject** it = PySequence_Fast_ITEMS(fs);
-    for (Py_ssize_t t = 0; t < nt; ++t) {
-      const at::Tensor* a = usable(it[t], &dev);
-      if (!a || a->numel() != sz[t]) return done(type_error("theta / v must match the server tensors"));
-      out[t] = a->data_ptr<float>();
-    }
-  }
+  for (int64_t s : sz) total += s;
+  if (total != n) return type_error("the server tensors do not hold the records' element count");
+  if (!optimizer_rows(refs, theta, v, nt, &dev, sz.data(), true, &tp, &vp)) return nullptr;
   int64_t off[4];
   const size_t stride = format < 0 ? flc_stacked_wire_layout(n, k, off) : flc_dense_wire_layout(n, format, bits, off);
-  if (stride == 0) return done(value_error("bad wire shape"));
+  if (stride == 0) return value_error("bad wire shape");
   std::vector<const void*> rp(nr);
   std::vector<float> w(nr);
-  PyObject** ri = PySequence_Fast_ITEMS(f[0]);
-  PyObject** wi = PySequence_Fast_ITEMS(f[1]);
   for (Py_ssize_t c = 0; c < nr; ++c) {
-    const at::Tensor* r = usable_as(ri[c], at::kByte, &dev);
-    if (!r || (size_t)r->numel() < stride || reinterpret_cast<uintptr_t>(r->data_ptr()) % 16 != 0)
-      return done(type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the server's device"));
-    rp[c] = r->data_ptr();
-    const double wd = PyFloat_AsDouble(wi[c]);
-    if (wd == -1.0 && PyErr_Occurred()) return done(nullptr);
-    w[c] = (float)wd;
+    if (!(rp[c] = record_ptr(items(f[0])[c], stride, &dev)))
+      return type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the server's device");
+    if (!as_f32(items(f[1])[c], &w[c])) return nullptr;
   }
-  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
-  int rc = FLC_OK;
-  Py_BEGIN_ALLOW_THREADS
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  if (cur != dev) (void)hipSetDevice(dev);
-  if (format < 0)
-    rc = flc_fedopt_fold_records(rp.data(), w.data(), (int)nr, n, k, levels, dp.data(),
-                                 tp.empty() ? nullptr : tp.data(), vp.empty() ? nullptr : vp.data(), sz.data(), (int)nt,
-                                 (float)beta0, opt, lr, beta2, tau, st);
-  else
-    rc = flc_fedopt_fold_dense_records(rp.data(), w.data(), (int)nr, n, format, levels, bits, dp.data(),
-                                       tp.empty() ? nullptr : tp.data(), vp.empty() ? nullptr : vp.data(), sz.data(),
-                                       (int)nt, (float)beta0, opt, lr, beta2, tau, st);
-  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
-  Py_END_ALLOW_THREADS
-  if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "%s failed with status %d: %s",
-                 format < 0 ? "flc_fedopt_fold_records" : "flc_fedopt_fold_dense_records", rc, flc_last_error());
-    return done(nullptr);
-  }
-  return done((Py_INCREF(Py_None), Py_None));
+  float* const* thp = tp.empty() ? nullptr : tp.data();
+  float* const* vvp = vp.empty() ? nullptr : vp.data();
+  if (!on_device(dev, format < 0 ? "flc_fedopt_fold_records" : "flc_fedopt_fold_dense_records", [&](void* st) {
+        return format < 0 ? flc_fedopt_fold_records(rp.data(), w.data(), (int)nr, n, k, levels, dp.data(), thp, vvp,
+                                                    sz.data(), (int)nt, (float)beta0, opt, lr, beta2, tau, st)
+                          : flc_fedopt_fold_dense_records(rp.data(), w.data(), (int)nr, n, format, levels, bits, dp.data(),
+                                                          thp, vvp, sz.data(), (int)nt, (float)beta0, opt, lr, beta2, tau,
+                                                          st);
+      }))
+    return nullptr;
+  Py_RETURN_NONE;
 }
 PyObject* fold_records(PyObject*, PyObject* args) {
   PyObject *recs, *weights, *delta, *theta, *v;
@@ -842,24 +716,17 @@ PyObject* fold_record_groups(PyObject*, PyObject* args) {
   long long n, k;
   int levels;
   if (!PyArg_ParseTuple(args, "OOOLLi", &recs, &weights, &dsts, &n, &k, &levels)) return nullptr;
-  std::vector<PyObject*> keep;
-  auto done = [&](PyObject* r) {
-    for (PyObject* o : keep) Py_XDECREF(o);
-    return r;
-  };
-  auto fast = [&](PyObject* o) {
-    PyObject* f = PySequence_Fast(o, "fold_record_groups takes sequences of sequences");
-    if (f) keep.push_back(f);
-    return f;
-  };
-  PyObject *fr = fast(recs), *fw = fr ? fast(weights) : nullptr, *fd = fw ? fast(dsts) : nullptr;
-  if (!fd) return done(nullptr);
-  const Py_ssize_t ng = PySequence_Fast_GET_SIZE(fd);
-  if (ng < 1 || PySequence_Fast_GET_SIZE(fr) != ng || PySequence_Fast_GET_SIZE(fw) != ng)
-    return done(type_error("fold_record_groups needs one record list, weight list and tensor list per group"));
+  Refs refs;
+  const char* const not_seq = "fold_record_groups takes sequences of sequences";
+  PyObject *fr = refs.fast(recs, not_seq), *fw = fr ? refs.fast(weights, not_seq) : nullptr,
+           *fd = fw ? refs.fast(dsts, not_seq) : nullptr;
+  if (!fd) return nullptr;
+  const Py_ssize_t ng = len(fd);
+  if (ng < 1 || len(fr) != ng || len(fw) != ng)
+    return type_error("fold_record_groups needs one record list, weight list and tensor list per group");
   int64_t off[4];
   const size_t stride = flc_stacked_wire_layout(n, k, off);
-  if (stride == 0) return done(value_error("bad wire shape"));
+  if (stride == 0) return value_error("bad wire shape");
   int dev = -1;
   std::vector<float*> dp;
   std::vector<int64_t> sz;
@@ -867,57 +734,46 @@ PyObject* fold_record_groups(PyObject*, PyObject* args) {
   std::vector<float> w;
   std::vector<int32_t> gof;
   for (Py_ssize_t g = 0; g < ng; ++g) {
-    PyObject* ft = fast(PySequence_Fast_ITEMS(fd)[g]);
-    if (!ft) return done(nullptr);
-    const Py_ssize_t nt = PySequence_Fast_GET_SIZE(ft);
+    PyObject* ft = refs.fast(items(fd)[g], not_seq);
+    if (!ft) return nullptr;
+    const Py_ssize_t nt = len(ft);
     if (nt < 1 || (g > 0 && (size_t)nt != sz.size()))
-      return done(type_error("every group needs the first group's number of tensors"));
+      return type_error("every group needs the first group's number of tensors");
     if (g == 0) sz.resize(nt);
     int64_t total = 0;
     for (Py_ssize_t t = 0; t < nt; ++t) {
-      const at::Tensor* a = usable(PySequence_Fast_ITEMS(ft)[t], &dev);
-      if (!a) return done(type_error("server tensors must be contiguous fp32 HIP tensors on one device"));
-      if (g == 0) sz[t] = a->numel();
-      else if (a->numel() != sz[t]) return done(type_error("every group's tensors must match the first group's sizes"));
+      float* q = nullptr;
+      if (Bad b = take(items(ft)[t], &dev, &sz[t], g == 0, &q))
+        return type_error(b == kBadTensor ? "server tensors must be contiguous fp32 HIP tensors on one device"
+                                          : "every group's tensors must match the first group's sizes");
       total += sz[t];
-      float* q = a->data_ptr<float>();
       if (sz[t] > 0)
         for (float* other : dp)
-          if (other == q) return done(type_error("a server tensor in two places"));
+          if (other == q) return type_error("a server tensor in two places");
       dp.push_back(q);
     }
-    if (total != n) return done(type_error("the server tensors do not hold the records' element count"));
-    PyObject* frg = fast(PySequence_Fast_ITEMS(fr)[g]);
-    PyObject* fwg = frg ? fast(PySequence_Fast_ITEMS(fw)[g]) : nullptr;
-    if (!fwg) return done(nullptr);
-    const Py_ssize_t nr = PySequence_Fast_GET_SIZE(frg);
-    if (PySequence_Fast_GET_SIZE(fwg) != nr) return done(value_error("one weight per record"));
+    if (total != n) return type_error("the server tensors do not hold the records' element count");
+    PyObject* frg = refs.fast(items(fr)[g], not_seq);
+    PyObject* fwg = frg ? refs.fast(items(fw)[g], not_seq) : nullptr;
+    if (!fwg) return nullptr;
+    const Py_ssize_t nr = len(frg);
+    if (len(fwg) != nr) return value_error("one weight per record");
     for (Py_ssize_t c = 0; c < nr; ++c) {
-      const at::Tensor* r = usable_as(PySequence_Fast_ITEMS(frg)[c], at::kByte, &dev);
-      if (!r || (size_t)r->numel() < stride || reinterpret_cast<uintptr_t>(r->data_ptr()) % 16 != 0)
-        return done(type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the server's device"));
-      rp.push_back(r->data_ptr());
-      const double wd = PyFloat_AsDouble(PySequence_Fast_ITEMS(fwg)[c]);
-      if (wd == -1.0 && PyErr_Occurred()) return done(nullptr);
-      w.push_back((float)wd);
+      const void* r = record_ptr(items(frg)[c], stride, &dev);
+      if (!r) return type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the server's device");
+      rp.push_back(r);
+      float wc;
+      if (!as_f32(items(fwg)[c], &wc)) return nullptr;
+      w.push_back(wc);
       gof.push_back((int32_t)g);
     }
   }
-  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
-  int rc = FLC_OK;
-  Py_BEGIN_ALLOW_THREADS
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  if (cur != dev) (void)hipSetDevice(dev);
-  rc = flc_fold_record_groups(rp.data(), w.data(), gof.data(), (int)rp.size(), n, k, levels, dp.data(), (int)ng,
-                              sz.data(), (int)sz.size(), st);
-  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
-  Py_END_ALLOW_THREADS
-  if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "flc_fold_record_groups failed with status %d: %s", rc, flc_last_error());
-    return done(nullptr);
-  }
-  return done((Py_INCREF(Py_None), Py_None));
+  if (!on_device(dev, "flc_fold_record_groups", [&](void* st) {
+        return flc_fold_record_groups(rp.data(), w.data(), gof.data(), (int)rp.size(), n, k, levels, dp.data(), (int)ng,
+                                      sz.data(), (int)sz.size(), st);
+      }))
+    return nullptr;
+  Py_RETURN_NONE;
 }
 
 // avg_and_gradient_records(params, msgs, records, w_params, w_grads, n, k, levels, inertia, set_grad): a
@@ -933,124 +789,53 @@ PyObject* avg_and_gradient_records(PyObject*, PyObject* args) {
   double inertia;
   if (!PyArg_ParseTuple(args, "OOOOOLLid|p", &params, &msgs, &recs, &wpar, &wgrd, &n, &k, &levels, &inertia, &set_grad))
     return nullptr;
-  std::vector<PyObject*> keep;
-  auto done = [&](PyObject* r) {
-    for (PyObject* o : keep) Py_XDECREF(o);
-    return r;
-  };
+  Refs refs;
   const bool p_on = msgs != Py_None;
   PyObject* seqs[5] = {params, recs, wgrd, p_on ? msgs : recs, p_on ? wpar : wgrd};
   PyObject* f[5];
-  for (int i = 0; i < 5; ++i) {
-    f[i] = PySequence_Fast(seqs[i], "avg_and_gradient_records takes sequences");
-    if (!f[i]) return done(nullptr);
-    keep.push_back(f[i]);
-  }
-  const Py_ssize_t nt = PySequence_Fast_GET_SIZE(f[0]), ns = PySequence_Fast_GET_SIZE(f[1]);
-  if (PySequence_Fast_GET_SIZE(f[2]) != ns || PySequence_Fast_GET_SIZE(f[3]) != ns || PySequence_Fast_GET_SIZE(f[4]) != ns)
-    return done(value_error("one record, one message and one weight of each kind per message"));
-  if (ns < 1 || nt < 1) return done(type_error("avg_and_gradient_records needs records and model tensors"));
+  for (int i = 0; i < 5; ++i)
+    if (!(f[i] = refs.fast(seqs[i], "avg_and_gradient_records takes sequences"))) return nullptr;
+  const Py_ssize_t nt = len(f[0]), ns = len(f[1]);
+  if (len(f[2]) != ns || len(f[3]) != ns || len(f[4]) != ns)
+    return value_error("one record, one message and one weight of each kind per message");
+  if (ns < 1 || nt < 1) return type_error("avg_and_gradient_records needs records and model tensors");
   int dev = -1;
   std::vector<float*> pp(nt), gp(nt);
   std::vector<int64_t> sz(nt);
   std::vector<const at::Tensor*> pt(nt);
+  if (tensor_row(items(f[0]), nt, &dev, sz.data(), true, pp.data(), pt.data()))
+    return type_error("model tensors must be contiguous fp32 HIP tensors on one device");
   int64_t total = 0;
-  PyObject** pi = PySequence_Fast_ITEMS(f[0]);
-  for (Py_ssize_t t = 0; t < nt; ++t) {
-    const at::Tensor* a = usable(pi[t], &dev);
-    if (!a) return done(type_error("model tensors must be contiguous fp32 HIP tensors on one device"));
-    pt[t] = a;
-    pp[t] = a->data_ptr<float>();
-    sz[t] = a->numel();
-    total += sz[t];
-  }
-  if (total != n) return done(type_error("the model tensors do not hold the records' element count"));
+  for (int64_t s : sz) total += s;
+  if (total != n) return type_error("the model tensors do not hold the records' element count");
   int64_t off4[4];
   const size_t stride = flc_stacked_wire_layout(n, k, off4);
-  if (stride == 0) return done(value_error("bad wire shape"));
+  if (stride == 0) return value_error("bad wire shape");
   std::vector<const void*> rp(ns);
   std::vector<const float*> ps(p_on ? (size_t)ns * nt : 0);
   std::vector<float> wp(ns), wg(ns);
-  PyObject** ri = PySequence_Fast_ITEMS(f[1]);
-  PyObject** wgi = PySequence_Fast_ITEMS(f[2]);
-  PyObject** mi = PySequence_Fast_ITEMS(f[3]);
-  PyObject** wpi = PySequence_Fast_ITEMS(f[4]);
   static PyObject* const key = PyUnicode_InternFromString("parameters");
   for (Py_ssize_t m = 0; m < ns; ++m) {
-    const at::Tensor* r = usable_as(ri[m], at::kByte, &dev);
-    if (!r || (size_t)r->numel() < stride || reinterpret_cast<uintptr_t>(r->data_ptr()) % 16 != 0)
-      return done(type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the model's device"));
-    rp[m] = r->data_ptr();
-    const double b = PyFloat_AsDouble(wgi[m]);
-    if (b == -1.0 && PyErr_Occurred()) return done(nullptr);
-    wg[m] = (float)b;
+    if (!(rp[m] = record_ptr(items(f[1])[m], stride, &dev)))
+      return type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the model's device");
+    if (!as_f32(items(f[2])[m], &wg[m])) return nullptr;
     if (!p_on) continue;
-    const double a = PyFloat_AsDouble(wpi[m]);
-    if (a == -1.0 && PyErr_Occurred()) return done(nullptr);
-    wp[m] = (float)a;
-    PyObject* v = PyObject_GetItem(mi[m], key);
-    if (!v) return done(nullptr);
-    keep.push_back(v);
-    PyObject* fv = PySequence_Fast(v, "a message's parameters are a sequence of tensors");
-    if (!fv) return done(nullptr);
-    keep.push_back(fv);
-    if (PySequence_Fast_GET_SIZE(fv) != nt) return done(type_error("every message has one tensor per model tensor"));
-    PyObject** it = PySequence_Fast_ITEMS(fv);
-    for (Py_ssize_t t = 0; t < nt; ++t) {
-      const at::Tensor* s = usable(it[t], &dev);
-      if (!s || s->numel() != sz[t])
-        return done(type_error("message tensors must be contiguous fp32 HIP tensors of the model's sizes and device"));
-      ps[(size_t)m * nt + t] = s->data_ptr<float>();
-    }
+    if (!as_f32(items(f[4])[m], &wp[m])) return nullptr;
+    if (Bad b = message_row(refs, items(f[3])[m], key, "a message's parameters are a sequence of tensors", nt, &dev,
+                            sz.data(), &ps[(size_t)m * nt]))
+      return message_error(b, true);
   }
   // (every tensor checked: the gradient buffer is allocated now)
   at::Tensor flat;
   std::vector<at::Tensor> gv;
-  try {
-    flat = at::empty({total > 0 ? total : 1}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, dev));
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
-    return done(nullptr);
-  }
-  gv.reserve(nt);
-  int64_t off = 0;
-  for (Py_ssize_t t = 0; t < nt; ++t) {
-    gv.push_back(flat.narrow(0, off, sz[t]).view(pt[t]->sizes()));
-    gp[t] = flat.data_ptr<float>() + off;
-    off += sz[t];
-  }
-  void* st = c10::hip::getCurrentHIPStream((c10::DeviceIndex)dev).stream();
-  int rc = FLC_OK;
-  Py_BEGIN_ALLOW_THREADS
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  if (cur != dev) (void)hipSetDevice(dev);
-  rc = flc_avg_and_gradient_records(p_on ? pp.data() : nullptr, gp.data(), p_on ? ps.data() : nullptr, rp.data(),
-                                    p_on ? wp.data() : nullptr, wg.data(), (int)ns, n, k, levels, sz.data(), (int)nt,
-                                    (float)inertia, st);
-  if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
-  Py_END_ALLOW_THREADS
-  if (rc != FLC_OK) {
-    PyErr_Format(PyExc_RuntimeError, "flc_avg_and_gradient_records failed with status %d: %s", rc, flc_last_error());
-    return done(nullptr);
-  }
-  PyObject* lst = PyList_New(nt);
-  if (!lst) return done(nullptr);
-  for (Py_ssize_t t = 0; t < nt; ++t) {
-    if (set_grad) pt[t]->mutable_grad() = gv[t];  // (update_gradients' `mp.grad = ...`: same device, dtype, sizes)
-    PyObject* w = THPVariable_Wrap(gv[t]);
-    if (!w) {
-      Py_DECREF(lst);
-      return done(nullptr);
-    }
-    PyList_SET_ITEM(lst, t, w);
-  }
-  PyObject* fl = THPVariable_Wrap(flat);
-  if (!fl) {
-    Py_DECREF(lst);
-    return done(nullptr);
-  }
-  return done(Py_BuildValue("(NN)", lst, fl));
+  if (!gradient_views(pt, sz, dev, &flat, &gv, gp.data())) return nullptr;
+  if (!on_device(dev, "flc_avg_and_gradient_records", [&](void* st) {
+        return flc_avg_and_gradient_records(p_on ? pp.data() : nullptr, gp.data(), p_on ? ps.data() : nullptr, rp.data(),
+                                            p_on ? wp.data() : nullptr, wg.data(), (int)ns, n, k, levels, sz.data(),
+                                            (int)nt, (float)inertia, st);
+      }))
+    return nullptr;
+  return views_result(pt, gv, flat, set_grad != 0);
 }
 
 void release_storage(void* ctx) { delete static_cast<c10::Storage*>(ctx); }
@@ -1071,8 +856,8 @@ PyObject* alias(PyObject*, PyObject* args) {
     return nullptr;
   }
   const size_t nbytes = (size_t)t.numel() * t.element_size();
-  auto* keep = new c10::Storage(t.storage());
-  c10::DataPtr dp(p, keep, &release_storage, c10::Device(c10::DeviceType::CUDA, (c10::DeviceIndex)dev));
+  auto* held = new c10::Storage(t.storage());
+  c10::DataPtr dp(p, held, &release_storage, c10::Device(c10::DeviceType::CUDA, (c10::DeviceIndex)dev));
   c10::Storage st(c10::Storage::use_byte_size_t(), nbytes, std::move(dp), /*allocator=*/nullptr, /*resizable=*/false);
   at::Tensor d = at::empty({0}, t.options().device(c10::Device(c10::DeviceType::CUDA, (c10::DeviceIndex)dev)).pinned_memory(false));
   d.set_(st, 0, t.sizes(), t.strides());
@@ -1110,9 +895,6 @@ PyMethodDef kMethods[] = {
     {"stacked_records_round", stacked_records_round, METH_VARARGS,
      "stacked_records_round(flats, seeds, counters, k, levels, records, counts, ws): flc_stacked_encode_round into the "
      "rows of a record block, one Philox counter per message, the send counts written by the encode itself"},
-    {"stacked_records_batch", stacked_records_batch, METH_VARARGS,
-     "stacked_records_batch(flats, seeds, counter, k, levels, records, counts, ws): flc_stacked_encode_batch into the "
-     "rows of a record block, then flc_count_nonzero_at_batch into counts"},
     {"stacked_delta_record", stacked_delta_record, METH_VARARGS,
      "stacked_delta_record(local, global, k, levels, seed, counter, record, count, ws): flc_stacked_encode_delta into a "
      "packed wire record (+ flc_delta_count_nonzero_at into count) on the current stream of the tensors' device"},
