@@ -161,6 +161,22 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
          c_void_p],
     ),
+    "flc_sparse_wire_layout": (c_size_t, [c_int64, c_int64, c_void_p]),
+    "flc_fold_sparse_wires": (
+        c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p]
+    ),
+    "flc_fedopt_fold_sparse_records": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int,
+         c_double, c_double, c_double, c_void_p],
+    ),
+    "flc_fold_sparse_record_groups": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p]
+    ),
+    "flc_avg_and_gradient_sparse_records": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                    c_int64, c_int64, c_void_p, c_int, c_float, c_void_p]),
+    "flc_sparse_gather": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p]),
+    "flc_ef_residual_sparse_round": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "flc_comm_id_bytes": (c_size_t, []),
     "flc_comm_rccl_origin": (c_char_p, []),
     "flc_comm_unique_id": (c_int, [c_void_p]),

@@ -178,9 +178,10 @@ def _flat_views(like: Sequence[torch.Tensor], **kw):
 
 def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs, wg: Sequence[float],
                   wp: Optional[Sequence[float]] = None, inertia: float = 0.0) -> Optional[List[torch.Tensor]]:
-    """A round whose ``gradients`` are stacked records (``recs``: compressed.stacked_round(messages, "gradients")):
-    every record decoded and folded into one flat gradient buffer and, with ``wp``, the dense ``parameters`` folded
-    into the model in the same pass (flc_avg_and_gradient_records); the records are never decoded densely.  Sets
+    """A round whose ``gradients`` are stacked records (``recs``: compressed.stacked_round(messages, "gradients")) or
+    sparse records (compressed.sparse_round): every record decoded and folded into one flat gradient buffer and, with
+    ``wp``, the dense ``parameters`` folded into the model in the same pass (flc_avg_and_gradient_records /
+    flc_avg_and_gradient_sparse_records); the records are never decoded densely.  Sets
     ``.grad`` of every parameter and returns the gradients; None (nothing launched, nothing changed) when the model
     is not one the launch takes — the caller's dense path follows.  A host-resident model is staged: the records (and
     the messages' parameters) in, the parameters out, the gradients out in one copy."""
@@ -213,7 +214,7 @@ def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs
             grads.append(host[off:off + p.numel()].view(p.shape))
             off += p.numel()
     else:
-        fast = codec._pygrecs()
+        fast = codec._pygrecs() if recs[0].kind == "stacked" else None  # (sparse records: the ctypes call below)
         if fast is not None and mps and isinstance(mps[0], torch.Tensor) and mps[0].is_cuda:
             # one C call: every tensor and record checked in place, the fold, the gradients' buffer and views, and every
             # parameter's `.grad`; a TypeError (a tensor the launch does not take, or messages elsewhere) leaves
@@ -245,7 +246,7 @@ def update_gradients(model_params: Sequence[torch.Tensor], messages: Sequence[Ma
         return None
     assert all(["gradients" in m for m in messages]), "some clients have not sent gradients yet"
     model_params = list(model_params)
-    recs = (compressed.stacked_round(messages, key="gradients")
+    recs = ((compressed.stacked_round(messages, key="gradients") or compressed.sparse_round(messages, key="gradients"))
             if isinstance(messages[0]["gradients"], compressed.CompressedDelta) else None)
     if recs is not None:
         total_samples = sum([m["train_samples"] for m in messages])
@@ -346,7 +347,7 @@ def avg_parameters_and_gradients(model_params: Sequence[torch.Tensor], messages:
     wg = [m["train_samples"] / total for m in messages]
     n = len(messages)
     if isinstance(messages[0]["gradients"], compressed.CompressedDelta):
-        recs = compressed.stacked_round(messages, key="gradients")
+        recs = compressed.stacked_round(messages, key="gradients") or compressed.sparse_round(messages, key="gradients")
         if recs is not None:  # compressed gradients: the records folded beside the dense parameters, in the same pass
             r = _record_round(mps, messages, recs, wg, wp, inertia)
             if r is not None:
@@ -789,7 +790,7 @@ class VRUpdateMixin:
         if hoststage.is_host(mps):
             keys = ["parameters"] + (["gradients"] if self.config.vr else [])
             # (compressed gradients are placed by their record or flat vector: iterating them would decode them)
-            _adopt([mps], [[m[k].record if m[k].kind == "stacked" else m[k].flat()]
+            _adopt([mps], [[m[k].record if m[k].kind in ("stacked", "sparse") else m[k].flat()]
                            if isinstance(m[k], compressed.CompressedDelta) else m[k]
                            for m in self._received_messages for k in keys])
             mps = list(self.model.parameters())  # (the adopted tensors)

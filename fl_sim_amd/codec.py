@@ -817,6 +817,122 @@ def stacked_decode(pkt: StackedPacket, out: Optional[torch.Tensor] = None, weigh
     return out
 
 
+# ------------------------------------------------------------------------- sparse records (top-k / rand-k wire)
+_SPARSE_LAYOUT = {}
+
+
+def sparse_wire_layout(n: int, k: int):
+    """(record bytes, {"idx", "val", "tiles"} byte offsets) of a sparse record (flc_sparse_wire_layout): the top-k /
+    rand-k wire — ascending int32 indices, the decoded fp32 values, tile pointers — as one contiguous record whose
+    layout depends on (n, k) only."""
+    import ctypes
+
+    key = (int(n), int(k))
+    r = _SPARSE_LAYOUT.get(key)
+    if r is None:
+        off = (ctypes.c_int64 * 3)()
+        total = _lib.size("flc_sparse_wire_layout", key[0], key[1], ctypes.cast(off, ctypes.c_void_p))
+        if total == 0:
+            raise ValueError(f"bad sparse record shape n={n}, k={k}")
+        r = _SPARSE_LAYOUT[key] = (int(total), dict(zip(("idx", "val", "tiles"), (int(v) for v in off))))
+    return r
+
+
+def sparse_wire_views(record: torch.Tensor, n: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(idx, val, tiles) views into a sparse record (a contiguous uint8 HIP tensor of at least
+    ``sparse_wire_layout(n, k)[0]`` bytes, 16-B aligned)."""
+    stride, off = sparse_wire_layout(n, k)
+    if record.dtype != torch.uint8 or record.device.type != "cuda" or not record.is_contiguous():
+        raise TypeError("a wire record is a contiguous uint8 HIP tensor")
+    rec = record.reshape(-1)
+    if rec.numel() < stride or rec.data_ptr() % 16 != 0:
+        raise ValueError(f"a sparse record needs {stride} bytes, 16-B aligned")
+    ntiles = (n + TILE - 1) // TILE + 1
+    return (rec[off["idx"]:off["idx"] + 4 * k].view(torch.int32), rec[off["val"]:off["val"] + 4 * k].view(torch.float32),
+            rec[off["tiles"]:off["tiles"] + 4 * ntiles].view(torch.int32))
+
+
+def sparse_record_decode(record: torch.Tensor, n: int, k: int, out: Optional[torch.Tensor] = None,
+                         weight: float = 1.0, accumulate: bool = False) -> torch.Tensor:
+    """The decoded flat vector of a sparse record (flc_sparse_decode_tiled on its views, scale 1)."""
+    idx, val, tiles = sparse_wire_views(record, n, k)
+    return sparse_decode(idx, val, n, 1.0, out=out, weight=weight, accumulate=accumulate, tiles=tiles)
+
+
+def topk_encode_record(x: torch.Tensor, k: int, record: torch.Tensor) -> torch.Tensor:
+    """The top-k of the flat vector ``x`` written into the sparse record ``record`` (flc_topk_encode_tiled with the
+    three pointers inside it)."""
+    x = _dev_f32(x).reshape(-1)
+    n = x.numel()
+    idx, val, tiles = sparse_wire_views(record, n, k)
+    ws = workspace(x.device, _ws_size(x.device, "flc_topk_workspace_size", n, k), "topk")
+    call("flc_topk_encode_tiled", _p(x), n, k, _p(idx), _p(val), _p(tiles), _p(ws), ws.numel(), _stream(x.device))
+    _after_encode(x.device)
+    return record
+
+
+def topk_encode_records(xs: Sequence[torch.Tensor], k: int, records: torch.Tensor) -> torch.Tensor:
+    """A round's top-k messages in one call (flc_topk_encode_batch): row c of the ``[C, >= stride]`` uint8 block
+    ``records`` (16-B rows) takes the sparse record of the flat fp32 vector ``xs[c]`` — all of one size on one device —
+    equal to ``topk_encode_record(xs[c], k, records[c])``."""
+    import ctypes
+
+    C = len(xs)
+    if C == 0:
+        return records
+    n, dev = xs[0].numel(), xs[0].device
+    xp = _batch_ptrs(xs, n, dev) if dev.type == "cuda" else None
+    if xp is None:
+        xs = [_dev_f32(x).reshape(-1) for x in xs]
+        if any(x.numel() != n or x.device != dev for x in xs):
+            raise ValueError("a batched encode takes clients of one size on one device")
+        xp = [x.data_ptr() for x in xs]
+    stride, off = sparse_wire_layout(n, k)
+    if not (isinstance(records, torch.Tensor) and records.dim() == 2 and records.shape[0] == C
+            and records.shape[1] % 16 == 0 and records.device == dev):
+        raise ValueError(f"records must be a [{C}, >= {stride}] uint8 block (16-B rows) on {dev}")
+    sparse_wire_views(records[0], n, k)  # (dtype, size and alignment, checked on one row for all)
+    bases = [records.data_ptr() + c * records.shape[1] for c in range(C)]
+    P = ctypes.c_void_p * C
+    vp = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+    ws = workspace(dev, _ws_size(dev, "flc_topk_encode_batch_workspace_size", n, k, C), "topk_batch")
+    with torch.cuda.device(dev):
+        call("flc_topk_encode_batch", vp(P(*xp)), C, n, k, vp(P(*[b + off["idx"] for b in bases])),
+             vp(P(*[b + off["val"] for b in bases])), vp(P(*[b + off["tiles"] for b in bases])), _p(ws), ws.numel(),
+             _stream(dev))
+    _after_encode(dev)
+    return records
+
+
+def sparse_gather(x: torch.Tensor, idx: torch.Tensor, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[j] = fp32(scale) * x[idx[j]]`` (flc_sparse_gather): rand-k's kept values, bit-equal to what
+    ``randk_apply`` scatters; ``out``: a sparse record's val view."""
+    x = _dev_f32(x).reshape(-1)
+    k = idx.numel()
+    if out is None:
+        out = torch.empty(k, dtype=torch.float32, device=x.device)
+    call("flc_sparse_gather", _p(x), x.numel(), _p(idx), k, scale, _p(out), _stream(x.device))
+    return out
+
+
+def fold_sparse_wires(wires: torch.Tensor, slots: Sequence[int], weights: Sequence[float], n: int, k: int,
+                      out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """``out = (accumulate ? out : 0) + Σ_c weights[c] · decode(wires[slots[c]])`` in client order, one pass
+    (flc_fold_sparse_wires).  ``wires``: a [records, stride] uint8 HIP tensor of sparse records."""
+    import ctypes
+
+    if wires.dtype != torch.uint8 or wires.dim() != 2 or not wires.is_contiguous() or wires.device.type != "cuda":
+        raise TypeError("wires must be a contiguous [records, stride] uint8 HIP tensor")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs an out tensor")
+        out = torch.empty(n, dtype=torch.float32, device=wires.device)
+    m = len(slots)
+    call("flc_fold_sparse_wires", _p(wires), wires.shape[1], (ctypes.c_int32 * m)(*[int(s) for s in slots]),
+         (ctypes.c_float * m)(*[float(w) for w in weights]), m, n, k, int(accumulate), _p(out), _stream(wires.device))
+    return out
+
+
 def stacked_fold_wires(wires: torch.Tensor, slots: Sequence[int], weights: Sequence[float], n: int, k: int,
                        levels: int = 127, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """Server fold of many clients' packed wires in one pass (flc_stacked_fold_wires):
@@ -996,6 +1112,7 @@ _PYSRV: list = []
 _PYPAIR: list = []
 _PYRECS: list = []
 _PYDRECS: list = []
+_PYSRECS: list = []
 _PYGROUPS: list = []
 _PYGRECS: list = []
 _PYFLAT: list = []
@@ -1027,6 +1144,11 @@ def _pyrecs():
 def _pydrecs():
     """_flcfold.fold_dense_records (flc_fedopt_fold_dense_records on lists, one C call), or None."""
     return _flcfold_entry(_PYDRECS, "fold_dense_records")
+
+
+def _pysrecs():
+    """_flcfold.fold_sparse_records (flc_fedopt_fold_sparse_records on lists, one C call), or None."""
+    return _flcfold_entry(_PYSRECS, "fold_sparse_records")
 
 
 def _pygroups():
@@ -1285,6 +1407,32 @@ def ef_residual_round(records: Sequence[torch.Tensor], memories: Sequence[torch.
     with torch.cuda.device(dev):
         call("flc_ef_residual_round", ctypes.cast(rp, ctypes.c_void_p), ctypes.cast(ep, ctypes.c_void_p), C, int(n),
              int(k), int(levels), _stream(dev))
+
+
+def ef_residual_sparse_round(records: Sequence[torch.Tensor], memories: Sequence[torch.Tensor], n: int, k: int) -> None:
+    """``memories[c][idx] -= val`` at every sparse record's kept entries, all clients in one launch
+    (flc_ef_residual_sparse_round): the residual ``e' = a − c`` of a round's top-k / rand-k records."""
+    import ctypes
+
+    if len(records) != len(memories):
+        raise ValueError("one memory per record")
+    if not records:
+        return
+    dev = memories[0].device
+    stride, _ = sparse_wire_layout(n, k)
+    for r, e in zip(records, memories):
+        _ef_memory(e, "a memory")
+        if e.numel() != n or e.device != dev:
+            raise ValueError(f"every memory holds n = {n} elements on one device")
+        if r.dtype != torch.uint8 or r.device != dev or not r.is_contiguous() or r.numel() < stride:
+            raise ValueError(f"a wire record is a contiguous uint8 tensor of at least {stride} bytes on the memories' "
+                             "device")
+    C = len(records)
+    rp = (ctypes.c_void_p * C)(*[r.data_ptr() for r in records])
+    ep = (ctypes.c_void_p * C)(*[e.data_ptr() for e in memories])
+    with torch.cuda.device(dev):
+        call("flc_ef_residual_sparse_round", ctypes.cast(rp, ctypes.c_void_p), ctypes.cast(ep, ctypes.c_void_p), C,
+             int(n), int(k), _stream(dev))
 
 
 def ef_residual_dense(e: torch.Tensor, c: torch.Tensor) -> torch.Tensor:

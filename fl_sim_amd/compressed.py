@@ -27,6 +27,15 @@ What runs here instead:
   In philox mode a dithering quantizer's records of up to 2^20 elements (device norm, p = ∞ or 2, no error feedback)
   are deferred like the stacked ones: the round's messages are encoded by one ``flc_quant_encode_round`` when a record
   or a statistic is first read (:func:`deferred_dense_stats` counts these batches).
+  With ``sparse_records`` on (a switch of its own, looked up the same way; ``sparse=True`` on the three compress
+  functions; off by default) a compressor list that is one float32 top-k or rand-k compressor with 0 < K < n whose
+  record is smaller than 4·n bytes (:func:`sparse_wire_codec`) sends its sparse record (``flc_sparse_wire_layout``:
+  the ascending kept indices, their decoded fp32 values — rand-k's already ``D / K · x`` — and the tile pointers: 8 B
+  per kept entry), written by ``flc_topk_encode_tiled`` (rand-k: the index set as today — the reference's ``np.random``
+  shuffle prefix sorted on the host, or the K largest Philox keys — then ``flc_sparse_gather``), the RNG streams and
+  send statistics advancing as ``compressVector`` advances them.  Top-k draws no random numbers, so in any
+  ``rng_mode`` its records of up to 2^24 elements are deferred: one ``flc_topk_encode_batch`` writes the round's
+  records (:func:`deferred_sparse_stats` counts these batches); rand-k encodes at once.
   Either way ``delta_parameters`` is a :class:`CompressedDelta`: a sequence of per-tensor tensors that decodes itself
   on first access, so any server — the reference's own ``update`` included — reads it unchanged.
 * ``aggregation.fedopt_update`` (and :class:`~fl_sim_amd.aggregation.FedOptUpdateMixin`) recognises a round of stacked
@@ -35,8 +44,10 @@ What runs here instead:
   v) read and written once; bit-identical to decoding each record and running the reference's update.  A round of
   dense records of one (n, format, levels, bits) (:func:`dense_record_round`) takes the same functions
   (``flc_fedopt_fold_dense_records``; for SCAFFOLD and IFCA ``flc_fold_dense_record_groups``): the server reads the
-  codes, 1/4 to 1/16 of the dense bytes.  A mixed round, and the variance-reduced servers' ``gradients``, read each
-  message as its decoded tensors.
+  codes, 1/4 to 1/16 of the dense bytes.  A round of sparse records of one (n, k) (:func:`sparse_round`) takes them too
+  (``flc_fedopt_fold_sparse_records``, ``flc_fold_sparse_record_groups``, and for the variance-reduced servers'
+  ``gradients`` ``flc_avg_and_gradient_sparse_records``).  A mixed round, and the variance-reduced servers'
+  ``gradients`` as dense records, read each message as its decoded tensors.
 
 The compressors' send statistics advance as ``compressVector`` advances them (``compressors.py:406-408``), per stage.
 
@@ -71,7 +82,9 @@ batch item's flat input (no snapshot), and after the batch's ``flc_stacked_encod
 stays pending with its memories holding ``a``; a memory still waiting in a batch when its client communicates again
 has that batch run first).  The immediate stacked paths encode the memory and run the residual with one client; any
 other compressor chain runs on the memory's values, then ``flc_ef_residual_dense`` (with ``wire`` on, on the decoded
-dense record, which the message does not keep).  ``feedback=None`` is the path above, untouched.
+dense record, which the message does not keep).  A sparse record's residual is K entries too
+(``flc_ef_residual_sparse_round``: once per deferred batch after its encode succeeded, with one client on the immediate
+paths).  ``feedback=None`` is the path above, untouched.
 """
 
 from __future__ import annotations
@@ -88,6 +101,7 @@ import torch
 
 from . import _lib, codec
 from ._lib import FLC_NORM_INF, FLC_NORM_L2, FLC_Q_NATURAL_DITHER, FLC_Q_STANDARD_DITHER, FLC_WIRE_NATURAL
+from . import rng as _rng
 from .compressors import Compressor, CompressorType
 from .feedback import ErrorFeedbackClientMixin, ErrorMemory
 
@@ -121,7 +135,8 @@ class CompressedDelta(_abc.Sequence):
     """A client's compressed model delta as its message carries it.
 
     ``kind == "stacked"``: the packed wire record of the stacked codec (top-k ascending int32 indices, 8-bit
-    sign | level codes, the kept set's norm, tile pointers); ``kind == "quant"`` / ``"natural"`` (``wire=True``): the
+    sign | level codes, the kept set's norm, tile pointers); ``kind == "sparse"`` (``sparse=True``): the sparse record
+    of a top-k or rand-k compressor (ascending int32 indices, the decoded fp32 values, tile pointers); ``kind == "quant"`` / ``"natural"`` (``wire=True``): the
     dense record of a dithering quantizer (its norm and packed ``bits``-bit codes) or of the natural compressor (one
     uint16 per element), ``format`` being flc_dense_wire_layout's; ``kind == "dense"``: the decoded flat delta.
     Indexing gives tensor ``j`` of the model's shapes (the decoded values, one flat decode on first access), so code
@@ -129,7 +144,7 @@ class CompressedDelta(_abc.Sequence):
 
     def __init__(self, shapes: Sequence[torch.Size], device: torch.device, n: int, *, record=None, k: int = 0,
                  levels: int = 0, flat: Optional[torch.Tensor] = None, batch: Optional["_Batch"] = None,
-                 format: Optional[int] = None, bits: int = 0):
+                 format: Optional[int] = None, bits: int = 0, sparse: bool = False):
         self.shapes = [torch.Size(s) for s in shapes]
         self.device = device
         self.n = int(n)
@@ -138,6 +153,8 @@ class CompressedDelta(_abc.Sequence):
         self.format, self.bits = format, int(bits)
         if format is not None:
             self.kind = "natural" if format == FLC_WIRE_NATURAL else "quant"
+        elif sparse:  # (a top-k / rand-k record, flc_sparse_wire_layout(n, k): levels 0, no format)
+            self.kind = "sparse"
         else:
             self.kind = "stacked" if record is not None or batch is not None else "dense"
         self._flat = flat
@@ -145,7 +162,7 @@ class CompressedDelta(_abc.Sequence):
 
     @property
     def record(self) -> Optional[torch.Tensor]:
-        """The packed wire record (stacked, quant, natural), or None (dense)."""
+        """The packed wire record (stacked, sparse, quant, natural), or None (dense)."""
         if self._batch is not None:
             self._batch.run()
         return self._record
@@ -172,11 +189,13 @@ class CompressedDelta(_abc.Sequence):
         return int(self.record.numel()) if self.record is not None else 4 * self.n
 
     def flat(self) -> torch.Tensor:
-        """The decoded flat delta (flc_stacked_decode_tiled, flc_quant_decode or flc_natural_decode of the record,
-        once)."""
+        """The decoded flat delta (flc_stacked_decode_tiled, flc_sparse_decode_tiled, flc_quant_decode or
+        flc_natural_decode of the record, once)."""
         if self._flat is None:
             if self.kind in ("quant", "natural"):
                 self._flat = codec.dense_record_decode(self.record, self.n, self.format, self.levels, self.bits)
+            elif self.kind == "sparse":
+                self._flat = codec.sparse_record_decode(self.record, self.n, self.k)
             else:
                 self._flat = codec.stacked_decode(codec.wire_packet(self.record, self.n, self.k, self.levels))
         return self._flat
@@ -258,28 +277,32 @@ def _norm_stage_send(sd: Compressor, norm: torch.Tensor) -> float:
 
 def compress_delta(local: Sequence[torch.Tensor], cached: Sequence[torch.Tensor],
                    compressors: Sequence[Compressor], feedback: Optional[ErrorMemory] = None,
-                   wire: bool = False) -> CompressedDelta:
+                   wire: bool = False, sparse: bool = False) -> CompressedDelta:
     """The client's compressed delta ``compressors(cat(local − cached))`` (see the module docstring); every compressor's
     RNG stream and send statistics advance as its own ``compressVector`` call would advance them.  ``feedback``: the
     client's :class:`~fl_sim_amd.feedback.ErrorMemory` ``e`` for this vector — the message is then that of the input
     ``a = e + (local − cached)`` and the memory takes ``a − c`` (error feedback; None: nothing remembered).  ``wire``:
     one float32 dithering quantizer or natural compressor (:func:`dense_wire_codec`) sends its dense record — the norm
-    and the packed codes — instead of the decoded vector; any other compressor list is sent as without it."""
+    and the packed codes — instead of the decoded vector; any other compressor list is sent as without it.  ``sparse``:
+    one top-k or rand-k compressor (:func:`sparse_wire_codec`) sends its sparse record — the kept indices, their decoded
+    values and the tile pointers — instead of the decoded vector; any other compressor list is sent as without it."""
     if feedback is not None:
-        return _compress_feedback(list(local), cached, compressors, feedback, wire)
-    return _compress(list(local), cached, compressors, wire)
+        return _compress_feedback(list(local), cached, compressors, feedback, wire, sparse)
+    return _compress(list(local), cached, compressors, wire, sparse)
 
 
 def compress_tensors(tensors: Sequence[torch.Tensor], compressors: Sequence[Compressor],
-                     feedback: Optional[ErrorMemory] = None, wire: bool = False) -> CompressedDelta:
+                     feedback: Optional[ErrorMemory] = None, wire: bool = False,
+                     sparse: bool = False) -> CompressedDelta:
     """``compressors(cat(tensors))`` — :func:`compress_delta` with nothing subtracted (a client's gradient list): the
     stacked pipeline gives a packed record, any other compressor the decoded flat vector (``wire``: a dithering
-    quantizer's or the natural compressor's dense record); the compressors' RNG streams
+    quantizer's or the natural compressor's dense record; ``sparse``: a top-k or rand-k compressor's sparse record);
+    the compressors' RNG streams
     and send statistics advance alike, and in philox mode a deferred message joins the round's batched encode with the
     flat vector as its snapshot.  ``feedback``: as for :func:`compress_delta` (``a = e + cat(tensors)``)."""
     if feedback is not None:
-        return _compress_feedback(list(tensors), None, compressors, feedback, wire)
-    return _compress(list(tensors), None, compressors, wire)
+        return _compress_feedback(list(tensors), None, compressors, feedback, wire, sparse)
+    return _compress(list(tensors), None, compressors, wire, sparse)
 
 
 def dense_wire_codec(compressors: Sequence[Compressor]) -> Optional[Tuple[int, int, int]]:
@@ -369,13 +392,77 @@ def _dense_record(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[i
     return CompressedDelta(shapes, dev, n, record=rec, levels=s, format=fmt, bits=bits)
 
 
+def sparse_wire_codec(compressors: Sequence[Compressor], n: Optional[int] = None) -> Optional[int]:
+    """``K`` of the sparse record ``compressors`` sends with ``sparse`` on for a float32 vector of ``n`` elements
+    (default: the compressor's own ``D``) — one top-k or rand-k compressor (compressors.py:284-296) with 0 < K < n (a
+    rand-k: built for that n) whose record, ``flc_sparse_wire_layout(n, K)``, is smaller than the vector's 4·n bytes —
+    else None: the message is then sent as without the option (a top-k with K <= 0 or K >= n copies,
+    compressors.py:293-296)."""
+    if len(compressors) != 1 or not isinstance(compressors[0], Compressor):
+        return None
+    c = compressors[0]
+    t = c.compressorType
+    if t not in (CompressorType.TOPK_COMPRESSOR, CompressorType.RANDK_COMPRESSOR):
+        return None
+    if n is None:
+        n = getattr(c, "D", None)
+    try:
+        n, K = int(n), int(c.K)
+    except (TypeError, ValueError):
+        return None
+    if K != c.K or not 0 < K < n or n >= 1 << 31:
+        return None
+    if t == CompressorType.RANDK_COMPRESSOR and int(c.D) != n:
+        return None
+    if codec.sparse_wire_layout(n, K)[0] >= 4 * n:
+        return None
+    return K
+
+
+def _all_f32(local, cached) -> bool:
+    """Every tensor of the message is float32 (the sparse record is the float32 form: a float64 model keeps today's
+    message)."""
+    return all(t.dtype is torch.float32 for t in local) and (
+        cached is None or all(t.dtype is torch.float32 for t in cached))
+
+
+def _sparse_record(x: torch.Tensor, shapes, n: int, comp: Compressor, K: int, dev) -> CompressedDelta:
+    """The sparse record of the flat fp32 vector ``x`` under the top-k or rand-k compressor ``comp``, written by the
+    encoders straight into the record, nothing decoded.  The RNG streams and send statistics advance exactly as
+    ``comp.compressVector(x)`` advances them (compressors.py:284-296): top-k draws nothing; rand-k takes the
+    reference's ``np.random`` shuffle prefix (compat; sorted ascending on the host — the indices are unique, so the
+    decoded vector does not depend on their order) or one ``philox.next()`` (the K largest Philox keys, ascending,
+    with their tile pointers), then ``flc_sparse_gather`` writes ``fp32(D / K) * x[idx]``."""
+    x = codec._dev_f32(x).reshape(-1)
+    stride, _ = codec.sparse_wire_layout(n, K)
+    rec = torch.empty(stride, dtype=torch.uint8, device=dev)
+    if comp.compressorType == CompressorType.TOPK_COMPRESSOR:
+        codec.topk_encode_record(x, K, rec)  # compressors.py:293-296
+        comp._finish(n, comp.K)
+        return CompressedDelta(shapes, dev, n, record=rec, k=K, sparse=True)
+    idx, val, tiles = codec.sparse_wire_views(rec, n, K)
+    st = codec._stream(dev)
+    if comp.rng_mode == "compat":  # compressors.py:285-288: the reference's own permutation, on the host
+        S = np.sort(_rng.numpy_shuffle_prefix(comp.D, comp.K)).astype(np.int32)
+        idx.copy_(torch.from_numpy(S))
+        _lib.call("flc_tile_index", idx.data_ptr(), K, n, tiles.data_ptr(), st)
+    else:  # the K largest of n Philox keys: the top-k encoder on the keys writes idx and tiles (val: the keys, replaced)
+        seed, ctr = comp.philox.next()
+        keys = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.call("flc_randk_keys", n, seed, ctr, keys.data_ptr(), st)
+        codec.topk_encode_record(keys, K, rec)
+    codec.sparse_gather(x, idx, float(np.float32(comp.D / comp.K)), out=val)  # compressors.py:289-291
+    comp._finish(n, comp.K)
+    return CompressedDelta(shapes, dev, n, record=rec, k=K, sparse=True)
+
+
 def _flatten(ts: Sequence[torch.Tensor], dev: torch.device) -> torch.Tensor:
     """cat(ts) as a new flat fp32 vector on ``dev`` (a snapshot: the tensors may change before a deferred encode)."""
     return torch.cat([t.reshape(-1) for t in _fp32_on(ts, dev)])
 
 
 def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
-              compressors: Sequence[Compressor], wire: bool = False) -> CompressedDelta:
+              compressors: Sequence[Compressor], wire: bool = False, sparse: bool = False) -> CompressedDelta:
     """``compressors(cat(local − cached))``, or (``cached`` None) ``compressors(cat(local))``."""
     dev = local[0].device if local[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
     shapes = [t.shape for t in local]
@@ -421,6 +508,11 @@ def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]
             if r is not None:
                 return r
         return _dense_record(out, shapes, n, compressors[0], dc, dev)
+    K = sparse_wire_codec(compressors, n) if sparse and _all_f32(local, cached) else None
+    if K is not None:  # the sparsifier's own wire as the message: (idx, val, tiles) written into the record
+        if DEFER_ENCODE and n <= _DEFER_MAX_N and compressors[0].compressorType == CompressorType.TOPK_COMPRESSOR:
+            return _defer_sparse(out, shapes, n, K, compressors[0], dev, None)  # (out: a new vector, the snapshot)
+        return _sparse_record(out, shapes, n, compressors[0], K, dev)
     for comp in compressors:  # the drop-in compressors on the device, in order
         out = comp.compressVector(out)
     return CompressedDelta(shapes, dev, n, flat=out)
@@ -440,10 +532,12 @@ def _accumulate(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tenso
 
 
 def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
-                       compressors: Sequence[Compressor], mem: ErrorMemory, wire: bool = False) -> CompressedDelta:
+                       compressors: Sequence[Compressor], mem: ErrorMemory, wire: bool = False,
+                       sparse: bool = False) -> CompressedDelta:
     """:func:`_compress` of ``a = e + (local − cached)`` with the memory ``e`` of ``mem`` as the encoders' flat input,
     then ``e = a − c`` (fl_sim_amd/feedback.py): the K-entry residual of a stacked record (after the batched encode
-    when the message is deferred), the dense one of any other compressor's decoded vector."""
+    when the message is deferred), the K-entry residual of a sparse record likewise (flc_ef_residual_sparse_round),
+    the dense one of any other compressor's decoded vector."""
     dev = local[0].device if local[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
     shapes = [t.shape for t in local]
     n = sum(t.numel() for t in local)
@@ -469,6 +563,13 @@ def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torc
     if dc is not None:  # the message carries the record; the memory takes a − decode(record) (these quantizers are
         d = _dense_record(e, shapes, n, compressors[0], dc, dev)  # unbiased: the plain dense residual)
         codec.ef_residual_dense(e, codec.dense_record_decode(d._record, n, dc[0], dc[1], dc[2]))
+        return d
+    K = sparse_wire_codec(compressors, n) if sparse and _all_f32(local, cached) else None
+    if K is not None:  # the memory is the encoder's input; it takes a − c at the record's K kept entries
+        if DEFER_ENCODE and n <= _DEFER_MAX_N and compressors[0].compressorType == CompressorType.TOPK_COMPRESSOR:
+            return _defer_sparse(e, shapes, n, K, compressors[0], dev, mem)
+        d = _sparse_record(e, shapes, n, compressors[0], K, dev)
+        codec.ef_residual_sparse_round([d._record], [e], n, K)
         return d
     out = e
     for comp in compressors:  # the drop-in compressors on the device, in order (each returns a new vector)
@@ -497,6 +598,7 @@ _DEFER_MAX_BATCHES = 16
 
 _STATS = {"batches": 0, "messages": 0}
 _DENSE_STATS = {"batches": 0, "messages": 0}
+_SPARSE_STATS = {"batches": 0, "messages": 0}
 
 
 def _read_stats(stats: dict, reset: bool) -> dict:
@@ -515,6 +617,11 @@ def deferred_stats(reset: bool = False) -> dict:
 def deferred_dense_stats(reset: bool = False) -> dict:
     """:func:`deferred_stats` for the dense records' batched encodes (flc_quant_encode_round), counted apart."""
     return _read_stats(_DENSE_STATS, reset)
+
+
+def deferred_sparse_stats(reset: bool = False) -> dict:
+    """:func:`deferred_stats` for the sparse records' batched encodes (flc_topk_encode_batch), counted apart."""
+    return _read_stats(_SPARSE_STATS, reset)
 
 
 class _Item(NamedTuple):
@@ -626,6 +733,30 @@ class _DenseBatch(_Batch):
         return recs.unbind(0)
 
 
+# Deferred sparse records (`sparse` on, one top-k compressor, any rng_mode: top-k draws no random numbers).  The
+# model-sized select is the same fixed latency as the stacked pipeline's, so these messages wait like the stacked ones
+# — the flat delta snapshotted (or the error memory's tensor itself), the send statistics advanced at `communicate` —
+# and one flc_topk_encode_batch writes the round's records into the rows of one block, equal to the per-message
+# flc_topk_encode_tiled.  The same switch (FLC_DEFER_ENCODE), size bound and pending bounds as the stacked batches.
+# Rand-k keeps the immediate path.
+class _SparseBatch(_Batch):
+    """The waiting top-k messages of one (device, "sparse", n, K); an item has no Philox state and no count slot."""
+
+    stats = _SPARSE_STATS
+
+    def _encode_rows(self, items, dev):
+        _, _, n, k = self.key
+        stride, _ = codec.sparse_wire_layout(n, k)
+        recs = torch.empty(len(items), stride, dtype=torch.uint8, device=dev)
+        codec.topk_encode_records([it.flat for it in items], k, recs)
+        rows = recs.unbind(0)
+        fed = [(r, it.mem) for it, r in zip(items, rows) if it.mem is not None]
+        if fed:  # error feedback: e = a − c at the records' kept entries, one launch for the round, after the encode
+            # succeeded (an encode that raised never gets here: the memories then still hold a)
+            codec.ef_residual_sparse_round([r for r, _ in fed], [m._e for _, m in fed], n, k)
+        return rows
+
+
 _PENDING: dict = {}
 
 
@@ -714,6 +845,18 @@ def _defer_dense(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[in
     else:
         comp._finish(n, n * _code_fraction(s))
     return _enqueue(b, _Item(d, x, seed, ctr, cnt, comp if std else None, st, st.cuda_stream, None))
+
+
+def _defer_sparse(flat: torch.Tensor, shapes, n: int, K: int, tk: Compressor, dev,
+                  mem: Optional[ErrorMemory]) -> CompressedDelta:
+    """The top-k message of the flat vector ``flat`` (a snapshot, or — ``mem`` — that error memory's tensor, which
+    takes the residual once the batch has encoded) joins the round's batched top-k encode; the send statistics advance
+    here as ``compressVector`` advances them (compressors.py:293-296)."""
+    st = torch.cuda.current_stream(dev)
+    b = _waiting(_SparseBatch, (dev.index, "sparse", n, K))
+    d = CompressedDelta(shapes, dev, n, k=K, batch=b, sparse=True)
+    tk._finish(n, tk.K)
+    return _enqueue(b, _Item(d, flat, 0, 0, None, None, st, st.cuda_stream, mem))
 
 
 def _stacked_fast(local, cached, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compressor, dev,
@@ -828,22 +971,38 @@ def dense_record_round(messages: Sequence, key: str = "delta_parameters") -> Opt
     return ds
 
 
+def sparse_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
+    """The messages' compressed deltas when every one is a sparse record (``kind`` "sparse") of one (n, k), else None
+    (a mixed round: each message then decodes itself)."""
+    ds = _round_deltas(messages, key, ("sparse",))
+    if ds is None:
+        return None
+    d0 = ds[0]
+    if any((d.n, d.k) != (d0.n, d0.k) for d in ds):
+        return None
+    return ds
+
+
 def record_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
-    """:func:`stacked_round` or :func:`dense_record_round`: a round the record folds take, else None."""
-    return stacked_round(messages, key) or dense_record_round(messages, key)
+    """:func:`stacked_round`, :func:`dense_record_round` or :func:`sparse_round`: a round the record folds take, else
+    None."""
+    return stacked_round(messages, key) or dense_record_round(messages, key) or sparse_round(messages, key)
 
 
 def fold_records(deltas: Sequence[CompressedDelta], weights: Sequence[float], delta_params: Sequence[torch.Tensor],
                  theta: Optional[Sequence[torch.Tensor]], v: Optional[Sequence[torch.Tensor]], beta0: float,
                  opt: str = "avg", lr: float = 1.0, beta2: float = 0.0, tau: float = 0.0) -> bool:
     """``δ = β0·δ + Σ_c w_c·decode(record_c)`` in message order, then (``theta``) the server optimiser's step — one
-    ``flc_fedopt_fold_records`` pass.  False (nothing launched) when the server tensors are not contiguous fp32 tensors
+    ``flc_fedopt_fold_records`` pass (``flc_fedopt_fold_dense_records`` / ``flc_fedopt_fold_sparse_records`` by the
+    records' kind).  False (nothing launched) when the server tensors are not contiguous fp32 tensors
     of one HIP device holding the records' element count (the caller then takes the dense path)."""
     dps = list(delta_params)
     d0 = deltas[0]
-    dense = d0.kind != "stacked"  # (a dense_record_round: flc_fedopt_fold_dense_records, the same contract)
-    shape = (d0.n, d0.format, d0.levels, d0.bits) if dense else (d0.n, d0.k, d0.levels)
-    fast = codec._pydrecs() if dense else codec._pyrecs()
+    # (a dense_record_round: flc_fedopt_fold_dense_records; a sparse_round: flc_fedopt_fold_sparse_records — the same
+    # contract)
+    sparse, dense = d0.kind == "sparse", d0.kind in ("quant", "natural")
+    shape = (d0.n, d0.k) if sparse else (d0.n, d0.format, d0.levels, d0.bits) if dense else (d0.n, d0.k, d0.levels)
+    fast = codec._pysrecs() if sparse else codec._pydrecs() if dense else codec._pyrecs()
     if fast is not None and dps:
         try:  # one C call: every tensor checked in place; TypeError: nothing launched, the checks below decide
             fast([d.record for d in deltas], [float(w) for w in weights], *shape, dps,
@@ -866,7 +1025,9 @@ def fold_records(deltas: Sequence[CompressedDelta], weights: Sequence[float], de
         return False
     recs = [d.record if d.record.device == dev else d.record.to(dev) for d in deltas]
     m, T = len(recs), len(dps)
-    _lib.call("flc_fedopt_fold_dense_records" if dense else "flc_fedopt_fold_records", _ptrs(recs),
+    fn = ("flc_fedopt_fold_sparse_records" if sparse else
+          "flc_fedopt_fold_dense_records" if dense else "flc_fedopt_fold_records")
+    _lib.call(fn, _ptrs(recs),
               (ctypes.c_float * m)(*[float(w) for w in weights]), m, *shape, _ptrs(dps),
               _ptrs(groups[1]) if theta is not None else None,
               _ptrs(groups[2]) if v is not None else None, (ctypes.c_int64 * T)(*[t.numel() for t in dps]), T,
@@ -906,10 +1067,13 @@ def fold_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequence[f
     recs = [d.record for d in deltas] if records is None else list(records)
     recs = [r if r.device == dev else r.to(dev) for r in recs]
     fl = lambda ws: (ctypes.c_float * m)(*[float(w) for w in ws])  # noqa: E731
+    sparse = d0.kind == "sparse"  # (a sparse_round: flc_avg_and_gradient_sparse_records, the same contract)
     with torch.cuda.device(dev):
-        _lib.call("flc_avg_and_gradient_records", _ptrs(ps) if ps is not None else None, _ptrs(gs),
+        _lib.call("flc_avg_and_gradient_sparse_records" if sparse else "flc_avg_and_gradient_records",
+                  _ptrs(ps) if ps is not None else None, _ptrs(gs),
                   _ptrs([t for r in srcs for t in r]) if srcs is not None else None, _ptrs(recs),
-                  fl(w_params) if ps is not None else None, fl(w_grads), m, d0.n, d0.k, d0.levels,
+                  fl(w_params) if ps is not None else None, fl(w_grads), m, d0.n, d0.k,
+                  *(() if sparse else (d0.levels,)),
                   (ctypes.c_int64 * T)(*[g.numel() for g in gs]), T, float(inertia), codec._stream(dev))
     return True
 
@@ -933,9 +1097,11 @@ def fold_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequenc
         return False
     if any(len(ws) != len(ds) or (rs is not None and len(rs) != len(ds)) for ds, ws, _, rs in live):
         return False
-    dense = d0.kind != "stacked"  # (dense records: flc_fold_dense_record_groups through ctypes, the same contract)
-    shape = (d0.n, d0.format, d0.levels, d0.bits) if dense else (d0.n, d0.k, d0.levels)
-    fast = None if dense else codec._pygroups()
+    # (dense and sparse records: flc_fold_dense_record_groups / flc_fold_sparse_record_groups through ctypes, the same
+    # contract)
+    sparse, dense = d0.kind == "sparse", d0.kind in ("quant", "natural")
+    shape = (d0.n, d0.k) if sparse else (d0.n, d0.format, d0.levels, d0.bits) if dense else (d0.n, d0.k, d0.levels)
+    fast = None if (dense or sparse) else codec._pygroups()
     if fast is not None:
         try:  # one C call: every tensor checked in place; TypeError: nothing launched, the checks below decide
             fast([[d.record for d in ds] if rs is None else rs for ds, _, _, rs in live],
@@ -971,7 +1137,9 @@ def fold_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequenc
         dsts += dst
     m, T = len(recs), len(sizes)
     with torch.cuda.device(dev):
-        _lib.call("flc_fold_dense_record_groups" if dense else "flc_fold_record_groups", _ptrs(recs),
+        fn = ("flc_fold_sparse_record_groups" if sparse else
+              "flc_fold_dense_record_groups" if dense else "flc_fold_record_groups")
+        _lib.call(fn, _ptrs(recs),
                   (ctypes.c_float * m)(*ws), (ctypes.c_int32 * m)(*gof), m, *shape, _ptrs(dsts), len(live),
                   (ctypes.c_int64 * T)(*sizes), T, codec._stream(dev))
     return True
@@ -995,6 +1163,15 @@ def _wire_records(node) -> bool:
     return bool(v)
 
 
+def _sparse_records(node) -> bool:
+    """``sparse_records`` looked up on the client, then on its config (as ``wire_records`` is); absent or false: the
+    top-k and rand-k compressors send their decoded vectors."""
+    v = getattr(node, "sparse_records", None)
+    if v is None:
+        v = getattr(getattr(node, "config", None), "sparse_records", None)
+    return bool(v)
+
+
 class CompressedFedOptClientMixin(ErrorFeedbackClientMixin):
     """Mix in before the reference's ``FedOptClient`` (``class C(CompressedFedOptClientMixin, FedOptClient)``):
     ``communicate`` (_fedopt.py:295-308) sends the delta through the client's compressors (``self.compressors``, or
@@ -1008,7 +1185,8 @@ class CompressedFedOptClientMixin(ErrorFeedbackClientMixin):
         # (the parameters as they are: the codec only reads them, and every converting path detaches first)
         params = list(self.model.parameters())
         delta = compress_delta(params, self._cached_parameters, _compressors_of(self),
-                               self._feedback_for("delta_parameters", params), wire=_wire_records(self))
+                               self._feedback_for("delta_parameters", params), wire=_wire_records(self),
+                               sparse=_sparse_records(self))
         target._received_messages.append(
             client_message_class()(
                 **{
@@ -1039,13 +1217,13 @@ class CompressedSCAFFOLDClientMixin(ErrorFeedbackClientMixin):
         params = list(self.model.parameters())
         if cs:
             pd = compress_delta(params, self._cached_parameters, cs, self._feedback_for("parameters_delta", params),
-                                wire=_wire_records(self))
+                                wire=_wire_records(self), sparse=_sparse_records(self))
         else:
             pd = [mp.detach().sub(cp) for mp, cp in zip(params, self._cached_parameters)]
         if ccs:
             ucvs = list(self._updated_control_variates)
             cd = compress_delta(ucvs, self._control_variates, ccs, self._feedback_for("control_variates_delta", ucvs),
-                                wire=_wire_records(self))
+                                wire=_wire_records(self), sparse=_sparse_records(self))
         else:
             cd = [ucv.sub(cv) for ucv, cv in zip(self._updated_control_variates, self._control_variates)]
         target._received_messages.append(
@@ -1075,7 +1253,8 @@ class CompressedIFCAClientMixin(ErrorFeedbackClientMixin):
     def communicate(self, target) -> None:
         params = list(self.model.parameters())
         delta = compress_delta(params, self._cached_parameters, _compressors_of(self),
-                               self._feedback_for("delta_parameters", params), wire=_wire_records(self))
+                               self._feedback_for("delta_parameters", params), wire=_wire_records(self),
+                               sparse=_sparse_records(self))
         target._received_messages.append(
             client_message_class()(
                 **{
@@ -1089,7 +1268,8 @@ class CompressedIFCAClientMixin(ErrorFeedbackClientMixin):
         )
 
 
-def compress_message_gradients(message, compressors: Sequence[Compressor], feedback=None, wire: bool = False) -> None:
+def compress_message_gradients(message, compressors: Sequence[Compressor], feedback=None, wire: bool = False,
+                               sparse: bool = False) -> None:
     """Replace ``message["gradients"]`` (a list of tensors) with the :class:`CompressedDelta` made from them
     (:func:`compress_tensors`); no compressors, no gradients or gradients already compressed: the message as it is.
     ``feedback``: the client's error memory for the vector, or a callable that makes it from the gradient list (called
@@ -1098,7 +1278,8 @@ def compress_message_gradients(message, compressors: Sequence[Compressor], feedb
     if not compressors or gs is None or isinstance(gs, CompressedDelta) or len(gs) == 0:
         return
     gs = list(gs)
-    message["gradients"] = compress_tensors(gs, compressors, feedback(gs) if callable(feedback) else feedback, wire)
+    message["gradients"] = compress_tensors(gs, compressors, feedback(gs) if callable(feedback) else feedback, wire,
+                                            sparse)
 
 
 class CompressedGradientsClientMixin(ErrorFeedbackClientMixin):
@@ -1123,4 +1304,5 @@ class CompressedGradientsClientMixin(ErrorFeedbackClientMixin):
             return
         for m in target._received_messages[before if target._received_messages is received else 0:]:
             if isinstance(m, dict) and "gradients" in m:
-                compress_message_gradients(m, cs, lambda gs: self._feedback_for("gradients", gs), _wire_records(self))
+                compress_message_gradients(m, cs, lambda gs: self._feedback_for("gradients", gs), _wire_records(self),
+                                           _sparse_records(self))

@@ -4,12 +4,14 @@
 // Per round and message vector (fl_sim_amd/feedback.py, compressed.py):
 //   a  = fp32(e + fp32(local - cached))    flc_ef_accumulate, in place in e (a gradient list: a = fp32(e + x))
 //   c  = compressors(a)                    the existing encoders with e as their flat input
-//   e' = fp32(a - c)                       flc_ef_residual_round (stacked records) / flc_ef_residual_dense
+//   e' = fp32(a - c)                       flc_ef_residual_round (stacked records) / flc_ef_residual_sparse_round
+//                                          (sparse records) / flc_ef_residual_dense
 // The stacked pipeline's c is nonzero only at the record's K kept indices, and a - (+0) == a bit for bit (a -0
 // included), so its residual is K read-modify-writes per client, not a pass over e: one launch covers a round's
 // clients (client on grid.y), each thread four consecutive entries of one record (one 16-B load of idx, one 4-B load
 // of codes).  A record's indices are unique, so nothing is atomic; an index outside [0, n) — a record an encode that
-// failed left behind — is skipped, so nothing is written outside e.
+// failed left behind — is skipped, so nothing is written outside e.  A sparse record (the top-k / rand-k wire,
+// compressors.py:284-296) takes the same K-entry pass with its fp32 val field in place of the dequantised codes.
 //
 // The accumulate has delta_flatten_kernel's shape (delta.hip): a kernel-argument tensor pack, one 4096-element chunk
 // of one tensor per 256-thread block, 16-B accesses where the operands and the tensor's slot in e are 16-B aligned
@@ -126,6 +128,40 @@ __global__ __launch_bounds__(kThreads) void ef_residual_round_kernel(ResidualPac
     if (i[r] < n) e[i[r]] = m[r] - stacked_dequant(code[r], levels, step, nrm);
 }
 
+// es[c][idx[j]] -= val[j] for the entries j < k of client c = blockIdx.y's sparse record (flc_sparse_wire_layout): the
+// kernel above with the record's fp32 values (one 16-B load) in place of its codes and norm
+__global__ __launch_bounds__(kThreads) void ef_residual_sparse_round_kernel(ResidualPack p, long long idx_off,
+                                                                           long long val_off, unsigned n, unsigned k) {
+  const int c = blockIdx.y;  // (uniform)
+  const uint8_t* __restrict__ rec = p.rec[c];
+  float* __restrict__ e = p.e[c];
+  const unsigned* __restrict__ ix = reinterpret_cast<const unsigned*>(rec + idx_off);
+  const float* __restrict__ vl = reinterpret_cast<const float*>(rec + val_off);
+  const unsigned j0 = (blockIdx.x * kThreads + threadIdx.x) * kPerThread;  // (k < 2^31: no wrap)
+  if (j0 >= k) return;
+  unsigned i[kPerThread];
+  float v[kPerThread];
+  if (j0 + kPerThread <= k) {  // (idx and val start 16-B aligned in a 16-B aligned record)
+    const uint4 iv = *reinterpret_cast<const uint4*>(ix + j0);
+    const float4 vv = *reinterpret_cast<const float4*>(vl + j0);
+    i[0] = iv.x, i[1] = iv.y, i[2] = iv.z, i[3] = iv.w;
+    v[0] = vv.x, v[1] = vv.y, v[2] = vv.z, v[3] = vv.w;
+  } else {
+#pragma unroll
+    for (int r = 0; r < kPerThread; ++r) {
+      const bool in = j0 + r < k;
+      i[r] = in ? ix[j0 + r] : 0xffffffffu;  // (past the record's end: an index no n admits)
+      v[r] = in ? vl[j0 + r] : 0.0f;
+    }
+  }
+  float m[kPerThread];
+#pragma unroll
+  for (int r = 0; r < kPerThread; ++r) m[r] = i[r] < n ? e[i[r]] : 0.0f;  // (unsigned compare: a negative index too)
+#pragma unroll
+  for (int r = 0; r < kPerThread; ++r)
+    if (i[r] < n) e[i[r]] = m[r] - v[r];
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void ef_residual_dense_kernel(float* __restrict__ e, const float* __restrict__ c,
                                                                     int64_t n) {
@@ -207,31 +243,34 @@ int flc_ef_accumulate(const float* const* local, const float* const* global, con
   return FLC_OK;
 }
 
-int flc_ef_residual_round(const void* const* records, float* const* es, int n_clients, int64_t n, int64_t k,
-                          int levels, void* stream) {
+// flc_ef_residual_round (sparse_rec false: stacked records) and flc_ef_residual_sparse_round: one argument check, one
+// chain of launches of <= kMaxC clients
+static int ef_residual_impl(const char* fn, bool sparse_rec, const void* const* records, float* const* es,
+                            int n_clients, int64_t n, int64_t k, int levels, void* stream) {
   if (n_clients < 0 || (n_clients > 0 && (!records || !es)) || n < 0 || k < 0)
-    return fail(FLC_EINVAL, "flc_ef_residual_round: bad arguments");
-  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "flc_ef_residual_round: n and k must be < 2^31");
-  if (k > n) return fail(FLC_EINVAL, "flc_ef_residual_round: k %lld > n %lld", (long long)k, (long long)n);
-  if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "flc_ef_residual_round: levels must be in [1, 127]");
+    return fail(FLC_EINVAL, "%s: bad arguments", fn);
+  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
+  if (k > n) return fail(FLC_EINVAL, "%s: k %lld > n %lld", fn, (long long)k, (long long)n);
+  if (!sparse_rec && (levels < 1 || levels > 127)) return fail(FLC_EINVAL, "%s: levels must be in [1, 127]", fn);
   std::vector<std::pair<const float*, int>> owners;
   owners.reserve((size_t)n_clients);
   for (int c = 0; c < n_clients; ++c) {
     if (!records[c] || !aligned16(records[c]))
-      return fail(FLC_EINVAL, "flc_ef_residual_round: record %d is null or not 16-B aligned", c);
-    if (!es[c]) return fail(FLC_EINVAL, "flc_ef_residual_round: null memory for client %d", c);
+      return fail(FLC_EINVAL, "%s: record %d is null or not 16-B aligned", fn, c);
+    if (!es[c]) return fail(FLC_EINVAL, "%s: null memory for client %d", fn, c);
     owners.emplace_back(es[c], c);
   }
   std::sort(owners.begin(), owners.end());
   for (size_t i = 1; i < owners.size(); ++i)
     if (owners[i].first == owners[i - 1].first)
-      return fail(FLC_EINVAL, "flc_ef_residual_round: clients %d and %d share a memory",
+      return fail(FLC_EINVAL, "%s: clients %d and %d share a memory", fn,
                   std::min(owners[i - 1].second, owners[i].second), std::max(owners[i - 1].second, owners[i].second));
   if (n_clients == 0 || k == 0) return FLC_OK;
   int64_t off[4];
-  if (flc_stacked_wire_layout(n, k, off) == 0) return fail(FLC_EINVAL, "flc_ef_residual_round: bad arguments");
+  if ((sparse_rec ? flc_sparse_wire_layout(n, k, off) : flc_stacked_wire_layout(n, k, off)) == 0)
+    return fail(FLC_EINVAL, "%s: bad arguments", fn);
   hipStream_t st = as_stream(stream);
-  const double step = 1.0 / (double)levels;
+  const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   const unsigned gx = (unsigned)cdiv(k, (int64_t)kThreads * kPerThread);
   for (int c0 = 0; c0 < n_clients; c0 += kMaxC) {
     const int nc = std::min(n_clients - c0, kMaxC);
@@ -240,10 +279,24 @@ int flc_ef_residual_round(const void* const* records, float* const* es, int n_cl
       p.rec[c] = static_cast<const uint8_t*>(records[c0 + c]);
       p.e[c] = es[c0 + c];
     }
-    FLC_LAUNCH("ef_residual_round", ef_residual_round_kernel, dim3(gx, (unsigned)nc), dim3(kThreads), 0, st, p,
-               (long long)off[1], (long long)off[2], (unsigned)n, (unsigned)k, levels, step);
+    if (sparse_rec)
+      FLC_LAUNCH("ef_residual_sparse_round", ef_residual_sparse_round_kernel, dim3(gx, (unsigned)nc), dim3(kThreads), 0,
+                 st, p, (long long)off[0], (long long)off[1], (unsigned)n, (unsigned)k);
+    else
+      FLC_LAUNCH("ef_residual_round", ef_residual_round_kernel, dim3(gx, (unsigned)nc), dim3(kThreads), 0, st, p,
+                 (long long)off[1], (long long)off[2], (unsigned)n, (unsigned)k, levels, step);
   }
   return FLC_OK;
+}
+
+int flc_ef_residual_round(const void* const* records, float* const* es, int n_clients, int64_t n, int64_t k,
+                          int levels, void* stream) {
+  return ef_residual_impl("flc_ef_residual_round", false, records, es, n_clients, n, k, levels, stream);
+}
+
+int flc_ef_residual_sparse_round(const void* const* records, float* const* es, int n_clients, int64_t n, int64_t k,
+                                 void* stream) {
+  return ef_residual_impl("flc_ef_residual_sparse_round", true, records, es, n_clients, n, k, 0, stream);
 }
 
 int flc_ef_residual_dense(float* e, const float* c, int64_t n, void* stream) {

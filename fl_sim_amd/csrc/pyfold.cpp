@@ -7,6 +7,7 @@
 //   avg_and_gradient_records  flc_avg_and_gradient_records: the same over compressed gradients
 //   fold_records              flc_fedopt_fold_records: the server update of a round of stacked records
 //   fold_dense_records        flc_fedopt_fold_dense_records: the same for dense records
+//   fold_sparse_records       flc_fedopt_fold_sparse_records: the same for sparse (top-k / rand-k) records
 //   fold_record_groups        flc_fold_record_groups: a round of records folded into several models
 //   stacked_delta_record      flc_stacked_encode_delta into a wire record + flc_delta_count_nonzero_at
 //   stacked_records_round     flc_stacked_encode_round into the rows of a record block
@@ -638,7 +639,9 @@ PyObject* stacked_records_round(PyObject*, PyObject* args) {
 // not what the pass takes — the server tensors contiguous fp32 HIP tensors of one device summing to n, the records
 // 16-B aligned uint8 tensors of at least the wire layout's bytes on that device — so the caller can take its other
 // path; theta / v None: the fold alone / no second moment.
-// (format < 0: stacked records of (n, k, levels); else dense records of (n, format, levels, bits))
+// (format kStackedRecords: stacked records of (n, k, levels); kSparseRecords: sparse records of (n, k), the
+// flc_sparse_wire_layout(n, k) layout; else dense records of (n, format, levels, bits))
+constexpr int kStackedRecords = -1, kSparseRecords = -2;
 PyObject* fold_records_of(PyObject* recs, PyObject* weights, long long n, long long k, int format, int levels, int bits,
                           PyObject* delta, PyObject* theta, PyObject* v, double beta0, int opt, double lr, double beta2,
                           double tau) {
@@ -660,7 +663,9 @@ PyObject* fold_records_of(PyObject* recs, PyObject* weights, long long n, long l
   if (total != n) return type_error("the server tensors do not hold the records' element count");
   if (!optimizer_rows(refs, theta, v, nt, &dev, sz.data(), true, &tp, &vp)) return nullptr;
   int64_t off[4];
-  const size_t stride = format < 0 ? flc_stacked_wire_layout(n, k, off) : flc_dense_wire_layout(n, format, bits, off);
+  const size_t stride = format == kSparseRecords    ? flc_sparse_wire_layout(n, k, off)
+                        : format == kStackedRecords ? flc_stacked_wire_layout(n, k, off)
+                                                    : flc_dense_wire_layout(n, format, bits, off);
   if (stride == 0) return value_error("bad wire shape");
   std::vector<const void*> rp(nr);
   std::vector<float> w(nr);
@@ -671,7 +676,13 @@ PyObject* fold_records_of(PyObject* recs, PyObject* weights, long long n, long l
   }
   float* const* thp = tp.empty() ? nullptr : tp.data();
   float* const* vvp = vp.empty() ? nullptr : vp.data();
-  if (!on_device(dev, format < 0 ? "flc_fedopt_fold_records" : "flc_fedopt_fold_dense_records", [&](void* st) {
+  const char* fn = format == kSparseRecords    ? "flc_fedopt_fold_sparse_records"
+                   : format == kStackedRecords ? "flc_fedopt_fold_records"
+                                               : "flc_fedopt_fold_dense_records";
+  if (!on_device(dev, fn, [&](void* st) {
+        if (format == kSparseRecords)
+          return flc_fedopt_fold_sparse_records(rp.data(), w.data(), (int)nr, n, k, dp.data(), thp, vvp, sz.data(),
+                                                (int)nt, (float)beta0, opt, lr, beta2, tau, st);
         return format < 0 ? flc_fedopt_fold_records(rp.data(), w.data(), (int)nr, n, k, levels, dp.data(), thp, vvp,
                                                     sz.data(), (int)nt, (float)beta0, opt, lr, beta2, tau, st)
                           : flc_fedopt_fold_dense_records(rp.data(), w.data(), (int)nr, n, format, levels, bits, dp.data(),
@@ -689,7 +700,19 @@ PyObject* fold_records(PyObject*, PyObject* args) {
   if (!PyArg_ParseTuple(args, "OOLLiOOOdiddd", &recs, &weights, &n, &k, &levels, &delta, &theta, &v, &beta0, &opt, &lr,
                         &beta2, &tau))
     return nullptr;
-  return fold_records_of(recs, weights, n, k, -1, levels, 0, delta, theta, v, beta0, opt, lr, beta2, tau);
+  return fold_records_of(recs, weights, n, k, kStackedRecords, levels, 0, delta, theta, v, beta0, opt, lr, beta2, tau);
+}
+// fold_sparse_records(records, weights, n, k, delta, theta, v, beta0, opt, lr, beta2, tau): the same for a round of
+// sparse records (flc_fedopt_fold_sparse_records; the flc_sparse_wire_layout(n, k) layout of a top-k / rand-k message)
+PyObject* fold_sparse_records(PyObject*, PyObject* args) {
+  PyObject *recs, *weights, *delta, *theta, *v;
+  long long n, k;
+  int opt;
+  double beta0, lr, beta2, tau;
+  if (!PyArg_ParseTuple(args, "OOLLOOOdiddd", &recs, &weights, &n, &k, &delta, &theta, &v, &beta0, &opt, &lr, &beta2,
+                        &tau))
+    return nullptr;
+  return fold_records_of(recs, weights, n, k, kSparseRecords, 0, 0, delta, theta, v, beta0, opt, lr, beta2, tau);
 }
 // fold_dense_records(records, weights, n, format, levels, bits, delta, theta, v, beta0, opt, lr, beta2, tau): the same
 // for a round of dense records (flc_fedopt_fold_dense_records; the flc_dense_wire_layout(n, format, bits) layout)
@@ -881,6 +904,9 @@ PyMethodDef kMethods[] = {
     {"fold_dense_records", fold_dense_records, METH_VARARGS,
      "fold_dense_records(records, weights, n, format, levels, bits, delta, theta, v, beta0, opt, lr, beta2, tau): "
      "flc_fedopt_fold_dense_records on Python lists"},
+    {"fold_sparse_records", fold_sparse_records, METH_VARARGS,
+     "fold_sparse_records(records, weights, n, k, delta, theta, v, beta0, opt, lr, beta2, tau): "
+     "flc_fedopt_fold_sparse_records on Python lists"},
     {"fold_record_groups", fold_record_groups, METH_VARARGS,
      "fold_record_groups(records, weights, dsts, n, k, levels): flc_fold_record_groups on Python lists (one sequence "
      "per group)"},

@@ -10,6 +10,8 @@
 //                   first.  Algorithmic bytes: 4 per output element + 8 (top-k: idx+val) or 5 (stacked: idx+code)
 //                   per kept entry.
 //   randk_scatter   out[idx[j]] = fp32(D/K) * x[idx[j]] after a zero fill (compressors.py:289-291).
+//   sparse_gather   val[j] = fp32(D/K) * x[idx[j]]: the same products as a sparse record's val field
+//                   (flc_sparse_wire_layout), the zero fill and the dense vector left out.
 //   elementwise     identical (+x) and lazy (x / p) (compressors.py:273-283).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -229,6 +231,18 @@ __global__ __launch_bounds__(kThreads) void randk_scatter_kernel(const float* __
   }
 }
 
+// rand-k's kept values without the dense vector (compressors.py:289-291's D / K * x[i] at the kept i only): the one
+// fp32 multiply randk_scatter_kernel makes, written to the record's val field in idx order.  An index outside [0, n)
+// (unsigned compare: a negative one too) reads nothing and writes +0.
+__global__ __launch_bounds__(kThreads) void sparse_gather_kernel(const float* __restrict__ x, unsigned n,
+                                                                 const int* __restrict__ idx, long long k, float scale,
+                                                                 float* __restrict__ val) {
+  for (long long j = (long long)blockIdx.x * kThreads + threadIdx.x; j < k; j += (long long)gridDim.x * kThreads) {
+    const unsigned i = (unsigned)idx[j];
+    val[j] = i < n ? scale * x[i] : 0.0f;
+  }
+}
+
 // out = x / p (lazy) or out = x (identical, p == 1 handled as a copy): one short workgroup per 16 KB chunk (4 float4
 // per lane in flight, every load issued before the first store), the tail elements by the last workgroup.  (A
 // grid-stride form moving one float4 per lane per iteration copied 1 GiB at 5.2 TB/s.)
@@ -429,6 +443,16 @@ int flc_randk_apply(const float* x, int64_t n, const int32_t* idx, int64_t k, fl
   if (k == 0) return FLC_OK;
   const unsigned grid = (unsigned)std::min<int64_t>(cdiv(k, kThreads), 256 * 16);
   FLC_LAUNCH("randk_scatter", randk_scatter_kernel, dim3(grid), dim3(kThreads), 0, st, x, idx, (long long)k, scale, out);
+  return FLC_OK;
+}
+
+int flc_sparse_gather(const float* x, int64_t n, const int32_t* idx, int64_t k, float scale, float* val, void* stream) {
+  if (!x || n <= 0 || k < 0 || (k > 0 && (!idx || !val))) return fail(FLC_EINVAL, "flc_sparse_gather: bad arguments");
+  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "flc_sparse_gather: n and k must be < 2^31");
+  if (k == 0) return FLC_OK;
+  const unsigned grid = (unsigned)std::min<int64_t>(cdiv(k, kThreads), 256 * 16);
+  FLC_LAUNCH("sparse_gather", sparse_gather_kernel, dim3(grid), dim3(kThreads), 0, as_stream(stream), x, (unsigned)n,
+             idx, (long long)k, scale, val);
   return FLC_OK;
 }
 

@@ -2489,6 +2489,8 @@ size_t flc_topk_workspace_size(int64_t n, int64_t k) {
   return need;
 }
 
+// (idx, val and tiles inside a flc_sparse_wire_layout(n, k) record: the call writes the top-k compressor's sparse
+// record, compressors.py:293-296 — wire.hip folds a round of them)
 int flc_topk_encode_tiled(const float* x, int64_t n, int64_t k, int32_t* idx, float* val, uint32_t* tiles, void* ws,
                           size_t ws_bytes, void* stream) {
   if (int rc = check_topk(x, n, k, "flc_topk_encode")) return rc;
@@ -2620,6 +2622,8 @@ size_t flc_topk_encode_batch_workspace_size(int64_t n, int64_t k, int n_clients)
   return flc_stacked_encode_batch_workspace_size(n, k, n_clients);
 }
 
+// (idx[c], val[c] and tiles[c] inside client c's flc_sparse_wire_layout(n, k) record: a round's sparse records,
+// compressors.py:293-296 per client, in one call)
 int flc_topk_encode_batch(const float* const* xs, int n_clients, int64_t n, int64_t k, int32_t* const* idx,
                           float* const* val, uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream) {
   const char* who = "flc_topk_encode_batch";

@@ -29,6 +29,13 @@
 // dense parameters folded in the same pass) and flc_fold_record_groups (GroupIO: the launch's records fall into
 // groups, each folded in place into its own model — SCAFFOLD's two vectors, IFCA's clusters).
 //
+// Sparse records (flc_sparse_wire_layout): the plain sparsifiers' wire (top-k and rand-k, compressors.py:284-296) —
+// idx, the decoded fp32 values and the tile pointers — as the message's record.  Their fold is the stacked kernel with
+// another entry codec (StackedEntry: u8 code + the record's norm; SparseEntry: the fp32 value, no norm): the wave-per-
+// tile shape, the single load batch, the per-client loop, the tile-pointer clamps and the -0 rule are shared code.
+// flc_fold_sparse_wires (FlatIO), flc_fedopt_fold_sparse_records (ModelIO), flc_fold_sparse_record_groups (GroupIO)
+// and flc_avg_and_gradient_sparse_records (PairIO) share the stacked entry points' host code.
+//
 // Dense records (flc_dense_wire_layout): the dithering quantizers' and the natural compressor's wire — one fp32 norm
 // and the packed 2-, 4- or 8-bit codes, or one uint16 per element — as the message's record.  Their fold
 // (dense_fold_records_kernel, below the stacked one) shares the IO policies: one wave per tile, the accumulator in
@@ -82,6 +89,7 @@ __device__ __forceinline__ float skip_clients(float a, unsigned from, unsigned t
 // of the tile starting at flat element t0.
 struct FlatIO {  // one flat vector: out = fold (from +0, or from out itself)
   static constexpr bool kGrouped = false;
+  static constexpr bool kSparseForm = true;  // (the host may choose the kernel's sparse form for this accumulator)
   float* out;
   int64_t n;
   int acc_in;
@@ -138,6 +146,7 @@ struct ModelTab {
 template <int OPT>  // OPT < 0: the fold only (δ written, no step)
 struct ModelIO {
   static constexpr bool kGrouped = false;
+  static constexpr bool kSparseForm = false;  // (its launches take every element through every record's fma)
   ModelTab m;
   __device__ __forceinline__ int first_tensor(int64_t t0) const {
     int t = 0;
@@ -241,6 +250,7 @@ struct PairTab {
 };
 struct PairIO {
   static constexpr bool kGrouped = false;
+  static constexpr bool kSparseForm = true;
   PairTab m;
   __device__ __forceinline__ int first_tensor(int64_t t0) const {
     int t = 0;
@@ -336,6 +346,7 @@ struct GroupTab {
 };
 struct GroupIO {
   static constexpr bool kGrouped = true;
+  static constexpr bool kSparseForm = true;
   GroupTab m;
   __device__ __forceinline__ int first() const { return m.first[blockIdx.y]; }
   __device__ __forceinline__ int count() const { return m.count[blockIdx.y]; }
@@ -386,7 +397,31 @@ struct GroupIO {
   }
 };
 
-template <bool SPARSE, class IO>
+// What a kept entry's wire word is and what it decodes to (the fold kernel's entry codec).  Both records keep an
+// ascending int32 idx field and the CSR tile pointers; they differ in the word that travels with each index.
+struct StackedEntry {  // the stacked record: a u8 code at L.codes + j, dequantised with the record's norm
+  static __device__ __forceinline__ float norm(const uint8_t* rec, const WireLayout& L) {
+    return *reinterpret_cast<const float*>(rec + L.norm);
+  }
+  static __device__ __forceinline__ unsigned raw(const uint8_t* rc, const WireLayout& L, unsigned j) {
+    return rc[L.codes + j];
+  }
+  static __device__ __forceinline__ float value(unsigned raw, int levels, double step, float nrm) {
+    return stacked_dequant(raw, levels, step, nrm);  // compressors.py:357
+  }
+};
+// The sparse record (flc_sparse_wire_layout: the top-k / rand-k wire of compressors.py:284-296): the decoded fp32
+// value itself at L.codes + 4 j (the layout's val field travels in WireLayout::codes), no norm — sparse.hip's
+// entry_value<0> at scale 1.
+struct SparseEntry {
+  static __device__ __forceinline__ float norm(const uint8_t*, const WireLayout&) { return 0.0f; }
+  static __device__ __forceinline__ unsigned raw(const uint8_t* rc, const WireLayout& L, unsigned j) {
+    return reinterpret_cast<const unsigned*>(rc + L.codes)[j];
+  }
+  static __device__ __forceinline__ float value(unsigned raw, int, double, float) { return __uint_as_float(raw); }
+};
+
+template <bool SPARSE, class IO, class EC = StackedEntry>
 __global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, WireLayout L, int nw_all, int levels,
                                                                    double step, int64_t tile0, IO io, unsigned k) {
   __shared__ __attribute__((aligned(16))) float s_tile[FLC_TILE];
@@ -422,7 +457,7 @@ __global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, W
     lo = min(tiles[t], k);
     const unsigned hi = min(tiles[t + 1], k);
     cnt = hi > lo ? hi - lo : 0u;
-    nrm = *reinterpret_cast<const float*>(rec + L.norm);
+    nrm = EC::norm(rec, L);
   }
   const unsigned long long pos = __ballot(lane < nw && !std::signbit(wl));  // sign-clear weights (sparse: -0 rule)
   const unsigned incl = wave_incl_scan(cnt);
@@ -461,7 +496,7 @@ __global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, W
         const uint8_t* rc = reinterpret_cast<const uint8_t*>((uintptr_t)(((unsigned long long)rhi << 32) | rlo));
         const unsigned j = lo_c + ((unsigned)lane + (unsigned)(r * kWave) - ex_c);
         idx_raw[r] = reinterpret_cast<const unsigned*>(rc + L.idx)[j];
-        code[r] = rc[L.codes + j];
+        code[r] = EC::raw(rc, L, j);
       }
     }
 #pragma unroll
@@ -469,7 +504,7 @@ __global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, W
       const int64_t o = (int64_t)idx_raw[r] - t0;
       if (cg[r] >= 0 && (o < 0 || o >= FLC_TILE)) cg[r] = -1;  // (a malformed wire: ignored, never out of the tile)
       off[r] = (unsigned)(o < 0 ? 0 : (o >= FLC_TILE ? 0 : o));
-      val[r] = stacked_dequant(code[r], levels, step, nr[r]);
+      val[r] = EC::value(code[r], levels, step, nr[r]);
     }
     if (SPARSE) {
       // the accumulator in LDS, updated at the kept entries only (see the launch: +0 start, finite weights, so
@@ -525,12 +560,11 @@ __global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, W
       const unsigned rhi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(rp >> 32), c);
       const uint8_t* rc = reinterpret_cast<const uint8_t*>((uintptr_t)(((unsigned long long)rhi << 32) | rlo));
       const unsigned* ix = reinterpret_cast<const unsigned*>(rc + L.idx);
-      const uint8_t* cd = rc + L.codes;
       if (SPARSE) {
         for (unsigned j = lo_c + lane; j < lo_c + n_c; j += kWave) {
           const int64_t o = (int64_t)ix[j] - t0;
           if (o >= 0 && o < FLC_TILE) {
-            s_tile[o] = fmaf(wc, stacked_dequant(cd[j], levels, step, nr_c),
+            s_tile[o] = fmaf(wc, EC::value(EC::raw(rc, L, j), levels, step, nr_c),
                              skip_clients(s_tile[o], s_last[o], (unsigned)c, pos));
             s_last[o] = (uint8_t)(c + 1);
           }
@@ -541,7 +575,7 @@ __global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, W
       }
       for (unsigned j = lo_c + lane; j < lo_c + n_c; j += kWave) {
         const int64_t o = (int64_t)ix[j] - t0;
-        if (o >= 0 && o < FLC_TILE) s_tile[o] = stacked_dequant(cd[j], levels, step, nr_c);
+        if (o >= 0 && o < FLC_TILE) s_tile[o] = EC::value(EC::raw(rc, L, j), levels, step, nr_c);
       }
       __builtin_amdgcn_wave_barrier();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -734,6 +768,54 @@ int check_dense_format(const char* fn, int format, int levels, int bits) {
   return FLC_OK;
 }
 
+// The sparsifiers' record (flc_sparse_wire_layout): idx int32[k] ascending, val fp32[k] (the decoded values), tiles —
+// the stacked record without its norm, its codes widened to the values.  WireLayout::codes is the val field.
+WireLayout sparse_wire_layout(int64_t n, int64_t k, size_t* total) {
+  WireLayout L;
+  L.norm = 0;  // (no norm: SparseEntry reads none)
+  L.idx = 0;
+  L.codes = (long long)align_up((size_t)(4 * k), 16);
+  L.tiles = (long long)align_up((size_t)L.codes + (size_t)(4 * k), 16);
+  const int64_t ntiles = cdiv(n < 1 ? 1 : n, (int64_t)FLC_TILE);
+  *total = align_up((size_t)L.tiles + 4 * (size_t)(ntiles + 1), 256);
+  return L;
+}
+
+enum RecordKind { kRecStacked = 0, kRecSparse = 1 };  // the entry records' two codecs (StackedEntry / SparseEntry)
+
+WireLayout record_layout(RecordKind kind, int64_t n, int64_t k, size_t* total) {
+  return kind == kRecSparse ? sparse_wire_layout(n, k, total) : wire_layout(n, k, total);
+}
+
+// the codec's own argument rule: a stacked record's levels, a sparse record's 1 <= k <= n (the layout's domain)
+int check_entry_codec(const char* fn, RecordKind kind, int64_t n, int64_t k, int levels) {
+  if (kind == kRecSparse) {
+    if (k < 1 || k > n) return fail(FLC_EINVAL, "%s: k %lld outside [1, n = %lld]", fn, (long long)k, (long long)n);
+    return FLC_OK;
+  }
+  if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "%s: levels must be in [1, 127]", fn);
+  return FLC_OK;
+}
+
+// one launch of the entry-record fold: the kernel by (sparse form, accumulator policy, entry codec)
+template <class IO>
+int launch_entry_fold(const char* probe, RecordKind kind, bool sparse, dim3 grid, hipStream_t st, const FoldArgs& a,
+                      const WireLayout& L, int nw, int levels, double step, int64_t tile0, const IO& io, unsigned k) {
+#define FLC_EF(S, EC)                                                                                              \
+  do {                                                                                                             \
+    FLC_LAUNCH(probe, (stacked_fold_wires_kernel<S, IO, EC>), grid, dim3(kWave), 0, st, a, L, nw, levels, step, tile0, \
+               io, k);                                                                                             \
+    return FLC_OK;                                                                                                 \
+  } while (0)
+  if constexpr (IO::kSparseForm) {
+    if (sparse && kind == kRecSparse) FLC_EF(true, SparseEntry);
+    if (sparse) FLC_EF(true, StackedEntry);
+  }
+  if (kind == kRecSparse) FLC_EF(false, SparseEntry);
+  FLC_EF(false, StackedEntry);
+#undef FLC_EF
+}
+
 }  // namespace
 }  // namespace flc
 
@@ -754,23 +836,37 @@ size_t flc_stacked_wire_layout(int64_t n, int64_t k, int64_t* offsets) {
   return total;
 }
 
-int flc_stacked_fold_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
-                           int64_t n, int64_t k, int levels, int accumulate, float* out, void* stream) {
+size_t flc_sparse_wire_layout(int64_t n, int64_t k, int64_t* offsets) {
+  if (n < 1 || k < 1 || k > n || n >= (1ll << 31) || k >= (1ll << 31)) return 0;
+  size_t total = 0;
+  const WireLayout L = sparse_wire_layout(n, k, &total);
+  if (offsets) {
+    offsets[0] = L.idx;
+    offsets[1] = L.codes;  // (val)
+    offsets[2] = L.tiles;
+  }
+  return total;
+}
+
+// flc_stacked_fold_wires (kRecStacked) and flc_fold_sparse_wires (kRecSparse): one argument check, one chain of
+// launches, the kernel's entry codec by the records' kind
+static int fold_wires_impl(const char* fn, const char* probe, RecordKind kind, const void* wires, int64_t stride,
+                           const int32_t* slots, const float* weights, int n_wires, int64_t n, int64_t k, int levels,
+                           int accumulate, float* out, void* stream) {
   if (!wires || !slots || !weights || !out || n_wires < 1 || n <= 0 || k < 0)
-    return fail(FLC_EINVAL, "flc_stacked_fold_wires: bad arguments");
-  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "flc_stacked_fold_wires: n and k must be < 2^31");
-  if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "flc_stacked_fold_wires: levels must be in [1, 127]");
+    return fail(FLC_EINVAL, "%s: bad arguments", fn);
+  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
+  if (int rc = check_entry_codec(fn, kind, n, k, levels)) return rc;
   size_t need = 0;
-  const WireLayout L = wire_layout(n, k, &need);
+  const WireLayout L = record_layout(kind, n, k, &need);
   if (stride < (int64_t)need || stride % 16 != 0)
-    return fail(FLC_EINVAL, "flc_stacked_fold_wires: stride %lld < record size %zu (or not 16-B aligned)",
-                (long long)stride, need);
-  if (!aligned16(wires) || !aligned16(out)) return fail(FLC_EINVAL, "flc_stacked_fold_wires: 16-B aligned buffers required");
+    return fail(FLC_EINVAL, "%s: stride %lld < record size %zu (or not 16-B aligned)", fn, (long long)stride, need);
+  if (!aligned16(wires) || !aligned16(out)) return fail(FLC_EINVAL, "%s: 16-B aligned buffers required", fn);
   for (int c = 0; c < n_wires; ++c)
-    if (slots[c] < 0) return fail(FLC_EINVAL, "flc_stacked_fold_wires: slot %d is negative", c);
+    if (slots[c] < 0) return fail(FLC_EINVAL, "%s: slot %d is negative", fn, c);
   hipStream_t st = as_stream(stream);
   const int64_t ntiles = cdiv(n, (int64_t)FLC_TILE);
-  const double step = 1.0 / (double)levels;
+  const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   // Sparse fold (from +0, finite weights): only the kept entries are fma'd, and a final -0 is resolved as the dense
   // chain would (kernel header).  Otherwise (accumulating into a given vector, or a non-finite weight) every element
   // takes every client's fma.
@@ -784,20 +880,31 @@ int flc_stacked_fold_wires(const void* wires, int64_t stride, const int32_t* slo
       a.rec[c] = static_cast<const uint8_t*>(wires) + (c < nw ? (int64_t)slots[c0 + c] * stride : 0);
     }
     const FlatIO io{out, n, (c0 > 0 || accumulate) ? 1 : 0};
-    if (sparse)
-      FLC_LAUNCH("stacked_fold_wires", (stacked_fold_wires_kernel<true, FlatIO>), dim3((unsigned)ntiles), dim3(kWave), 0,
-                 st, a, L, nw, levels, step, (int64_t)0, io, (unsigned)k);
-    else
-      FLC_LAUNCH("stacked_fold_wires", (stacked_fold_wires_kernel<false, FlatIO>), dim3((unsigned)ntiles), dim3(kWave),
-                 0, st, a, L, nw, levels, step, (int64_t)0, io, (unsigned)k);
+    if (int rc = launch_entry_fold(probe, kind, sparse, dim3((unsigned)ntiles), st, a, L, nw, levels, step, (int64_t)0,
+                                   io, (unsigned)k))
+      return rc;
   }
   return FLC_OK;
 }
 
-// flc_fedopt_fold_records (dense == NULL: stacked records of (n, k, levels)) and flc_fedopt_fold_dense_records (the
-// records of *dense): one argument check, one chain of launches, the kernel by the records' codec.  `fn` names the
-// entry point in messages, `probe` its launches for flc_probe_set.
-static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec* dense, const void* const* records,
+int flc_stacked_fold_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
+                           int64_t n, int64_t k, int levels, int accumulate, float* out, void* stream) {
+  return fold_wires_impl("flc_stacked_fold_wires", "stacked_fold_wires", kRecStacked, wires, stride, slots, weights,
+                         n_wires, n, k, levels, accumulate, out, stream);
+}
+
+int flc_fold_sparse_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
+                          int64_t n, int64_t k, int accumulate, float* out, void* stream) {
+  return fold_wires_impl("flc_fold_sparse_wires", "fold_sparse_wires", kRecSparse, wires, stride, slots, weights,
+                         n_wires, n, k, 0, accumulate, out, stream);
+}
+
+// flc_fedopt_fold_records (dense == NULL, kRecStacked: stacked records of (n, k, levels)), flc_fedopt_fold_sparse_records
+// (dense == NULL, kRecSparse: sparse records of (n, k)) and flc_fedopt_fold_dense_records (the records of *dense): one
+// argument check, one chain of launches, the kernel by the records' codec.  `fn` names the entry point in messages,
+// `probe` its launches for flc_probe_set.
+static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec* dense, RecordKind kind,
+                            const void* const* records,
                             const float* weights, int n_records, int64_t n, int64_t k, int levels,
                             float* const* delta, float* const* theta, float* const* v, const int64_t* sizes,
                             int n_tensors, float beta0, int opt, double lr, double beta2, double tau, void* stream) {
@@ -807,8 +914,8 @@ static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec*
   if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
   if (dense) {
     if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
-  } else if (levels < 1 || levels > 127) {
-    return fail(FLC_EINVAL, "%s: levels must be in [1, 127]", fn);
+  } else if (int rc = check_entry_codec(fn, kind, n, k, levels)) {
+    return rc;
   }
   const bool step_on = theta != nullptr;
   if (step_on && opt != FLC_OPT_AVG && opt != FLC_OPT_ADAGRAD && opt != FLC_OPT_YOGI && opt != FLC_OPT_ADAM)
@@ -828,7 +935,7 @@ static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec*
     if (!records[c] || !aligned16(records[c]))
       return fail(FLC_EINVAL, "%s: record %d is null or not 16-B aligned", fn, c);
   size_t need = 0;
-  const WireLayout L = wire_layout(n, k, &need);
+  const WireLayout L = record_layout(kind, n, k, &need);
   hipStream_t st = as_stream(stream);
   const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   const float omb = (float)(1.0 - beta2), nomb = (float)(-(1.0 - beta2));
@@ -874,9 +981,9 @@ static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec*
   do {                                                                                                            \
     if (dense) {                                                                                                  \
       if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, ModelIO<O>{m})) return rc;          \
-    } else {                                                                                                      \
-      FLC_LAUNCH(probe, (stacked_fold_wires_kernel<false, ModelIO<O>>), grid, dim3(kWave), 0, st, a, L, nw, levels, \
-                 step, tile_lo, ModelIO<O>{m}, (unsigned)k);                                                      \
+    } else if (int rc = launch_entry_fold(probe, kind, false, grid, st, a, L, nw, levels, step, tile_lo,          \
+                                          ModelIO<O>{m}, (unsigned)k)) {                                          \
+      return rc;                                                                                                  \
     }                                                                                                             \
   } while (0)
       if (!step_on || !last) FLC_FR(-1);
@@ -895,8 +1002,17 @@ int flc_fedopt_fold_records(const void* const* records, const float* weights, in
                             int levels, float* const* delta, float* const* theta, float* const* v,
                             const int64_t* sizes, int n_tensors, float beta0, int opt, double lr, double beta2,
                             double tau, void* stream) {
-  return fedopt_fold_impl("flc_fedopt_fold_records", "fedopt_fold_records", nullptr, records, weights, n_records, n, k,
-                          levels, delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau, stream);
+  return fedopt_fold_impl("flc_fedopt_fold_records", "fedopt_fold_records", nullptr, kRecStacked, records, weights,
+                          n_records, n, k, levels, delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau, stream);
+}
+
+int flc_fedopt_fold_sparse_records(const void* const* records, const float* weights, int n_records, int64_t n,
+                                   int64_t k, float* const* delta, float* const* theta, float* const* v,
+                                   const int64_t* sizes, int n_tensors, float beta0, int opt, double lr, double beta2,
+                                   double tau, void* stream) {
+  return fedopt_fold_impl("flc_fedopt_fold_sparse_records", "fedopt_fold_sparse_records", nullptr, kRecSparse, records,
+                          weights, n_records, n, k, 0, delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau,
+                          stream);
 }
 
 int flc_fedopt_fold_dense_records(const void* const* records, const float* weights, int n_records, int64_t n,
@@ -904,44 +1020,45 @@ int flc_fedopt_fold_dense_records(const void* const* records, const float* weigh
                                   float* const* v, const int64_t* sizes, int n_tensors, float beta0, int opt,
                                   double lr, double beta2, double tau, void* stream) {
   const DenseCodec cd{format, levels, bits, n};
-  return fedopt_fold_impl("flc_fedopt_fold_dense_records", "fedopt_fold_dense_records", &cd, records, weights,
-                          n_records, n, 0, levels, delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau,
+  return fedopt_fold_impl("flc_fedopt_fold_dense_records", "fedopt_fold_dense_records", &cd, kRecStacked, records,
+                          weights, n_records, n, 0, levels, delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau,
                           stream);
 }
 
-int flc_avg_and_gradient_records(float* const* params, float* const* grads, const float* const* param_srcs,
-                                 const void* const* grad_records, const float* w_params, const float* w_grads,
-                                 int n_src, int64_t n, int64_t k, int levels, const int64_t* sizes, int n_tensors,
-                                 float inertia, void* stream) {
+// flc_avg_and_gradient_records (kRecStacked) and flc_avg_and_gradient_sparse_records (kRecSparse), as fedopt_fold_impl
+// serves the FedOpt folds
+static int avg_and_gradient_impl(const char* fn, const char* probe, RecordKind kind, float* const* params,
+                                 float* const* grads, const float* const* param_srcs, const void* const* grad_records,
+                                 const float* w_params, const float* w_grads, int n_src, int64_t n, int64_t k,
+                                 int levels, const int64_t* sizes, int n_tensors, float inertia, void* stream) {
   const bool p_on = param_srcs != nullptr;
   if (n_src < 1 || !grad_records || !w_grads || n <= 0 || k < 0 || n_tensors < 1 || !grads || !sizes ||
       (p_on && (!params || !w_params)))
-    return fail(FLC_EINVAL, "flc_avg_and_gradient_records: bad arguments");
+    return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (n >= (1ll << 31) || k >= (1ll << 31))
-    return fail(FLC_EINVAL, "flc_avg_and_gradient_records: n and k must be < 2^31");
-  if (levels < 1 || levels > 127)
-    return fail(FLC_EINVAL, "flc_avg_and_gradient_records: levels must be in [1, 127]");
+    return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
+  if (int rc = check_entry_codec(fn, kind, n, k, levels)) return rc;
   int64_t total = 0;
   for (int t = 0; t < n_tensors; ++t) {
-    if (sizes[t] < 0) return fail(FLC_EINVAL, "flc_avg_and_gradient_records: negative size for tensor %d", t);
+    if (sizes[t] < 0) return fail(FLC_EINVAL, "%s: negative size for tensor %d", fn, t);
     if (sizes[t] > 0 && (!grads[t] || (p_on && !params[t])))
-      return fail(FLC_EINVAL, "flc_avg_and_gradient_records: null pointer for tensor %d", t);
+      return fail(FLC_EINVAL, "%s: null pointer for tensor %d", fn, t);
     if (p_on && sizes[t] > 0)
       for (int m = 0; m < n_src; ++m)
         if (!param_srcs[(size_t)m * n_tensors + t])
-          return fail(FLC_EINVAL, "flc_avg_and_gradient_records: null source %d of tensor %d", m, t);
+          return fail(FLC_EINVAL, "%s: null source %d of tensor %d", fn, m, t);
     total += sizes[t];
   }
   if (total != n)
-    return fail(FLC_EINVAL, "flc_avg_and_gradient_records: the tensors hold %lld elements, the records %lld",
+    return fail(FLC_EINVAL, "%s: the tensors hold %lld elements, the records %lld", fn,
                 (long long)total, (long long)n);
   for (int c = 0; c < n_src; ++c)
     if (!grad_records[c] || !aligned16(grad_records[c]))
-      return fail(FLC_EINVAL, "flc_avg_and_gradient_records: record %d is null or not 16-B aligned", c);
+      return fail(FLC_EINVAL, "%s: record %d is null or not 16-B aligned", fn, c);
   size_t need = 0;
-  const WireLayout L = wire_layout(n, k, &need);
+  const WireLayout L = record_layout(kind, n, k, &need);
   hipStream_t st = as_stream(stream);
-  const double step = 1.0 / (double)levels;
+  const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   // the gradient chain starts at +0: with finite weights only the kept entries are fma'd (the sparse form, its -0
   // rule as in flc_stacked_fold_wires); a non-finite weight takes every element through every record's fma
   bool sparse = true;
@@ -990,20 +1107,35 @@ int flc_avg_and_gradient_records(float* const* params, float* const* grads, cons
       m.start[m.nt] = off;
       const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
       const dim3 grid((unsigned)(tile_hi - tile_lo));
-      if (sparse)
-        FLC_LAUNCH("avg_and_gradient_records", (stacked_fold_wires_kernel<true, PairIO>), grid, dim3(kWave), 0, st, a,
-                   L, nw, levels, step, tile_lo, io, (unsigned)k);
-      else
-        FLC_LAUNCH("avg_and_gradient_records", (stacked_fold_wires_kernel<false, PairIO>), grid, dim3(kWave), 0, st,
-                   a, L, nw, levels, step, tile_lo, io, (unsigned)k);
+      if (int rc = launch_entry_fold(probe, kind, sparse, grid, st, a, L, nw, levels, step, tile_lo, io, (unsigned)k))
+        return rc;
     }
   }
   return FLC_OK;
 }
 
-// flc_fold_record_groups (dense == NULL) and flc_fold_dense_record_groups (the records of *dense), as
-// fedopt_fold_impl serves the two FedOpt folds
-static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec* dense, const void* const* records,
+int flc_avg_and_gradient_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                 const void* const* grad_records, const float* w_params, const float* w_grads,
+                                 int n_src, int64_t n, int64_t k, int levels, const int64_t* sizes, int n_tensors,
+                                 float inertia, void* stream) {
+  return avg_and_gradient_impl("flc_avg_and_gradient_records", "avg_and_gradient_records", kRecStacked, params, grads,
+                               param_srcs, grad_records, w_params, w_grads, n_src, n, k, levels, sizes, n_tensors,
+                               inertia, stream);
+}
+
+int flc_avg_and_gradient_sparse_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                        const void* const* grad_records, const float* w_params, const float* w_grads,
+                                        int n_src, int64_t n, int64_t k, const int64_t* sizes, int n_tensors,
+                                        float inertia, void* stream) {
+  return avg_and_gradient_impl("flc_avg_and_gradient_sparse_records", "avg_and_gradient_sparse_records", kRecSparse,
+                               params, grads, param_srcs, grad_records, w_params, w_grads, n_src, n, k, 0, sizes,
+                               n_tensors, inertia, stream);
+}
+
+// flc_fold_record_groups (dense == NULL, kRecStacked), flc_fold_sparse_record_groups (dense == NULL, kRecSparse) and
+// flc_fold_dense_record_groups (the records of *dense), as fedopt_fold_impl serves the FedOpt folds
+static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec* dense, RecordKind kind,
+                            const void* const* records,
                             const float* weights, const int32_t* group_of, int n_records, int64_t n, int64_t k,
                             int levels, float* const* dsts, int n_groups, const int64_t* sizes, int n_tensors,
                             void* stream) {
@@ -1013,8 +1145,8 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
   if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
   if (dense) {
     if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
-  } else if (levels < 1 || levels > 127) {
-    return fail(FLC_EINVAL, "%s: levels must be in [1, 127]", fn);
+  } else if (int rc = check_entry_codec(fn, kind, n, k, levels)) {
+    return rc;
   }
   int64_t total = 0;
   for (int t = 0; t < n_tensors; ++t) {
@@ -1050,7 +1182,7 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
                   owners[i].second);
   if (n_records == 0) return FLC_OK;
   size_t need = 0;
-  const WireLayout L = wire_layout(n, k, &need);
+  const WireLayout L = record_layout(kind, n, k, &need);
   hipStream_t st = as_stream(stream);
   const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   // the records ordered by group, each group's in message order
@@ -1110,12 +1242,9 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
       const dim3 grid((unsigned)(tile_hi - tile_lo), (unsigned)ng);
       if (dense) {
         if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, io)) return rc;
-      } else if (sparse) {
-        FLC_LAUNCH(probe, (stacked_fold_wires_kernel<true, GroupIO>), grid, dim3(kWave), 0, st, a, L, nw, levels, step,
-                   tile_lo, io, (unsigned)k);
-      } else {
-        FLC_LAUNCH(probe, (stacked_fold_wires_kernel<false, GroupIO>), grid, dim3(kWave), 0, st, a, L, nw, levels,
-                   step, tile_lo, io, (unsigned)k);
+      } else if (int rc = launch_entry_fold(probe, kind, sparse, grid, st, a, L, nw, levels, step, tile_lo, io,
+                                            (unsigned)k)) {
+        return rc;
       }
     }
     c0 += nw;
@@ -1126,16 +1255,23 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
 int flc_fold_record_groups(const void* const* records, const float* weights, const int32_t* group_of, int n_records,
                            int64_t n, int64_t k, int levels, float* const* dsts, int n_groups, const int64_t* sizes,
                            int n_tensors, void* stream) {
-  return fold_groups_impl("flc_fold_record_groups", "fold_record_groups", nullptr, records, weights, group_of,
-                          n_records, n, k, levels, dsts, n_groups, sizes, n_tensors, stream);
+  return fold_groups_impl("flc_fold_record_groups", "fold_record_groups", nullptr, kRecStacked, records, weights,
+                          group_of, n_records, n, k, levels, dsts, n_groups, sizes, n_tensors, stream);
+}
+
+int flc_fold_sparse_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
+                                  int n_records, int64_t n, int64_t k, float* const* dsts, int n_groups,
+                                  const int64_t* sizes, int n_tensors, void* stream) {
+  return fold_groups_impl("flc_fold_sparse_record_groups", "fold_sparse_record_groups", nullptr, kRecSparse, records,
+                          weights, group_of, n_records, n, k, 0, dsts, n_groups, sizes, n_tensors, stream);
 }
 
 int flc_fold_dense_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
                                  int n_records, int64_t n, int format, int levels, int bits, float* const* dsts,
                                  int n_groups, const int64_t* sizes, int n_tensors, void* stream) {
   const DenseCodec cd{format, levels, bits, n};
-  return fold_groups_impl("flc_fold_dense_record_groups", "fold_dense_record_groups", &cd, records, weights, group_of,
-                          n_records, n, 0, levels, dsts, n_groups, sizes, n_tensors, stream);
+  return fold_groups_impl("flc_fold_dense_record_groups", "fold_dense_record_groups", &cd, kRecStacked, records, weights,
+                          group_of, n_records, n, 0, levels, dsts, n_groups, sizes, n_tensors, stream);
 }
 
 size_t flc_dense_wire_layout(int64_t n, int format, int bits, int64_t* offsets) {

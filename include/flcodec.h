@@ -210,6 +210,8 @@ int flc_topk_encode(const float* x, int64_t n, int64_t k, int32_t* idx, float* v
  * them from idx alone. */
 #define FLC_TILE 1024
 int flc_tile_index(const int32_t* idx, int64_t k, int64_t n, uint32_t* tiles, void* stream);
+/* flc_topk_encode_tiled writes a sparse record (flc_sparse_wire_layout(n, k), below) when idx, val and tiles are the
+ * three pointers inside it. */
 int flc_topk_encode_tiled(const float* x, int64_t n, int64_t k, int32_t* idx, float* val, uint32_t* tiles,
                           void* ws, size_t ws_bytes, void* stream);
 /* dense decode of an ascending sparse stream: out[idx[j]] = scale * val[j], zeros elsewhere
@@ -292,6 +294,48 @@ int flc_fedopt_fold_records(const void* const* records, const float* weights, in
 int flc_fold_record_groups(const void* const* records, const float* weights, const int32_t* group_of, int n_records,
                            int64_t n, int64_t k, int levels, float* const* dsts /* [n_groups][n_tensors] */,
                            int n_groups, const int64_t* sizes, int n_tensors, void* stream);
+
+/* ------------------------------------------------------------------ sparse records (top-k / rand-k wire)
+ * One client's top-k or rand-k wire (compressors.py:284-296) as ONE contiguous record, the plain sparsifiers'
+ * counterpart of the stacked record above: what a message carries in place of the 4 n bytes of the decoded vector
+ * compressVector returns.  Returns the record size (a multiple of 256 B; 0 for bad arguments: n < 1, k < 1, k > n, n or
+ * k >= 2^31) and, if offsets != NULL, the byte offsets of
+ * offsets[0] idx (int32[k], ascending), [1] val (fp32[k]: the DECODED values, so for rand-k already scale * x[idx],
+ * compressors.py:290-291), [2] tiles (u32[ceil(n/FLC_TILE)+1], the stacked record's CSR pointers); every field 16-B
+ * aligned.  The layout depends on (n, k) only.  decode(record) is flc_sparse_decode_tiled(idx, val, k, scale = 1, n,
+ * ..., tiles).  flc_topk_encode_tiled and flc_topk_encode_batch write a record when given the three pointers inside it;
+ * a rand-k record is its ascending index set, flc_sparse_gather's values and flc_tile_index's (or the key select's)
+ * tiles. */
+size_t flc_sparse_wire_layout(int64_t n, int64_t k, int64_t* offsets);
+/* flc_stacked_fold_wires' contract over sparse records (the server's weighted aggregation, nodes.py:1165-1180 /
+ * _fedopt.py:202-208, fused with the decode of compressors.py:289-291 / 294-295):
+ *   out = (accumulate ? out : +0);  for c = 0 .. n_wires-1:  out = fmaf(weights[c], decode(record slots[c]), out)
+ * elementwise, in that order — bit-identical to n_wires flc_sparse_decode_tiled(scale 1, weight = w_c, accumulate = 1)
+ * calls on a zeroed (or the given) out: fmaf(w, +0, a) on the elements no entry names (a -0 accumulator included),
+ * +-inf and NaN accumulators, weights of either sign, zero or denormal, kept values that are -0, denormal, +-inf or NaN.
+ * The stacked fold's kernel with the fp32 value as its entry codec: one wave per tile, one load batch for tiles of
+ * <= 128 entries over all clients, every tile pointer clamped to k, an index outside its tile ignored.  wires, stride,
+ * slots, weights and the chaining past 64 records as flc_stacked_fold_wires'.  FLC_EINVAL (nothing launched): its
+ * cases, with k outside [1, n] in place of the levels. */
+int flc_fold_sparse_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
+                          int64_t n, int64_t k, int accumulate, float* out, void* stream);
+/* flc_fedopt_fold_records' contract over sparse records (replaces FedOptServer.update, _fedopt.py:196-240, when each
+ * client message carries its delta as a sparse record in place of compressors.py:284-296's decoded vector):
+ *   a = delta * beta0;  for c = 0 .. n_records-1:  a = fmaf(weights[c], decode(records[c]), a);  delta = a;
+ *   then, if theta != NULL, the optimiser's step (avg / adagrad / yogi / adam, as flc_model_fold).
+ * Bit-identical to decoding every record densely (flc_sparse_decode_tiled) and running flc_model_fold with init_mode 0
+ * and the step.  Arguments as flc_fedopt_fold_records' without levels; k in [1, n]. */
+int flc_fedopt_fold_sparse_records(const void* const* records, const float* weights, int n_records, int64_t n,
+                                   int64_t k, float* const* delta, float* const* theta, float* const* v,
+                                   const int64_t* sizes, int n_tensors, float beta0, int opt, double lr, double beta2,
+                                   double tau, void* stream);
+/* flc_fold_record_groups' contract over sparse records (add_parameters' in-place accumulation per group,
+ * nodes.py:1116-1132; SCAFFOLD's two vectors, _scaffold.py:160-169, IFCA's clusters, _ifca.py:186-195): bit-identical
+ * to decoding every record densely and calling flc_weighted_sum(init_mode 2) per group and tensor.  Arguments, chaining
+ * and FLC_EINVAL cases as flc_fold_record_groups' without levels; k in [1, n]. */
+int flc_fold_sparse_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
+                                  int n_records, int64_t n, int64_t k, float* const* dsts /* [n_groups][n_tensors] */,
+                                  int n_groups, const int64_t* sizes, int n_tensors, void* stream);
 
 /* ------------------------------------------------------------------ dense records (dithering / natural wire)
  * One client's dithering or natural-compressor wire as ONE contiguous record, the dense quantizers' counterpart of the
@@ -418,7 +462,8 @@ int flc_stacked_encode_batch(const float* const* xs, int n_clients, int64_t n, i
 
 /* plain top-k of many clients in one launch (compressors.py:293-296 per client): client c's (idx, val, tiles) equal
  * flc_topk_encode_tiled(xs[c], n, k, ...); arrays and workspace as in flc_stacked_encode_batch (the two share a
- * workspace size). */
+ * workspace size).  The three pointers inside a sparse record (flc_sparse_wire_layout(n, k)) make client c's record: a
+ * round's records in one call. */
 size_t flc_topk_encode_batch_workspace_size(int64_t n, int64_t k, int n_clients);
 int flc_topk_encode_batch(const float* const* xs, int n_clients, int64_t n, int64_t k, int32_t* const* idx,
                           float* const* val, uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream);
@@ -466,6 +511,11 @@ int flc_randk_apply(const float* x, int64_t n, const int32_t* idx, int64_t k, fl
  * fp32 bit pattern; the K largest keys (flc_topk_encode_tiled on keys) are a uniformly random K-subset, ascending.
  * keys must be 16-B aligned. */
 int flc_randk_keys(int64_t n, uint64_t seed, uint64_t counter, float* keys, void* stream);
+/* rand-k's kept values without the dense vector (compressors.py:289-291 at the kept indices only): val[j] = scale *
+ * x[idx[j]], one fp32 multiply — bit-equal to what flc_randk_apply scatters to out[idx[j]]; the val field of a sparse
+ * record (flc_sparse_wire_layout).  An index outside [0, n) writes +0 and reads nothing.  FLC_EINVAL: a null pointer,
+ * n < 1, k < 0, n or k >= 2^31.  k == 0: nothing launched. */
+int flc_sparse_gather(const float* x, int64_t n, const int32_t* idx, int64_t k, float scale, float* val, void* stream);
 
 /* ------------------------------------------------------------------ float64 inputs (f64.hip)
  * The reference runs every compressor on whatever dtype x has (compressors.py:267-410): on a float64 vector
@@ -562,6 +612,13 @@ int flc_ef_accumulate(const float* const* local, const float* const* global /* N
  * outside [1, 127].  n_clients == 0 or k == 0: the tables are checked, nothing is launched. */
 int flc_ef_residual_round(const void* const* records, float* const* es, int n_clients, int64_t n, int64_t k,
                           int levels, void* stream);
+/* The residual of a round's sparse records (flc_sparse_wire_layout(n, k): top-k's and rand-k's messages,
+ * compressors.py:284-296): es[c][idx[j]] -= val[j] for every client c and entry j < k.  Bit-identical to
+ * flc_sparse_decode_tiled(scale 1, weight 1, accumulate 0) into a zeroed c_dense followed by flc_ef_residual_dense: an
+ * element no entry names keeps its bits (a -0 included).  The launch bound (32 clients, more chain), the skipped
+ * out-of-range indices and the FLC_EINVAL cases are flc_ef_residual_round's, without levels. */
+int flc_ef_residual_sparse_round(const void* const* records, float* const* es, int n_clients, int64_t n, int64_t k,
+                                 void* stream);
 /* e[i] = e[i] - c[i], i < n: the residual of a message that carries its decoded flat vector c (every compressor but
  * the stacked pipeline).  16-B accesses when both pointers are 16-B aligned, 4-B otherwise; the same bits either way.
  * FLC_EINVAL: n < 0, a null pointer with n > 0, e == c. */
@@ -617,6 +674,15 @@ int flc_avg_and_gradient_records(float* const* params, float* const* grads, cons
                                  const void* const* grad_records, const float* w_params, const float* w_grads,
                                  int n_src, int64_t n, int64_t k, int levels, const int64_t* sizes, int n_tensors,
                                  float inertia, void* stream);
+/* flc_avg_and_gradient_records' contract when every message carries its gradients as a sparse record
+ * (flc_sparse_wire_layout(n, k); replaces the same reference lines: fedprox/_fedprox.py:163-167, fedpd/_fedpd.py:197-202,
+ * proxskip/_proxskip.py:212-216, pfedmac/_pfedmac.py:158-162, nodes.py:1134-1180): bit-identical to decoding every
+ * record densely (flc_sparse_decode_tiled) and calling flc_avg_and_gradients.  Arguments and chaining as
+ * flc_avg_and_gradient_records' without levels; k in [1, n]. */
+int flc_avg_and_gradient_sparse_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                        const void* const* grad_records, const float* w_params, const float* w_grads,
+                                        int n_src, int64_t n, int64_t k, const int64_t* sizes, int n_tensors,
+                                        float inertia, void* stream);
 /* FedDyn's and pFedMe's server updates on a whole model, one pass per <= 16 tensors and <= 16 messages
  * (theta = the model, aux = the per-element second state; srcs[m * n_tensors + t] = message m's tensor t):
  *   FLC_SRV_FEDDYN (feddyn/_feddyn.py:172-184): h = aux, for each message in order h = fmaf(c, fl(src - theta0), h)
