@@ -262,21 +262,12 @@ def _fused_fedopt(recs, ws, n, k, sizes, state, beta0, opt, lr, beta2, tau, step
     torch.cuda.synchronize()
 
 
-def _assert_adaptive_tail(fa, fb, theta0):
-    """test_gpu_round._check_adaptive_tail's comparison on (theta, delta, v): δ bit for bit, v within 1 ulp on under 1 %
-    of the elements, θ within 1e-6 of the update + 1 ulp (lanes that are not finite on the reference side compare as
-    bit patterns)."""
-    (ta, da, va), (tb, db, vb) = [[_bits(f) for f in fs] for fs in (fa, fb)]
-    assert gc.same_bits(da, db)
-    fin = np.isfinite(vb)
-    assert gc.same_bits(va[~fin], vb[~fin])
-    ulp_v = np.abs(va[fin].view(np.int32).astype(np.int64) - vb[fin].view(np.int32).astype(np.int64))
-    assert ulp_v.size == 0 or (ulp_v.max() <= 1 and (ulp_v > 0).mean() < 0.01)
-    fin = np.isfinite(tb)
-    assert gc.same_bits(ta[~fin], tb[~fin])
-    upd = np.abs(tb[fin].astype(np.float64) - _bits(theta0)[fin])
-    err = np.abs(tb[fin].astype(np.float64) - ta[fin].astype(np.float64))
-    assert np.all(err <= 1e-6 * upd + np.spacing(np.abs(tb[fin])))
+def _assert_adaptive_tail(fa, fb):
+    """(theta, delta, v) of the fused fold and of decode-then-model_fold, bit for bit: both sides inline the one
+    opt_step (flc_device.hpp) under -ffp-contract=off, so no tolerance applies (the tolerance of
+    test_gpu_round._check_adaptive_tail is for comparisons with torch only)."""
+    for name, a, b in zip(("theta", "delta", "v"), fa, fb):
+        assert gc.same_bits(_bits(a), _bits(b)), name
 
 
 @pytest.mark.parametrize("n,kk,R", [(4097, "third", 3), (4097, "percent", 65), (70001, "percent", 10),
@@ -295,13 +286,12 @@ def test_fedopt_fold_sparse_records_equals_decode_then_model_fold(n, kk, R):
             lead = 0 if name == "one" else 1
             base_a, fa, a = _state(n, sizes, n + R, lead)
             base_b, fb, b = _state(n, sizes, n + R, lead)
-            theta0 = fa[0].clone()
             _fused_fedopt(recs, ws, n, k, sizes, a, beta0, opt, lr, beta2, tau, step)
             _dense_fedopt(recs, ws, n, k, sizes, b, beta0, opt, lr, beta2, tau, step)
             if opt == "avg":
                 assert gc.same_bits(_bits(base_a), _bits(base_b)), (name, opt, step)
             else:
-                _assert_adaptive_tail(fa, fb, theta0)
+                _assert_adaptive_tail(fa, fb)
 
 
 @pytest.mark.parametrize("ext", [True, False])
