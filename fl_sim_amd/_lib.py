@@ -161,6 +161,8 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
          c_void_p],
     ),
+    "flc_avg_and_gradient_dense_records": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                   c_int64, c_int, c_int, c_int, c_void_p, c_int, c_float, c_void_p]),
     "flc_sparse_wire_layout": (c_size_t, [c_int64, c_int64, c_void_p]),
     "flc_fold_sparse_wires": (
         c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p]

@@ -178,10 +178,11 @@ def _flat_views(like: Sequence[torch.Tensor], **kw):
 
 def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs, wg: Sequence[float],
                   wp: Optional[Sequence[float]] = None, inertia: float = 0.0) -> Optional[List[torch.Tensor]]:
-    """A round whose ``gradients`` are stacked records (``recs``: compressed.stacked_round(messages, "gradients")) or
-    sparse records (compressed.sparse_round): every record decoded and folded into one flat gradient buffer and, with
-    ``wp``, the dense ``parameters`` folded into the model in the same pass (flc_avg_and_gradient_records /
-    flc_avg_and_gradient_sparse_records); the records are never decoded densely.  Sets
+    """A round whose ``gradients`` are stacked records (``recs``: compressed.stacked_round(messages, "gradients")),
+    sparse records (compressed.sparse_round) or dense records (compressed.dense_record_round): every record decoded
+    and folded into one flat gradient buffer and, with ``wp``, the dense ``parameters`` folded into the model in the
+    same pass (flc_avg_and_gradient_records / flc_avg_and_gradient_sparse_records /
+    flc_avg_and_gradient_dense_records); the records are never decoded densely.  Sets
     ``.grad`` of every parameter and returns the gradients; None (nothing launched, nothing changed) when the model
     is not one the launch takes — the caller's dense path follows.  A host-resident model is staged: the records (and
     the messages' parameters) in, the parameters out, the gradients out in one copy."""
@@ -214,15 +215,20 @@ def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs
             grads.append(host[off:off + p.numel()].view(p.shape))
             off += p.numel()
     else:
-        fast = codec._pygrecs() if recs[0].kind == "stacked" else None  # (sparse records: the ctypes call below)
+        d0 = recs[0]
+        if d0.kind == "sparse":
+            fast, shape = codec._pygsrecs(), (d0.n, d0.k)
+        elif d0.kind in ("quant", "natural"):
+            fast, shape = codec._pygdrecs(), (d0.n, d0.format, d0.levels, d0.bits)
+        else:
+            fast, shape = codec._pygrecs(), (d0.n, d0.k, d0.levels)
         if fast is not None and mps and isinstance(mps[0], torch.Tensor) and mps[0].is_cuda:
             # one C call: every tensor and record checked in place, the fold, the gradients' buffer and views, and every
             # parameter's `.grad`; a TypeError (a tensor the launch does not take, or messages elsewhere) leaves
-            # everything untouched
-            d0 = recs[0]
+            # everything untouched and the ctypes call below decides
             try:
-                return fast(mps, messages if wp is not None else None, [d.record for d in recs], wp, wg, d0.n, d0.k,
-                            d0.levels, float(inertia), True)[0]
+                return fast(mps, messages if wp is not None else None, [d.record for d in recs], wp, wg, *shape,
+                            float(inertia), True)[0]
             except TypeError:
                 pass
         ps = _params(mps)
@@ -241,12 +247,13 @@ def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs
 def update_gradients(model_params: Sequence[torch.Tensor], messages: Sequence[Mapping]) -> Optional[List[torch.Tensor]]:
     """nodes.py:1165-1180: sets ``.grad`` of each model parameter to the sample-weighted gradient sum, on the model's
     device (a host-resident model gets host gradients, as the reference's ``.to(self.device)`` gives).  A round whose
-    gradients are stacked records is folded from the records (flc_avg_and_gradient_records, the parameters untouched)."""
+    gradients are records of one kind and shape (compressed.record_round: stacked, dense or sparse) is folded from the
+    records (flc_avg_and_gradient_records and its dense and sparse counterparts, the parameters untouched)."""
     if len(messages) == 0:
         return None
     assert all(["gradients" in m for m in messages]), "some clients have not sent gradients yet"
     model_params = list(model_params)
-    recs = ((compressed.stacked_round(messages, key="gradients") or compressed.sparse_round(messages, key="gradients"))
+    recs = (compressed.record_round(messages, key="gradients")
             if isinstance(messages[0]["gradients"], compressed.CompressedDelta) else None)
     if recs is not None:
         total_samples = sum([m["train_samples"] for m in messages])
@@ -335,8 +342,10 @@ def avg_parameters_and_gradients(model_params: Sequence[torch.Tensor], messages:
     fedpd/_fedpd.py:197-202, proxskip/_proxskip.py:212-216, pfedmac/_pfedmac.py:158-162).  Bit-identical to the two
     calls; a host-resident model is staged once (its messages and parameters in; the parameters and, in one copy, the
     gradients out).  Sets ``.grad`` of each parameter as update_gradients does and returns the gradients.  A round
-    whose ``gradients`` are stacked records (compressed.CompressedGradientsClientMixin) is folded from the records in
-    the same single pass (flc_avg_and_gradient_records); a mixed or dense round takes the dense path."""
+    whose ``gradients`` are records of one kind and shape (compressed.CompressedGradientsClientMixin; stacked, dense
+    or sparse: compressed.record_round) is folded from the records in the same single pass
+    (flc_avg_and_gradient_records / flc_avg_and_gradient_dense_records / flc_avg_and_gradient_sparse_records); a mixed
+    round, or one of decoded gradients, takes the dense path."""
     assert 0.0 <= inertia < 1.0, "`inertia` should be in [0, 1)"
     if len(messages) == 0:
         return None
@@ -347,7 +356,7 @@ def avg_parameters_and_gradients(model_params: Sequence[torch.Tensor], messages:
     wg = [m["train_samples"] / total for m in messages]
     n = len(messages)
     if isinstance(messages[0]["gradients"], compressed.CompressedDelta):
-        recs = compressed.stacked_round(messages, key="gradients") or compressed.sparse_round(messages, key="gradients")
+        recs = compressed.record_round(messages, key="gradients")
         if recs is not None:  # compressed gradients: the records folded beside the dense parameters, in the same pass
             r = _record_round(mps, messages, recs, wg, wp, inertia)
             if r is not None:
@@ -790,7 +799,7 @@ class VRUpdateMixin:
         if hoststage.is_host(mps):
             keys = ["parameters"] + (["gradients"] if self.config.vr else [])
             # (compressed gradients are placed by their record or flat vector: iterating them would decode them)
-            _adopt([mps], [[m[k].record if m[k].kind in ("stacked", "sparse") else m[k].flat()]
+            _adopt([mps], [[m[k].flat() if m[k].kind == "dense" else m[k].record]
                            if isinstance(m[k], compressed.CompressedDelta) else m[k]
                            for m in self._received_messages for k in keys])
             mps = list(self.model.parameters())  # (the adopted tensors)

@@ -1115,6 +1115,8 @@ _PYDRECS: list = []
 _PYSRECS: list = []
 _PYGROUPS: list = []
 _PYGRECS: list = []
+_PYGDRECS: list = []
+_PYGSRECS: list = []
 _PYFLAT: list = []
 _PYROUND: list = []
 _PYDELTA: list = []
@@ -1159,6 +1161,16 @@ def _pygroups():
 def _pygrecs():
     """_flcfold.avg_and_gradient_records (flc_avg_and_gradient_records on lists, one C call), or None."""
     return _flcfold_entry(_PYGRECS, "avg_and_gradient_records")
+
+
+def _pygdrecs():
+    """_flcfold.avg_and_gradient_dense_records (flc_avg_and_gradient_dense_records on lists, one C call), or None."""
+    return _flcfold_entry(_PYGDRECS, "avg_and_gradient_dense_records")
+
+
+def _pygsrecs():
+    """_flcfold.avg_and_gradient_sparse_records (flc_avg_and_gradient_sparse_records on lists, one C call), or None."""
+    return _flcfold_entry(_PYGSRECS, "avg_and_gradient_sparse_records")
 
 
 def _pyflat():

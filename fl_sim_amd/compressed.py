@@ -44,10 +44,10 @@ What runs here instead:
   v) read and written once; bit-identical to decoding each record and running the reference's update.  A round of
   dense records of one (n, format, levels, bits) (:func:`dense_record_round`) takes the same functions
   (``flc_fedopt_fold_dense_records``; for SCAFFOLD and IFCA ``flc_fold_dense_record_groups``): the server reads the
-  codes, 1/4 to 1/16 of the dense bytes.  A round of sparse records of one (n, k) (:func:`sparse_round`) takes them too
-  (``flc_fedopt_fold_sparse_records``, ``flc_fold_sparse_record_groups``, and for the variance-reduced servers'
-  ``gradients`` ``flc_avg_and_gradient_sparse_records``).  A mixed round, and the variance-reduced servers'
-  ``gradients`` as dense records, read each message as its decoded tensors.
+  codes, 1/4 to 1/16 of the dense bytes; the variance-reduced servers' ``gradients`` as dense records take
+  ``flc_avg_and_gradient_dense_records``.  A round of sparse records of one (n, k) (:func:`sparse_round`) takes them
+  too (``flc_fedopt_fold_sparse_records``, ``flc_fold_sparse_record_groups``, and for the variance-reduced servers'
+  ``gradients`` ``flc_avg_and_gradient_sparse_records``).  A mixed round reads each message as its decoded tensors.
 
 The compressors' send statistics advance as ``compressVector`` advances them (``compressors.py:406-408``), per stage.
 
@@ -59,8 +59,10 @@ the one whose server fold starts from +0 (``tests/golden/gen_golden_vr_codec.py`
 * :class:`CompressedGradientsClientMixin` — runs the client's own ``communicate`` and sends the ``gradients`` of the
   message it appended through :func:`compress_tensors` (everything :func:`compress_delta` does, nothing subtracted);
 * ``aggregation.avg_parameters_and_gradients`` / ``update_gradients`` (and the ``VRUpdateMixin`` family) recognise a
-  round of stacked records and run :func:`fold_gradient_records`: every record decoded and folded into the gradients
-  and the dense parameters folded into the model in one ``flc_avg_and_gradient_records`` pass.
+  round of stacked, dense or sparse records (:func:`record_round`) and run :func:`fold_gradient_records`: every record
+  decoded and folded into the gradients and the dense parameters folded into the model in one
+  ``flc_avg_and_gradient_records`` pass (``flc_avg_and_gradient_dense_records`` /
+  ``flc_avg_and_gradient_sparse_records`` by the records' kind).
 
 SCAFFOLD and IFCA send deltas (scaffold/_scaffold.py:210-222: ``parameters_delta`` and ``control_variates_delta``;
 ifca/_ifca.py:228-240: ``delta_parameters`` and a ``cluster_id``), and their servers accumulate each message in place
@@ -1042,7 +1044,8 @@ def fold_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequence[f
                           records: Optional[Sequence[torch.Tensor]] = None) -> bool:
     """``grads = Σ_m w_grads[m]·decode(record_m)`` from +0 in message order and, with ``params``,
     ``θ = θ·inertia + Σ_m w_params[m]·param_srcs[m]`` — one ``flc_avg_and_gradient_records`` pass (``params`` None:
-    ``update_gradients`` alone).  ``records``: the messages' records where they were staged (default: the deltas' own).
+    ``update_gradients`` alone; ``flc_avg_and_gradient_sparse_records`` / ``flc_avg_and_gradient_dense_records`` by
+    the records' kind).  ``records``: the messages' records where they were staged (default: the deltas' own).
     False (nothing launched) when a tensor is not a contiguous fp32 tensor of the gradients' HIP device holding the
     records' element count (the caller then takes the dense path); records and parameter sources elsewhere are moved."""
     gs = list(grads)
@@ -1067,13 +1070,16 @@ def fold_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequence[f
     recs = [d.record for d in deltas] if records is None else list(records)
     recs = [r if r.device == dev else r.to(dev) for r in recs]
     fl = lambda ws: (ctypes.c_float * m)(*[float(w) for w in ws])  # noqa: E731
-    sparse = d0.kind == "sparse"  # (a sparse_round: flc_avg_and_gradient_sparse_records, the same contract)
+    # (a sparse_round: flc_avg_and_gradient_sparse_records; a dense_record_round: flc_avg_and_gradient_dense_records —
+    # the same contract)
+    sparse, dense = d0.kind == "sparse", d0.kind in ("quant", "natural")
+    shape = (d0.n, d0.k) if sparse else (d0.n, d0.format, d0.levels, d0.bits) if dense else (d0.n, d0.k, d0.levels)
+    fn = ("flc_avg_and_gradient_sparse_records" if sparse else
+          "flc_avg_and_gradient_dense_records" if dense else "flc_avg_and_gradient_records")
     with torch.cuda.device(dev):
-        _lib.call("flc_avg_and_gradient_sparse_records" if sparse else "flc_avg_and_gradient_records",
-                  _ptrs(ps) if ps is not None else None, _ptrs(gs),
+        _lib.call(fn, _ptrs(ps) if ps is not None else None, _ptrs(gs),
                   _ptrs([t for r in srcs for t in r]) if srcs is not None else None, _ptrs(recs),
-                  fl(w_params) if ps is not None else None, fl(w_grads), m, d0.n, d0.k,
-                  *(() if sparse else (d0.levels,)),
+                  fl(w_params) if ps is not None else None, fl(w_grads), m, *shape,
                   (ctypes.c_int64 * T)(*[g.numel() for g in gs]), T, float(inertia), codec._stream(dev))
     return True
 
@@ -1291,8 +1297,8 @@ class CompressedGradientsClientMixin(ErrorFeedbackClientMixin):
     :class:`~fl_sim_amd.compressors.Compressor` or a sequence applied in order; none leaves the message unchanged).
     A client that skips the round appends nothing, so nothing is compressed and no compressor advances; ``parameters``
     stay as the reference sends them.  The server side is :class:`~fl_sim_amd.aggregation.VRUpdateMixin`, which folds a
-    round of stacked records and the dense parameters in one pass (or any reference server: the compressed gradients
-    read as a list of tensors).  With ``error_feedback`` the gradients go through the memory
+    round of stacked, dense or sparse records and the dense parameters in one pass (or any reference server: the
+    compressed gradients read as a list of tensors).  With ``error_feedback`` the gradients go through the memory
     ``self.error_memory("gradients")``; a client that skips the round touches no memory."""
 
     def communicate(self, target) -> None:

@@ -5,6 +5,8 @@
 //   server_fold               flc_model_fold_server: FedDyn's and pFedMe's server updates
 //   avg_and_gradients         flc_avg_and_gradients: the variance-reduced servers' avg_parameters + update_gradients
 //   avg_and_gradient_records  flc_avg_and_gradient_records: the same over compressed gradients
+//   avg_and_gradient_sparse_records / avg_and_gradient_dense_records
+//                             the same over sparse (top-k / rand-k) and dense (dithering / natural) gradient records
 //   fold_records              flc_fedopt_fold_records: the server update of a round of stacked records
 //   fold_dense_records        flc_fedopt_fold_dense_records: the same for dense records
 //   fold_sparse_records       flc_fedopt_fold_sparse_records: the same for sparse (top-k / rand-k) records
@@ -805,13 +807,12 @@ PyObject* fold_record_groups(PyObject*, PyObject* args) {
 // unused); the gradients decoded and folded into one new flat fp32 buffer on the model's device, returned as (list of
 // per-parameter views, flat buffer); with `set_grad` each parameter's `.grad` is set to its view.  TypeError (nothing
 // allocated or launched) when a tensor is not what the pass takes, as fold_records and avg_and_gradients raise it.
-PyObject* avg_and_gradient_records(PyObject*, PyObject* args) {
-  PyObject *params, *msgs, *recs, *wpar, *wgrd;
-  long long n, k;
-  int levels, set_grad = 0;
-  double inertia;
-  if (!PyArg_ParseTuple(args, "OOOOOLLid|p", &params, &msgs, &recs, &wpar, &wgrd, &n, &k, &levels, &inertia, &set_grad))
-    return nullptr;
+// (format kStackedRecords: stacked records of (n, k, levels) — flc_avg_and_gradient_records; kSparseRecords: sparse
+// records of (n, k) — flc_avg_and_gradient_sparse_records; else dense records of (n, format, levels, bits) —
+// flc_avg_and_gradient_dense_records: one worker, as fold_records_of is the FedOpt entries')
+PyObject* avg_and_gradient_records_of(PyObject* params, PyObject* msgs, PyObject* recs, PyObject* wpar, PyObject* wgrd,
+                                      long long n, long long k, int format, int levels, int bits, double inertia,
+                                      int set_grad) {
   Refs refs;
   const bool p_on = msgs != Py_None;
   PyObject* seqs[5] = {params, recs, wgrd, p_on ? msgs : recs, p_on ? wpar : wgrd};
@@ -832,7 +833,9 @@ PyObject* avg_and_gradient_records(PyObject*, PyObject* args) {
   for (int64_t s : sz) total += s;
   if (total != n) return type_error("the model tensors do not hold the records' element count");
   int64_t off4[4];
-  const size_t stride = flc_stacked_wire_layout(n, k, off4);
+  const size_t stride = format == kSparseRecords    ? flc_sparse_wire_layout(n, k, off4)
+                        : format == kStackedRecords ? flc_stacked_wire_layout(n, k, off4)
+                                                    : flc_dense_wire_layout(n, format, bits, off4);
   if (stride == 0) return value_error("bad wire shape");
   std::vector<const void*> rp(ns);
   std::vector<const float*> ps(p_on ? (size_t)ns * nt : 0);
@@ -852,13 +855,59 @@ PyObject* avg_and_gradient_records(PyObject*, PyObject* args) {
   at::Tensor flat;
   std::vector<at::Tensor> gv;
   if (!gradient_views(pt, sz, dev, &flat, &gv, gp.data())) return nullptr;
-  if (!on_device(dev, "flc_avg_and_gradient_records", [&](void* st) {
-        return flc_avg_and_gradient_records(p_on ? pp.data() : nullptr, gp.data(), p_on ? ps.data() : nullptr, rp.data(),
-                                            p_on ? wp.data() : nullptr, wg.data(), (int)ns, n, k, levels, sz.data(),
-                                            (int)nt, (float)inertia, st);
+  float* const* ppp = p_on ? pp.data() : nullptr;
+  const float* const* psp = p_on ? ps.data() : nullptr;
+  const float* wpp = p_on ? wp.data() : nullptr;
+  const char* fn = format == kSparseRecords    ? "flc_avg_and_gradient_sparse_records"
+                   : format == kStackedRecords ? "flc_avg_and_gradient_records"
+                                               : "flc_avg_and_gradient_dense_records";
+  if (!on_device(dev, fn, [&](void* st) {
+        if (format == kSparseRecords)
+          return flc_avg_and_gradient_sparse_records(ppp, gp.data(), psp, rp.data(), wpp, wg.data(), (int)ns, n, k,
+                                                     sz.data(), (int)nt, (float)inertia, st);
+        return format < 0 ? flc_avg_and_gradient_records(ppp, gp.data(), psp, rp.data(), wpp, wg.data(), (int)ns, n, k,
+                                                         levels, sz.data(), (int)nt, (float)inertia, st)
+                          : flc_avg_and_gradient_dense_records(ppp, gp.data(), psp, rp.data(), wpp, wg.data(), (int)ns,
+                                                               n, format, levels, bits, sz.data(), (int)nt,
+                                                               (float)inertia, st);
       }))
     return nullptr;
   return views_result(pt, gv, flat, set_grad != 0);
+}
+PyObject* avg_and_gradient_records(PyObject*, PyObject* args) {
+  PyObject *params, *msgs, *recs, *wpar, *wgrd;
+  long long n, k;
+  int levels, set_grad = 0;
+  double inertia;
+  if (!PyArg_ParseTuple(args, "OOOOOLLid|p", &params, &msgs, &recs, &wpar, &wgrd, &n, &k, &levels, &inertia, &set_grad))
+    return nullptr;
+  return avg_and_gradient_records_of(params, msgs, recs, wpar, wgrd, n, k, kStackedRecords, levels, 0, inertia,
+                                     set_grad);
+}
+// avg_and_gradient_sparse_records(params, msgs, records, w_params, w_grads, n, k, inertia, set_grad): the same for a
+// round of sparse records (flc_avg_and_gradient_sparse_records; the flc_sparse_wire_layout(n, k) layout)
+PyObject* avg_and_gradient_sparse_records(PyObject*, PyObject* args) {
+  PyObject *params, *msgs, *recs, *wpar, *wgrd;
+  long long n, k;
+  int set_grad = 0;
+  double inertia;
+  if (!PyArg_ParseTuple(args, "OOOOOLLd|p", &params, &msgs, &recs, &wpar, &wgrd, &n, &k, &inertia, &set_grad))
+    return nullptr;
+  return avg_and_gradient_records_of(params, msgs, recs, wpar, wgrd, n, k, kSparseRecords, 0, 0, inertia, set_grad);
+}
+// avg_and_gradient_dense_records(params, msgs, records, w_params, w_grads, n, format, levels, bits, inertia, set_grad):
+// the same for a round of dense records (flc_avg_and_gradient_dense_records; the flc_dense_wire_layout(n, format, bits)
+// layout of a dithering or natural-compressor message)
+PyObject* avg_and_gradient_dense_records(PyObject*, PyObject* args) {
+  PyObject *params, *msgs, *recs, *wpar, *wgrd;
+  long long n;
+  int format, levels, bits, set_grad = 0;
+  double inertia;
+  if (!PyArg_ParseTuple(args, "OOOOOLiiid|p", &params, &msgs, &recs, &wpar, &wgrd, &n, &format, &levels, &bits, &inertia,
+                        &set_grad))
+    return nullptr;
+  if (format < 0) return value_error("bad wire shape");
+  return avg_and_gradient_records_of(params, msgs, recs, wpar, wgrd, n, 0, format, levels, bits, inertia, set_grad);
 }
 
 void release_storage(void* ctx) { delete static_cast<c10::Storage*>(ctx); }
@@ -913,6 +962,12 @@ PyMethodDef kMethods[] = {
     {"avg_and_gradient_records", avg_and_gradient_records, METH_VARARGS,
      "avg_and_gradient_records(params, msgs, records, w_params, w_grads, n, k, levels, inertia[, set_grad]): "
      "flc_avg_and_gradient_records on Python lists (messages: mappings with 'parameters', or None)"},
+    {"avg_and_gradient_sparse_records", avg_and_gradient_sparse_records, METH_VARARGS,
+     "avg_and_gradient_sparse_records(params, msgs, records, w_params, w_grads, n, k, inertia[, set_grad]): "
+     "flc_avg_and_gradient_sparse_records on Python lists"},
+    {"avg_and_gradient_dense_records", avg_and_gradient_dense_records, METH_VARARGS,
+     "avg_and_gradient_dense_records(params, msgs, records, w_params, w_grads, n, format, levels, bits, inertia"
+     "[, set_grad]): flc_avg_and_gradient_dense_records on Python lists"},
     {"delta_flat", delta_flat, METH_VARARGS,
      "delta_flat(local, global): a new flat fp32 tensor cat(local - global) (flc_delta_flatten) on the tensors' device"},
     {"ef_accumulate", ef_accumulate, METH_VARARGS,

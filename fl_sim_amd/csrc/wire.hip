@@ -42,7 +42,8 @@
 // registers as IO::load lays it out, every record's code words of the tile loaded before the ordered fma chain, each
 // code decoded as flc_quant_decode / flc_natural_decode decode it.  flc_fold_dense_wires (FlatIO),
 // flc_fedopt_fold_dense_records (ModelIO) and flc_fold_dense_record_groups (GroupIO) are the stacked entry points'
-// counterparts; a variance-reduced round's gradients (PairIO) have none: such messages decode themselves.
+// counterparts, and flc_avg_and_gradient_dense_records (PairIO) is flc_avg_and_gradient_records': a variance-reduced
+// round's dense gradient records folded into the gradients, the dense parameters into the model in the same pass.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1025,19 +1026,25 @@ int flc_fedopt_fold_dense_records(const void* const* records, const float* weigh
                           stream);
 }
 
-// flc_avg_and_gradient_records (kRecStacked) and flc_avg_and_gradient_sparse_records (kRecSparse), as fedopt_fold_impl
-// serves the FedOpt folds
-static int avg_and_gradient_impl(const char* fn, const char* probe, RecordKind kind, float* const* params,
-                                 float* const* grads, const float* const* param_srcs, const void* const* grad_records,
-                                 const float* w_params, const float* w_grads, int n_src, int64_t n, int64_t k,
-                                 int levels, const int64_t* sizes, int n_tensors, float inertia, void* stream) {
+// flc_avg_and_gradient_records (dense == NULL, kRecStacked), flc_avg_and_gradient_sparse_records (dense == NULL,
+// kRecSparse) and flc_avg_and_gradient_dense_records (the records of *dense), as fedopt_fold_impl serves the FedOpt
+// folds: one argument check and one chain of launches, the kernel by the records' codec
+static int avg_and_gradient_impl(const char* fn, const char* probe, const DenseCodec* dense, RecordKind kind,
+                                 float* const* params, float* const* grads, const float* const* param_srcs,
+                                 const void* const* grad_records, const float* w_params, const float* w_grads,
+                                 int n_src, int64_t n, int64_t k, int levels, const int64_t* sizes, int n_tensors,
+                                 float inertia, void* stream) {
   const bool p_on = param_srcs != nullptr;
   if (n_src < 1 || !grad_records || !w_grads || n <= 0 || k < 0 || n_tensors < 1 || !grads || !sizes ||
       (p_on && (!params || !w_params)))
     return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (n >= (1ll << 31) || k >= (1ll << 31))
     return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
-  if (int rc = check_entry_codec(fn, kind, n, k, levels)) return rc;
+  if (dense) {
+    if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
+  } else if (int rc = check_entry_codec(fn, kind, n, k, levels)) {
+    return rc;
+  }
   int64_t total = 0;
   for (int t = 0; t < n_tensors; ++t) {
     if (sizes[t] < 0) return fail(FLC_EINVAL, "%s: negative size for tensor %d", fn, t);
@@ -1060,7 +1067,8 @@ static int avg_and_gradient_impl(const char* fn, const char* probe, RecordKind k
   hipStream_t st = as_stream(stream);
   const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   // the gradient chain starts at +0: with finite weights only the kept entries are fma'd (the sparse form, its -0
-  // rule as in flc_stacked_fold_wires); a non-finite weight takes every element through every record's fma
+  // rule as in flc_stacked_fold_wires); a non-finite weight takes every element through every record's fma.  (Dense
+  // records carry a code for every element: their fold has no sparse form and needs no -0 replay.)
   bool sparse = true;
   for (int c = 0; c < n_src; ++c) sparse = sparse && std::isfinite(w_grads[c]);
   // launch i of the chain folds records [64 i, 64 i + 64) and parameter sources [16 i, 16 i + 16), each chain
@@ -1107,8 +1115,12 @@ static int avg_and_gradient_impl(const char* fn, const char* probe, RecordKind k
       m.start[m.nt] = off;
       const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
       const dim3 grid((unsigned)(tile_hi - tile_lo));
-      if (int rc = launch_entry_fold(probe, kind, sparse, grid, st, a, L, nw, levels, step, tile_lo, io, (unsigned)k))
+      if (dense) {
+        if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, io)) return rc;
+      } else if (int rc = launch_entry_fold(probe, kind, sparse, grid, st, a, L, nw, levels, step, tile_lo, io,
+                                            (unsigned)k)) {
         return rc;
+      }
     }
   }
   return FLC_OK;
@@ -1118,17 +1130,27 @@ int flc_avg_and_gradient_records(float* const* params, float* const* grads, cons
                                  const void* const* grad_records, const float* w_params, const float* w_grads,
                                  int n_src, int64_t n, int64_t k, int levels, const int64_t* sizes, int n_tensors,
                                  float inertia, void* stream) {
-  return avg_and_gradient_impl("flc_avg_and_gradient_records", "avg_and_gradient_records", kRecStacked, params, grads,
-                               param_srcs, grad_records, w_params, w_grads, n_src, n, k, levels, sizes, n_tensors,
-                               inertia, stream);
+  return avg_and_gradient_impl("flc_avg_and_gradient_records", "avg_and_gradient_records", nullptr, kRecStacked, params,
+                               grads, param_srcs, grad_records, w_params, w_grads, n_src, n, k, levels, sizes,
+                               n_tensors, inertia, stream);
 }
 
 int flc_avg_and_gradient_sparse_records(float* const* params, float* const* grads, const float* const* param_srcs,
                                         const void* const* grad_records, const float* w_params, const float* w_grads,
                                         int n_src, int64_t n, int64_t k, const int64_t* sizes, int n_tensors,
                                         float inertia, void* stream) {
-  return avg_and_gradient_impl("flc_avg_and_gradient_sparse_records", "avg_and_gradient_sparse_records", kRecSparse,
-                               params, grads, param_srcs, grad_records, w_params, w_grads, n_src, n, k, 0, sizes,
+  return avg_and_gradient_impl("flc_avg_and_gradient_sparse_records", "avg_and_gradient_sparse_records", nullptr,
+                               kRecSparse, params, grads, param_srcs, grad_records, w_params, w_grads, n_src, n, k, 0,
+                               sizes, n_tensors, inertia, stream);
+}
+
+int flc_avg_and_gradient_dense_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                       const void* const* grad_records, const float* w_params, const float* w_grads,
+                                       int n_src, int64_t n, int format, int levels, int bits, const int64_t* sizes,
+                                       int n_tensors, float inertia, void* stream) {
+  const DenseCodec cd{format, levels, bits, n};
+  return avg_and_gradient_impl("flc_avg_and_gradient_dense_records", "avg_and_gradient_dense_records", &cd, kRecStacked,
+                               params, grads, param_srcs, grad_records, w_params, w_grads, n_src, n, 0, levels, sizes,
                                n_tensors, inertia, stream);
 }
 

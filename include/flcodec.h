@@ -683,6 +683,23 @@ int flc_avg_and_gradient_sparse_records(float* const* params, float* const* grad
                                         const void* const* grad_records, const float* w_params, const float* w_grads,
                                         int n_src, int64_t n, int64_t k, const int64_t* sizes, int n_tensors,
                                         float inertia, void* stream);
+/* flc_avg_and_gradient_records' contract when every message carries its gradients as a dense record
+ * (flc_dense_wire_layout(n, format, bits): the dithering quantizers' and the natural compressor's wire; replaces
+ * nodes.py:1134-1180 — avg_parameters and update_gradients — over compressors.py:357 / 394 / 302-325's decoded vectors,
+ * for fedprox/_fedprox.py:163-167, fedpd/_fedpd.py:197-202, proxskip/_proxskip.py:212-216, pfedmac/_pfedmac.py:158-162):
+ *   params[t] = params[t] * inertia, then fmaf(w_params[m], param_srcs[m * n_tensors + t], .) for m in order
+ *               (param_srcs == NULL: params is neither read nor written — update_gradients alone);
+ *   grads[t]  = +0, then fmaf(w_grads[m], decode(grad_records[m])[e], .) for m in order;
+ * bit-identical to decoding every record densely (flc_quant_decode; flc_natural_decode for FLC_WIRE_NATURAL) and calling
+ * flc_avg_and_gradients: every element takes every record's fma (a dense record holds a code for every element, so
+ * there is no sparse form), a norm that is 0, +-inf, NaN or negative decodes as flc_fold_dense_wires states.  The
+ * records' codes are read once (bits / 32 of the decoded vectors' bytes) and no decoded vector is ever written.
+ * Arguments and chaining as flc_avg_and_gradient_records' (records per 64, parameter sources per 16, tensors per 16),
+ * (format, levels, bits) and their FLC_EINVAL cases as flc_fold_dense_wires'. */
+int flc_avg_and_gradient_dense_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                       const void* const* grad_records, const float* w_params, const float* w_grads,
+                                       int n_src, int64_t n, int format, int levels, int bits,
+                                       const int64_t* sizes, int n_tensors, float inertia, void* stream);
 /* FedDyn's and pFedMe's server updates on a whole model, one pass per <= 16 tensors and <= 16 messages
  * (theta = the model, aux = the per-element second state; srcs[m * n_tensors + t] = message m's tensor t):
  *   FLC_SRV_FEDDYN (feddyn/_feddyn.py:172-184): h = aux, for each message in order h = fmaf(c, fl(src - theta0), h)
