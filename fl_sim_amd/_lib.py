@@ -20,6 +20,7 @@ FLC_OK = 0
 FLC_Q_STANDARD_DITHER = 0
 FLC_Q_NATURAL_DITHER = 1
 FLC_WIRE_NATURAL = 2  # flc_dense_wire_layout's format for the natural compressor's uint16 codes
+FLC_REC_STACKED, FLC_REC_SPARSE, FLC_REC_DENSE, FLC_REC_FLAT = 0, 1, 2, 3  # flc_record_kind (the mixed folds)
 FLC_NORM_INF = 0
 FLC_NORM_L2 = 2
 FLC_OPT = {"avg": 0, "adagrad": 1, "yogi": 2, "adam": 3}
@@ -177,6 +178,19 @@ SIGNATURES = {
     ),
     "flc_avg_and_gradient_sparse_records": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                                     c_int64, c_int64, c_void_p, c_int, c_float, c_void_p]),
+    "flc_fedopt_fold_mixed_records": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_int, c_float, c_int, c_double, c_double, c_double, c_void_p],
+    ),
+    "flc_fold_mixed_record_groups": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_int, c_void_p, c_int, c_void_p],
+    ),
+    "flc_avg_and_gradient_mixed_records": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                   c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_int, c_float, c_void_p]),
     "flc_sparse_gather": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "flc_ef_residual_sparse_round": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "flc_comm_id_bytes": (c_size_t, []),

@@ -188,8 +188,10 @@ def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs
     the messages' parameters) in, the parameters out, the gradients out in one copy."""
     n = len(messages)
     psrc = [m["parameters"] for m in messages] if wp is not None else None
+    # (a compressed.mixed_round: the messages differ in codec — flc_avg_and_gradient_mixed_records, device servers only)
+    mixed = compressed.MIXED_FOLD and any(d.codec_key != recs[0].codec_key for d in recs)
     if hoststage.is_host(mps):
-        if not all(isinstance(p, torch.Tensor) and p.is_cpu and p.dtype is torch.float32 for p in mps):
+        if mixed or not all(isinstance(p, torch.Tensor) and p.is_cpu and p.dtype is torch.float32 for p in mps):
             return None
         rmsgs = [[d.record] for d in recs]
         host = None
@@ -222,7 +224,7 @@ def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs
             fast, shape = codec._pygdrecs(), (d0.n, d0.format, d0.levels, d0.bits)
         else:
             fast, shape = codec._pygrecs(), (d0.n, d0.k, d0.levels)
-        if fast is not None and mps and isinstance(mps[0], torch.Tensor) and mps[0].is_cuda:
+        if fast is not None and not mixed and mps and isinstance(mps[0], torch.Tensor) and mps[0].is_cuda:
             # one C call: every tensor and record checked in place, the fold, the gradients' buffer and views, and every
             # parameter's `.grad`; a TypeError (a tensor the launch does not take, or messages elsewhere) leaves
             # everything untouched and the ctypes call below decides
@@ -236,7 +238,8 @@ def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs
             return None
         with torch.cuda.device(ps[0].device):
             _, grads = _flat_views(ps, device=ps[0].device)
-            if not compressed.fold_gradient_records(recs, wg, grads, ps if wp is not None else None, psrc, wp, inertia):
+            fold = compressed.fold_mixed_gradient_records if mixed else compressed.fold_gradient_records
+            if not fold(recs, wg, grads, ps if wp is not None else None, psrc, wp, inertia):
                 return None
     for mp, g in zip(mps, grads):
         if isinstance(mp, torch.Tensor):
@@ -254,6 +257,7 @@ def update_gradients(model_params: Sequence[torch.Tensor], messages: Sequence[Ma
     assert all(["gradients" in m for m in messages]), "some clients have not sent gradients yet"
     model_params = list(model_params)
     recs = (compressed.record_round(messages, key="gradients")
+            or compressed.mixed_round(messages, key="gradients")
             if isinstance(messages[0]["gradients"], compressed.CompressedDelta) else None)
     if recs is not None:
         total_samples = sum([m["train_samples"] for m in messages])
@@ -356,7 +360,7 @@ def avg_parameters_and_gradients(model_params: Sequence[torch.Tensor], messages:
     wg = [m["train_samples"] / total for m in messages]
     n = len(messages)
     if isinstance(messages[0]["gradients"], compressed.CompressedDelta):
-        recs = compressed.record_round(messages, key="gradients")
+        recs = compressed.record_round(messages, key="gradients") or compressed.mixed_round(messages, key="gradients")
         if recs is not None:  # compressed gradients: the records folded beside the dense parameters, in the same pass
             r = _record_round(mps, messages, recs, wg, wp, inertia)
             if r is not None:
@@ -429,6 +433,11 @@ def fedopt_update(model_params: Sequence[torch.Tensor], delta_parameters: Sequen
     if recs is not None and compressed.fold_records(recs, [alpha] * len(recs), delta_parameters, model_params, vps,
                                                     betas[0], opt if vps is not None else "avg", lr, betas[1], tau):
         return  # every record decoded, folded and the optimizer step applied in one pass
+    mixed = compressed.mixed_round(messages) if recs is None else None  # (FLC_MIXED_FOLD=1: the messages' codecs differ)
+    if mixed is not None and compressed.fold_mixed_records(mixed, [alpha] * len(mixed), delta_parameters, model_params,
+                                                           vps, betas[0], opt if vps is not None else "avg", lr,
+                                                           betas[1], tau):
+        return  # the same pass, every message read by its own codec
     ps = _params(model_params)
     if _fold(delta_parameters, messages, [alpha] * len(messages), 0, betas[0], key="delta_parameters",
              theta=ps, v=vps, opt=opt if vps is not None else "avg", lr=lr, beta2=betas[1], tau=tau):
@@ -462,8 +471,14 @@ def _fold_groups(groups, records=None) -> List[bool]:
     and shape (``CompressedDelta.codec_key``: stacked records of one (n, k, levels), dense records of one (n, format,
     levels, bits)) in one pass (SCAFFOLD's two compressor sets may differ); per group, whether it was folded."""
     done = [False] * len(groups)
+    if (compressed.MIXED_FOLD and records is None
+            and len({d.codec_key for ds, _, _ in groups for d in ds}) > 1
+            and compressed.fold_mixed_record_groups(groups)):
+        return [True] * len(groups)  # (groups of different codecs, or messages within one: one launch for them all)
     shapes: dict = {}
     for i, (ds, _, _) in enumerate(groups):
+        if compressed.MIXED_FOLD and (ds[0].kind == "dense" or any(d.codec_key != ds[0].codec_key for d in ds)):
+            continue  # (a compressed.mixed_round the mixed fold did not take: the dense path)
         shapes.setdefault(ds[0].codec_key, []).append(i)
     for ids in shapes.values():
         ok = compressed.fold_record_groups([groups[i] for i in ids],
@@ -508,6 +523,8 @@ def scaffold_update(model_params: Sequence[torch.Tensor], control_variates: Sequ
                 _add_round(dst, messages if recs[i] is not None else [{key: d} for d in staged[i]], key, ratio)
         return
     ps, cvs = _params(model_params), list(control_variates)
+    if compressed.MIXED_FOLD:  # (a vector whose messages differ in codec joins the grouped fold)
+        recs = [r if r is not None else compressed.mixed_round(messages, key) for r, key in zip(recs, keys)]
     if recs[0] is None and recs[1] is None:
         if not _fold(ps, messages, [ratio_p] * len(messages), 2, key="parameters_delta"):
             for j, sp in enumerate(ps):
@@ -544,7 +561,8 @@ def ifca_update(cluster_centers: Mapping[int, dict], messages: Sequence[Mapping]
     collected = set(i for v in cluster_centers.values() for i in v["client_ids"])
     for c, v in cluster_centers.items():
         v["client_ids"].extend(i for i in prev[c] if i not in collected)
-    if not (compressed.record_round(messages) is not None and _ifca_records(cluster_centers, members, sizes)):
+    if not ((compressed.record_round(messages) is not None and _ifca_records(cluster_centers, members, sizes))
+            or (compressed.mixed_round(messages) is not None and _ifca_mixed(cluster_centers, members, sizes))):
         for c, ms in members.items():
             center = list(cluster_centers[c]["center_model_params"])
             if hoststage.is_host(center):
@@ -585,6 +603,18 @@ def _ifca_records(cluster_centers: Mapping[int, dict], members: Mapping[int, lis
     if any(host):
         return False
     return compressed.fold_record_groups(list(zip(deltas, weights, [_params(center) for center in centers])))
+
+
+def _ifca_mixed(cluster_centers: Mapping[int, dict], members: Mapping[int, list], sizes: Mapping[int, int]) -> bool:
+    """A round whose messages differ in codec (compressed.mixed_round): every cluster with messages folded in one
+    grouped pass (flc_fold_mixed_record_groups), device-resident centres only.  False: nothing launched."""
+    cs = list(members)
+    centers = [list(cluster_centers[c]["center_model_params"]) for c in cs]
+    if any(hoststage.is_host(center) for center in centers):
+        return False
+    return compressed.fold_mixed_record_groups(
+        [([m["delta_parameters"] for m in members[c]], [1 / sizes[c]] * len(members[c]), _params(center))
+         for c, center in zip(cs, centers)])
 
 
 _PROX_KIND = {"l1": "l1", "l2": "l2", "l2squared": "l2squared", "no": "none", "empty": "none", "zero": "none",

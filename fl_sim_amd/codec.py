@@ -1113,6 +1113,7 @@ _PYPAIR: list = []
 _PYRECS: list = []
 _PYDRECS: list = []
 _PYSRECS: list = []
+_PYMRECS: list = []
 _PYGROUPS: list = []
 _PYGRECS: list = []
 _PYGDRECS: list = []
@@ -1151,6 +1152,11 @@ def _pydrecs():
 def _pysrecs():
     """_flcfold.fold_sparse_records (flc_fedopt_fold_sparse_records on lists, one C call), or None."""
     return _flcfold_entry(_PYSRECS, "fold_sparse_records")
+
+
+def _pymrecs():
+    """_flcfold.fold_mixed_records (flc_fedopt_fold_mixed_records on lists, one C call), or None."""
+    return _flcfold_entry(_PYMRECS, "fold_mixed_records")
 
 
 def _pygroups():

@@ -47,7 +47,11 @@ What runs here instead:
   codes, 1/4 to 1/16 of the dense bytes; the variance-reduced servers' ``gradients`` as dense records take
   ``flc_avg_and_gradient_dense_records``.  A round of sparse records of one (n, k) (:func:`sparse_round`) takes them
   too (``flc_fedopt_fold_sparse_records``, ``flc_fold_sparse_record_groups``, and for the variance-reduced servers'
-  ``gradients`` ``flc_avg_and_gradient_sparse_records``).  A mixed round reads each message as its decoded tensors.
+  ``gradients`` ``flc_avg_and_gradient_sparse_records``).  A mixed round reads each message as its decoded tensors —
+  unless ``FLC_MIXED_FOLD=1`` (:data:`MIXED_FOLD`, off by default): then a round whose messages differ in codec, one
+  decoded vector among them included (:func:`mixed_round`), is folded in one pass with every record read by its own
+  descriptor (``flc_fedopt_fold_mixed_records``, ``flc_fold_mixed_record_groups``,
+  ``flc_avg_and_gradient_mixed_records``), on device-resident servers.
 
 The compressors' send statistics advance as ``compressVector`` advances them (``compressors.py:406-408``), per stage.
 
@@ -1149,6 +1153,213 @@ def fold_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequenc
                   (ctypes.c_float * m)(*ws), (ctypes.c_int32 * m)(*gof), m, *shape, _ptrs(dsts), len(live),
                   (ctypes.c_int64 * T)(*sizes), T, codec._stream(dev))
     return True
+
+
+# Mixed rounds.  A round whose messages do not share one codec_key — another K, another bit width, another record
+# kind, or one client that sends its decoded vector — is declined by record_round, and every message then decodes
+# itself (4·n bytes written per message, read back by the dense fold).  With FLC_MIXED_FOLD=1 such a round is folded in
+# one pass over the messages as they are: every record carries its own descriptor (flc_record_kind, k, format, levels,
+# bits) and a decoded vector is read as a flat fp32 record (flc_fedopt_fold_mixed_records, flc_fold_mixed_record_groups,
+# flc_avg_and_gradient_mixed_records), bit-identical to the per-message path.  Off by default; uniform rounds take the
+# uniform folds either way.  mixed_fold_stats() counts the mixed folds run and their messages.
+MIXED_FOLD = os.environ.get("FLC_MIXED_FOLD", "0") == "1"
+_MIXED_STATS = {"folds": 0, "messages": 0}
+_REC_STACKED, _REC_SPARSE, _REC_DENSE, _REC_FLAT = (_lib.FLC_REC_STACKED, _lib.FLC_REC_SPARSE, _lib.FLC_REC_DENSE,
+                                                     _lib.FLC_REC_FLAT)
+
+
+def mixed_fold_stats(reset: bool = False) -> dict:
+    """``{"folds": mixed one-pass folds run, "messages": messages they folded}`` since import or since the last
+    ``mixed_fold_stats(reset=True)`` (which returns the figures up to then)."""
+    out = dict(_MIXED_STATS)
+    if reset:
+        _MIXED_STATS.update(folds=0, messages=0)
+    return out
+
+
+def _mixed_done(messages: int) -> bool:
+    _MIXED_STATS["folds"] += 1
+    _MIXED_STATS["messages"] += messages
+    return True
+
+
+def mixed_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
+    """The messages' compressed deltas when :data:`MIXED_FOLD` is on and the round is one the mixed fold takes and the
+    uniform folds do not: every message carries a :class:`CompressedDelta` of one ``n`` under ``key``, at least one is
+    a record, they do not all share one ``codec_key``, and every decoded (``"dense"``) one holds a float32 flat vector;
+    else None."""
+    if not MIXED_FOLD or not messages:
+        return None
+    ds = []
+    for m in messages:
+        d = m.get(key) if isinstance(m, dict) else None
+        if not isinstance(d, CompressedDelta):
+            return None
+        ds.append(d)
+    d0 = ds[0]
+    if any(d.n != d0.n for d in ds) or all(d.kind == "dense" for d in ds):
+        return None
+    if all(d.codec_key == d0.codec_key for d in ds):
+        return None
+    if any(d.kind == "dense" and not (isinstance(d._flat, torch.Tensor) and d._flat.dtype is torch.float32
+                                      and d._flat.numel() == d.n) for d in ds):
+        return None
+    return ds
+
+
+def _mixed_tables(deltas: Sequence[CompressedDelta], dev: torch.device, records=None):
+    """What the mixed entry points read of ``deltas`` on ``dev``: (tensors, kinds, ks, formats, levels, bits) — a
+    record's bytes (a deferred one is encoded by this read), a decoded message's flat fp32 vector; tensors elsewhere
+    (or not 16-B aligned) are copied.  ``records``: the records where they were staged (None entries: the delta's own)."""
+    ts, kinds, ks, fmts, lvs, bits = [], [], [], [], [], []
+    for i, d in enumerate(deltas):
+        if d.kind == "dense":
+            t, desc = d._flat, (_REC_FLAT, 0, 0, 0, 0)
+        else:
+            t = d.record
+            desc = ((_REC_STACKED, d.k, 0, d.levels, 0) if d.kind == "stacked" else
+                    (_REC_SPARSE, d.k, 0, 0, 0) if d.kind == "sparse" else
+                    (_REC_DENSE, 0, d.format, d.levels, d.bits))
+        if records is not None and records[i] is not None:
+            t = records[i]
+        t = t.detach()
+        if t.device != dev:
+            t = t.to(dev)
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            t = t.clone(memory_format=torch.contiguous_format)
+        ts.append(t)
+        for col, x in zip((kinds, ks, fmts, lvs, bits), desc):
+            col.append(int(x))
+    return ts, kinds, ks, fmts, lvs, bits
+
+
+def _mixed_ctypes(kinds, ks, fmts, lvs, bits):
+    m = len(kinds)
+    i32 = lambda xs: (ctypes.c_int32 * m)(*xs)  # noqa: E731
+    return i32(kinds), (ctypes.c_int64 * m)(*ks), i32(fmts), i32(lvs), i32(bits)
+
+
+def _server_ok(groups: Sequence[Sequence[torch.Tensor]], n: int) -> Optional[torch.device]:
+    """The HIP device of server tensor lists that are, list by list, contiguous fp32 tensors of one device holding the
+    first list's element counts, ``n`` in all; else None."""
+    first = list(groups[0]) if groups else []
+    if not first or not isinstance(first[0], torch.Tensor) or not first[0].is_cuda:
+        return None
+    dev = first[0].device
+    for g in groups:
+        if len(g) != len(first) or any(not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev
+                                            and t.dtype is torch.float32 and t.is_contiguous()
+                                            and t.numel() == f.numel()) for t, f in zip(g, first)):
+            return None
+    return dev if sum(t.numel() for t in first) == n else None
+
+
+def fold_mixed_records(deltas: Sequence[CompressedDelta], weights: Sequence[float],
+                       delta_params: Sequence[torch.Tensor], theta: Optional[Sequence[torch.Tensor]],
+                       v: Optional[Sequence[torch.Tensor]], beta0: float, opt: str = "avg", lr: float = 1.0,
+                       beta2: float = 0.0, tau: float = 0.0) -> bool:
+    """:func:`fold_records` for a :func:`mixed_round`: ``δ = β0·δ + Σ_c w_c·decode_c(message_c)`` in message order,
+    every message by its own codec, then (``theta``) the server optimiser's step — one
+    ``flc_fedopt_fold_mixed_records`` pass.  False (nothing launched) when the server tensors are not contiguous fp32
+    tensors of one HIP device holding the messages' element count."""
+    dps = list(delta_params)
+    groups = [dps] + ([list(theta)] if theta is not None else []) + ([list(v)] if v is not None else [])
+    n = deltas[0].n
+    dev = _server_ok([[p.data if isinstance(p, torch.nn.Parameter) else p for p in g] for g in groups], n)
+    if dev is None:
+        return False
+    ts, kinds, ks, fmts, lvs, bits = _mixed_tables(deltas, dev)
+    ws = [float(w) for w in weights]
+    fast = codec._pymrecs()
+    if fast is not None:
+        try:  # one C call: every tensor checked in place; TypeError: nothing launched, the ctypes call below decides
+            fast(ts, ws, n, kinds, ks, fmts, lvs, bits, dps, None if theta is None else groups[1],
+                 None if v is None else groups[-1], float(beta0), _lib.FLC_OPT[opt], float(lr), float(beta2),
+                 float(tau))
+            return _mixed_done(len(ts))
+        except TypeError:
+            pass
+    m, T = len(ts), len(dps)
+    with torch.cuda.device(dev):
+        _lib.call("flc_fedopt_fold_mixed_records", _ptrs(ts), (ctypes.c_float * m)(*ws), m, n,
+                  *_mixed_ctypes(kinds, ks, fmts, lvs, bits), _ptrs(dps),
+                  _ptrs(groups[1]) if theta is not None else None, _ptrs(groups[-1]) if v is not None else None,
+                  (ctypes.c_int64 * T)(*[t.numel() for t in dps]), T, float(beta0), _lib.FLC_OPT[opt], float(lr),
+                  float(beta2), float(tau), codec._stream(dev))
+    return _mixed_done(m)
+
+
+def fold_mixed_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequence[float],
+                                                    Sequence[torch.Tensor]]]) -> bool:
+    """:func:`fold_record_groups` for groups whose messages differ in codec, within a group or between groups: for
+    every ``(deltas, weights, dst_tensors)``, ``dst += Σ_c w_c·decode_c(message_c)`` in place in the group's message
+    order — all groups in one ``flc_fold_mixed_record_groups`` pass.  False (nothing launched) when a destination is
+    not a contiguous fp32 tensor of one HIP device, the groups' tensors do not all hold the messages' element counts
+    tensor by tensor, or two groups share a destination."""
+    live = [(list(ds), [float(w) for w in ws], [p.data if isinstance(p, torch.nn.Parameter) else p for p in dst])
+            for ds, ws, dst in groups if len(ds)]
+    if not live:
+        return True
+    n = live[0][0][0].n
+    if any(d.n != n for ds, _, _ in live for d in ds) or any(len(ws) != len(ds) for ds, ws, _ in live):
+        return False
+    dev = _server_ok([dst for _, _, dst in live], n)
+    if dev is None:
+        return False
+    seen = set()
+    for _, _, dst in live:
+        for t in dst:
+            if t.numel() and t.data_ptr() in seen:
+                return False
+            seen.add(t.data_ptr())
+    ts, ws, gof, dsts = [], [], [], []
+    cols = ([], [], [], [], [])
+    for g, (ds, w, dst) in enumerate(live):
+        t, *desc = _mixed_tables(ds, dev)
+        ts += t
+        for col, x in zip(cols, desc):
+            col += x
+        ws += w
+        gof += [g] * len(ds)
+        dsts += dst
+    m, T = len(ts), len(live[0][2])
+    with torch.cuda.device(dev):
+        _lib.call("flc_fold_mixed_record_groups", _ptrs(ts), (ctypes.c_float * m)(*ws), (ctypes.c_int32 * m)(*gof), m,
+                  n, *_mixed_ctypes(*cols), _ptrs(dsts), len(live),
+                  (ctypes.c_int64 * T)(*[t.numel() for t in live[0][2]]), T, codec._stream(dev))
+    return _mixed_done(m)
+
+
+def fold_mixed_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequence[float],
+                                grads: Sequence[torch.Tensor], params: Optional[Sequence[torch.Tensor]] = None,
+                                param_srcs: Optional[Sequence[Sequence[torch.Tensor]]] = None,
+                                w_params: Optional[Sequence[float]] = None, inertia: float = 0.0) -> bool:
+    """:func:`fold_gradient_records` for a :func:`mixed_round` of gradients: ``grads = Σ_m w_grads[m]·decode_m(message_m)``
+    from +0 in message order and, with ``params``, ``θ = θ·inertia + Σ_m w_params[m]·param_srcs[m]`` — one
+    ``flc_avg_and_gradient_mixed_records`` pass.  False (nothing launched) when a tensor is not a contiguous fp32 tensor
+    of the gradients' HIP device holding the messages' element count; records and parameter sources elsewhere are
+    moved."""
+    gs = list(grads)
+    n, m = deltas[0].n, len(deltas)
+    ps = srcs = None
+    if params is not None:
+        ps = [p.data if isinstance(p, torch.nn.Parameter) else p for p in params]
+    dev = _server_ok([gs] + ([ps] if ps is not None else []), n)
+    if dev is None:
+        return False
+    if ps is not None:
+        srcs = [[t.detach() if t.device == dev else t.detach().to(dev) for t in r] for r in param_srcs]
+        if len(srcs) != m or _server_ok([gs] + srcs, n) is None:
+            return False
+    ts, *desc = _mixed_tables(deltas, dev)
+    T = len(gs)
+    fl = lambda ws: (ctypes.c_float * m)(*[float(w) for w in ws])  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.call("flc_avg_and_gradient_mixed_records", _ptrs(ps) if ps is not None else None, _ptrs(gs),
+                  _ptrs([t for r in srcs for t in r]) if srcs is not None else None, _ptrs(ts),
+                  fl(w_params) if ps is not None else None, fl(w_grads), m, n, *_mixed_ctypes(*desc),
+                  (ctypes.c_int64 * T)(*[g.numel() for g in gs]), T, float(inertia), codec._stream(dev))
+    return _mixed_done(m)
 
 
 def _compressors_of(node, name: str = "compressors") -> List[Compressor]:

@@ -10,6 +10,7 @@
 //   fold_records              flc_fedopt_fold_records: the server update of a round of stacked records
 //   fold_dense_records        flc_fedopt_fold_dense_records: the same for dense records
 //   fold_sparse_records       flc_fedopt_fold_sparse_records: the same for sparse (top-k / rand-k) records
+//   fold_mixed_records        flc_fedopt_fold_mixed_records: the same for a round whose records differ in codec
 //   fold_record_groups        flc_fold_record_groups: a round of records folded into several models
 //   stacked_delta_record      flc_stacked_encode_delta into a wire record + flc_delta_count_nonzero_at
 //   stacked_records_round     flc_stacked_encode_round into the rows of a record block
@@ -730,6 +731,92 @@ PyObject* fold_dense_records(PyObject*, PyObject* args) {
   return fold_records_of(recs, weights, n, 0, format, levels, bits, delta, theta, v, beta0, opt, lr, beta2, tau);
 }
 
+// A sequence of `want` Python ints into *out; false with the error set (TypeError for another length).
+template <class T>
+bool int_row(Refs& refs, PyObject* o, Py_ssize_t want, std::vector<T>* out) {
+  PyObject* f = refs.fast(o, "fold_mixed_records takes sequences");
+  if (!f) return false;
+  if (len(f) != want) {
+    type_error("one kind, k, format, levels and bits per record");
+    return false;
+  }
+  out->resize(want);
+  for (Py_ssize_t c = 0; c < want; ++c) {
+    const long long x = PyLong_AsLongLong(items(f)[c]);
+    if (x == -1 && PyErr_Occurred()) return false;
+    (*out)[c] = (T)x;
+  }
+  return true;
+}
+
+// fold_mixed_records(records, weights, n, kinds, ks, formats, levels, bits, delta, theta, v, beta0, opt, lr, beta2,
+// tau): the server update of a round whose records differ in codec (flc_fedopt_fold_mixed_records) on Python lists —
+// one descriptor (flc_record_kind, k, format, levels, bits) per record; a FLC_REC_FLAT record is the message's decoded
+// fp32 vector of n elements.  TypeError (nothing launched) when a tensor is not what the pass takes, as fold_records
+// raises it: the server tensors contiguous fp32 HIP tensors of one device summing to n, every record a 16-B aligned
+// tensor on that device holding its own layout's bytes (uint8) or the n elements (fp32).
+PyObject* fold_mixed_records(PyObject*, PyObject* args) {
+  PyObject *recs, *weights, *kinds, *ks, *fmts, *lvs, *bts, *delta, *theta, *v;
+  long long n;
+  int opt;
+  double beta0, lr, beta2, tau;
+  if (!PyArg_ParseTuple(args, "OOLOOOOOOOOdiddd", &recs, &weights, &n, &kinds, &ks, &fmts, &lvs, &bts, &delta, &theta, &v,
+                        &beta0, &opt, &lr, &beta2, &tau))
+    return nullptr;
+  Refs refs;
+  PyObject* seqs[3] = {recs, weights, delta};
+  PyObject* f[3];
+  for (int i = 0; i < 3; ++i)
+    if (!(f[i] = refs.fast(seqs[i], "fold_mixed_records takes sequences"))) return nullptr;
+  const Py_ssize_t nr = len(f[0]), nt = len(f[2]);
+  if (len(f[1]) != nr) return value_error("one weight per record");
+  if (nr < 1 || nt < 1) return type_error("fold_mixed_records needs records and server tensors");
+  std::vector<int32_t> kd, fm, lv, bt;
+  std::vector<int64_t> kk;
+  if (!int_row(refs, kinds, nr, &kd) || !int_row(refs, ks, nr, &kk) || !int_row(refs, fmts, nr, &fm) ||
+      !int_row(refs, lvs, nr, &lv) || !int_row(refs, bts, nr, &bt))
+    return nullptr;
+  int dev = -1;
+  std::vector<float*> dp(nt), tp, vp;
+  std::vector<int64_t> sz(nt);
+  if (tensor_row(items(f[2]), nt, &dev, sz.data(), true, dp.data()))
+    return type_error("server tensors must be contiguous fp32 HIP tensors on one device");
+  int64_t total = 0;
+  for (int64_t s : sz) total += s;
+  if (total != n) return type_error("the server tensors do not hold the records' element count");
+  if (!optimizer_rows(refs, theta, v, nt, &dev, sz.data(), true, &tp, &vp)) return nullptr;
+  std::vector<const void*> rp(nr);
+  std::vector<float> w(nr);
+  for (Py_ssize_t c = 0; c < nr; ++c) {
+    if (kd[c] == FLC_REC_FLAT) {
+      int64_t want = n;
+      const float* x = nullptr;
+      if (take(items(f[0])[c], &dev, &want, false, &x) || reinterpret_cast<uintptr_t>(x) % 16 != 0)
+        return type_error("a flat record must be a 16-B aligned contiguous fp32 HIP tensor of n elements on the server's device");
+      rp[c] = x;
+    } else {
+      int64_t off[4];
+      size_t stride = 0;
+      if (kd[c] == FLC_REC_STACKED) stride = flc_stacked_wire_layout(n, kk[c], off);
+      else if (kd[c] == FLC_REC_SPARSE) stride = flc_sparse_wire_layout(n, kk[c], off);
+      else if (kd[c] == FLC_REC_DENSE) stride = flc_dense_wire_layout(n, fm[c], bt[c], off);
+      if (stride == 0) return value_error("bad wire shape");
+      if (!(rp[c] = record_ptr(items(f[0])[c], stride, &dev)))
+        return type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the server's device");
+    }
+    if (!as_f32(items(f[1])[c], &w[c])) return nullptr;
+  }
+  float* const* thp = tp.empty() ? nullptr : tp.data();
+  float* const* vvp = vp.empty() ? nullptr : vp.data();
+  if (!on_device(dev, "flc_fedopt_fold_mixed_records", [&](void* st) {
+        return flc_fedopt_fold_mixed_records(rp.data(), w.data(), (int)nr, n, kd.data(), kk.data(), fm.data(), lv.data(),
+                                             bt.data(), dp.data(), thp, vvp, sz.data(), (int)nt, (float)beta0, opt, lr,
+                                             beta2, tau, st);
+      }))
+    return nullptr;
+  Py_RETURN_NONE;
+}
+
 // fold_record_groups(records, weights, dsts, n, k, levels): a round whose stacked records fall into groups, each
 // folded in place into its own model (flc_fold_record_groups) on Python lists — records / weights / dsts hold one
 // sequence per group (SCAFFOLD: θ and c; IFCA: the clusters with messages).  TypeError (nothing launched) when a tensor
@@ -956,6 +1043,9 @@ PyMethodDef kMethods[] = {
     {"fold_sparse_records", fold_sparse_records, METH_VARARGS,
      "fold_sparse_records(records, weights, n, k, delta, theta, v, beta0, opt, lr, beta2, tau): "
      "flc_fedopt_fold_sparse_records on Python lists"},
+    {"fold_mixed_records", fold_mixed_records, METH_VARARGS,
+     "fold_mixed_records(records, weights, n, kinds, ks, formats, levels, bits, delta, theta, v, beta0, opt, lr, beta2, "
+     "tau): flc_fedopt_fold_mixed_records on Python lists (one descriptor per record)"},
     {"fold_record_groups", fold_record_groups, METH_VARARGS,
      "fold_record_groups(records, weights, dsts, n, k, levels): flc_fold_record_groups on Python lists (one sequence "
      "per group)"},

@@ -44,6 +44,11 @@
 // flc_fedopt_fold_dense_records (ModelIO) and flc_fold_dense_record_groups (GroupIO) are the stacked entry points'
 // counterparts, and flc_avg_and_gradient_dense_records (PairIO) is flc_avg_and_gradient_records': a variance-reduced
 // round's dense gradient records folded into the gradients, the dense parameters into the model in the same pass.
+//
+// Mixed rounds (flc_record_kind): every record carries its own descriptor — kind, k, format, levels, bits — or is the
+// decoded fp32 vector itself, and mixed_fold_records_kernel (below the entry-fold launcher) folds them in message order
+// in one pass with the same IO policies: flc_fedopt_fold_mixed_records (ModelIO), flc_fold_mixed_record_groups
+// (GroupIO) and flc_avg_and_gradient_mixed_records (PairIO), through the uniform entry points' host code.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -817,6 +822,445 @@ int launch_entry_fold(const char* probe, RecordKind kind, bool sparse, dim3 grid
 #undef FLC_EF
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Mixed rounds: every record of the launch carries its own descriptor (flc_record_kind, k, format, levels, bits), so a
+// round whose clients chose different codecs — or one whose message is the decoded fp32 vector — folds in one pass.
+// One wave per tile, the accumulator in registers as IO::load lays it out (the register-accumulator form: every
+// record's fma reaches every element, so no -0 replay is needed).  The launch's records are walked in message order as
+// RUNS of one class; the class of a run is wave-uniform, so every branch on it is scalar:
+//   entry run   stacked and sparse records (any k, any levels): stacked_fold_wires_kernel's dense form with the layout,
+//               the entry codec and the levels per lane — one load batch for <= 128 entries over the run's records,
+//               else the per-record loop; scattered into the zeroed LDS tile, read back densely, cleared again
+//   dense run   dithering records of one code width (any format and levels: the level table is per record) or natural-
+//               compressor records: dense_fold_records_kernel's load batch, then the ordered chain
+//   flat run    decoded fp32 vectors: the batch's float4 groups loaded, then the ordered chain
+// The level tables — one per distinct (format, levels, bits) of the launch, at most kMaxTabs (the host ends a launch
+// before a record that would need one more) — are built in LDS once per block; a stacked record's (levels, step) take a
+// table entry without LDS values (stacked_dequant evaluates its level in fp64).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kMaxTabs = 8;
+constexpr int kTabStacked = 3;  // tab_fmt of a stacked record's (levels, step) entry (0 / 1: the dithering formats)
+enum MixedClass : uint8_t {
+  kClsStacked = 0,
+  kClsSparse = 1,
+  kClsQ8 = 2,
+  kClsQ4 = 3,
+  kClsQ2 = 4,
+  kClsN16 = 5,
+  kClsFlat = 6
+};
+struct MixedDesc {
+  double tab_step[kMaxTabs];  // 1 / levels in fp64, as the uniform entry points pass it
+  unsigned k[kMaxWires];      // entries of a stacked or sparse record
+  uint8_t cls[kMaxWires];     // MixedClass
+  uint8_t tab[kMaxWires];     // the record's table entry (stacked and dithering records)
+  uint8_t tab_fmt[kMaxTabs], tab_levels[kMaxTabs], tab_bits[kMaxTabs];
+  int ntab;
+};
+
+__device__ __forceinline__ int run_class(int cls) { return cls <= kClsSparse ? 0 : cls; }
+
+// wire_layout's / sparse_wire_layout's field offsets from the record's own k
+struct EntryOffsets {
+  long long idx, codes, tiles;
+};
+__device__ __forceinline__ EntryOffsets entry_offsets(bool sparse, unsigned k) {
+  EntryOffsets o;
+  const long long k4 = 4ll * (long long)k;
+  if (sparse) {
+    o.idx = 0;
+    o.codes = (k4 + 15ll) & ~15ll;
+    o.tiles = (o.codes + k4 + 15ll) & ~15ll;
+  } else {
+    o.idx = 16;
+    o.codes = (16ll + k4 + 15ll) & ~15ll;
+    o.tiles = (o.codes + (long long)(k > 16u ? k : 16u) + 15ll) & ~15ll;
+  }
+  return o;
+}
+__device__ __forceinline__ unsigned entry_raw(const uint8_t* rc, bool sparse, const EntryOffsets& o, unsigned j) {
+  return sparse ? reinterpret_cast<const unsigned*>(rc + o.codes)[j] : (unsigned)rc[o.codes + j];
+}
+__device__ __forceinline__ float entry_value(const MixedDesc& d, bool sparse, unsigned slot, unsigned raw, float nrm) {
+  if (sparse) return __uint_as_float(raw);
+  return stacked_dequant(raw, (int)d.tab_levels[slot], d.tab_step[slot], nrm);  // compressors.py:357
+}
+
+// records [r0, r0 + rn) of the launch, all stacked or sparse: lane c holds record r0 + c
+__device__ __forceinline__ void mixed_entry_run(const FoldArgs& a, const MixedDesc& d, int r0, int rn, int64_t t,
+                                                int64_t t0, int lane, float* s_tile, float4 acc[4]) {
+  float4* tile4 = reinterpret_cast<float4*>(s_tile);
+  const uint8_t* rec = nullptr;
+  unsigned lo = 0, cnt = 0, kk = 0, meta = 0;  // meta: bit 0 sparse, bits 1.. the table entry
+  float nrm = 0.0f, wl = 0.0f;
+  if (lane < rn) {
+    const int r = r0 + lane;
+    rec = a.rec[r];
+    wl = a.w[r];
+    kk = d.k[r];
+    const bool sp = d.cls[r] == kClsSparse;
+    meta = (sp ? 1u : 0u) | ((unsigned)d.tab[r] << 1);
+    const EntryOffsets o = entry_offsets(sp, kk);
+    const unsigned* tiles = reinterpret_cast<const unsigned*>(rec + o.tiles);
+    // (clamped to the record's own k entries: a malformed or unwritten tile pointer never reads past the record)
+    lo = min(tiles[t], kk);
+    const unsigned hi = min(tiles[t + 1], kk);
+    cnt = hi > lo ? hi - lo : 0u;
+    nrm = sp ? 0.0f : *reinterpret_cast<const float*>(rec);
+  }
+  const unsigned incl = wave_incl_scan(cnt);
+  const unsigned excl = incl - cnt;
+  const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, kWave - 1);
+  const unsigned long long rp = (unsigned long long)(uintptr_t)rec;
+
+  if (total <= 2u * kWave) {
+    // every entry of the tile over the run's records in registers (g = lane, lane + 64), one load batch
+    int cg[2] = {-1, -1};
+    unsigned off[2] = {0u, 0u};
+    float val[2] = {0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const unsigned g = (unsigned)lane + (unsigned)(r * kWave);
+      int c = -1;
+      for (int cc = 0; cc < rn; ++cc) {  // (uniform loop; the record whose range holds g)
+        const unsigned ec = (unsigned)__builtin_amdgcn_readlane((int)excl, cc);
+        const unsigned nc = (unsigned)__builtin_amdgcn_readlane((int)cnt, cc);
+        if (g >= ec && g < ec + nc) c = cc;
+      }
+      cg[r] = g < total ? c : -1;
+    }
+    unsigned idx_raw[2] = {0u, 0u}, code[2] = {0u, 0u}, mt[2] = {0u, 0u};
+    float nr[2] = {0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int src = cg[r] < 0 ? 0 : cg[r];
+      const unsigned lo_c = (unsigned)__shfl((int)lo, src, kWave);
+      const unsigned ex_c = (unsigned)__shfl((int)excl, src, kWave);
+      const unsigned k_c = (unsigned)__shfl((int)kk, src, kWave);
+      const unsigned rlo = (unsigned)__shfl((int)(unsigned)rp, src, kWave);
+      const unsigned rhi = (unsigned)__shfl((int)(unsigned)(rp >> 32), src, kWave);
+      mt[r] = (unsigned)__shfl((int)meta, src, kWave);
+      nr[r] = __shfl(nrm, src, kWave);
+      if (cg[r] >= 0) {
+        const uint8_t* rc = reinterpret_cast<const uint8_t*>((uintptr_t)(((unsigned long long)rhi << 32) | rlo));
+        const bool sp = mt[r] & 1u;
+        const EntryOffsets o = entry_offsets(sp, k_c);
+        const unsigned j = lo_c + ((unsigned)lane + (unsigned)(r * kWave) - ex_c);  // (< the record's k: lo, hi clamped)
+        idx_raw[r] = reinterpret_cast<const unsigned*>(rc + o.idx)[j];
+        code[r] = entry_raw(rc, sp, o, j);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int64_t o = (int64_t)idx_raw[r] - t0;
+      if (cg[r] >= 0 && (o < 0 || o >= FLC_TILE)) cg[r] = -1;  // (a malformed wire: ignored, never out of the tile)
+      off[r] = (unsigned)(o < 0 ? 0 : (o >= FLC_TILE ? 0 : o));
+      val[r] = entry_value(d, mt[r] & 1u, mt[r] >> 1, code[r], nr[r]);
+    }
+    for (int c = 0; c < rn; ++c) {  // the ordered fold
+      const float wc = __shfl(wl, c, kWave);
+      const bool any = __builtin_amdgcn_readlane((int)cnt, c) != 0;
+      if (any) {
+        if (cg[0] == c) s_tile[off[0]] = val[0];
+        if (cg[1] == c) s_tile[off[1]] = val[1];
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float4 v = tile4[lane + u * kWave];
+          acc[u] = make_float4(fmaf(wc, v.x, acc[u].x), fmaf(wc, v.y, acc[u].y), fmaf(wc, v.z, acc[u].z),
+                               fmaf(wc, v.w, acc[u].w));
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (cg[0] == c) s_tile[off[0]] = 0.0f;
+        if (cg[1] == c) s_tile[off[1]] = 0.0f;
+      } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          acc[u] = make_float4(fmaf(wc, 0.0f, acc[u].x), fmaf(wc, 0.0f, acc[u].y), fmaf(wc, 0.0f, acc[u].z),
+                               fmaf(wc, 0.0f, acc[u].w));
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  } else {
+    // dense tiles: per record, its entries in rounds of 64, scattered, folded, cleared
+    for (int c = 0; c < rn; ++c) {
+      const float wc = __shfl(wl, c, kWave);
+      const unsigned lo_c = (unsigned)__builtin_amdgcn_readlane((int)lo, c);
+      const unsigned n_c = (unsigned)__builtin_amdgcn_readlane((int)cnt, c);
+      const unsigned k_c = (unsigned)__builtin_amdgcn_readlane((int)kk, c);
+      const unsigned mt_c = (unsigned)__builtin_amdgcn_readlane((int)meta, c);
+      const float nr_c = __shfl(nrm, c, kWave);
+      const unsigned rlo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)rp, c);
+      const unsigned rhi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(rp >> 32), c);
+      const uint8_t* rc = reinterpret_cast<const uint8_t*>((uintptr_t)(((unsigned long long)rhi << 32) | rlo));
+      const bool sp = mt_c & 1u;
+      const EntryOffsets o = entry_offsets(sp, k_c);
+      const unsigned* ix = reinterpret_cast<const unsigned*>(rc + o.idx);
+      for (unsigned j = lo_c + lane; j < lo_c + n_c; j += kWave) {
+        const int64_t e = (int64_t)ix[j] - t0;
+        if (e >= 0 && e < FLC_TILE) s_tile[e] = entry_value(d, sp, mt_c >> 1, entry_raw(rc, sp, o, j), nr_c);
+      }
+      __builtin_amdgcn_wave_barrier();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float4 v = tile4[lane + u * kWave];
+        acc[u] = make_float4(fmaf(wc, v.x, acc[u].x), fmaf(wc, v.y, acc[u].y), fmaf(wc, v.z, acc[u].z),
+                             fmaf(wc, v.w, acc[u].w));
+      }
+      __builtin_amdgcn_wave_barrier();
+      for (unsigned j = lo_c + lane; j < lo_c + n_c; j += kWave) {
+        const int64_t e = (int64_t)ix[j] - t0;
+        if (e >= 0 && e < FLC_TILE) s_tile[e] = 0.0f;
+      }
+      __builtin_amdgcn_wave_barrier();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+  }
+}
+
+// records [r0, r0 + rn) of the launch, all dense records of BITS-bit codes (16: the natural compressor's):
+// dense_fold_records_kernel's batches, the level table by the record
+template <int BITS>
+__device__ __forceinline__ void mixed_dense_run(const FoldArgs& a, const MixedDesc& d, int r0, int rn,
+                                                const float* s_lvt, int64_t n, int64_t t0, int lane, float4 acc[4]) {
+  typedef typename Quad<BITS>::type Q;
+  constexpr int kBatch = BITS == 16 ? 8 : 16;
+  for (int c0 = 0; c0 < rn; c0 += kBatch) {
+    Q cw[kBatch][4];
+    float nr[kBatch];
+#pragma unroll
+    for (int i = 0; i < kBatch; ++i) {
+      nr[i] = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) cw[i][u] = Q{};
+      if (c0 + i < rn) {
+        const uint8_t* __restrict__ rc = a.rec[r0 + c0 + i];
+        if constexpr (BITS != 16) nr[i] = *reinterpret_cast<const float*>(rc + kDenseNorm);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int64_t e = t0 + 4 * (int64_t)(lane + u * kWave);
+          if (e < n) cw[i][u] = load_quad<BITS>(rc + kDenseCodes, e);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < kBatch; ++i) {
+      if (c0 + i >= rn) continue;  // (uniform)
+      const float wc = a.w[r0 + c0 + i];
+      const float nrm = nr[i];
+      const bool regular = norm_regular(nrm);
+      const float* lvt = s_lvt + 128 * (int)d.tab[r0 + c0 + i];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t code = quad_code<BITS>(cw[i][u], j);
+          if constexpr (BITS == 16) {
+            v[j] = natural_value(code);
+          } else if (!regular) {
+            v[j] = code == 0u ? 0.0f : __uint_as_float(0x7fc00000u);
+          } else {
+            const float lv = lvt[code & ((1u << (BITS - 1)) - 1u)];
+            const float sv = (code >> (BITS - 1)) ? -lv : lv;  // fp32(lv) * sign, -0 kept
+            v[j] = sv * nrm;                                   // compressors.py:357 (rounded before the fma)
+          }
+        }
+        acc[u] = make_float4(fmaf(wc, v[0], acc[u].x), fmaf(wc, v[1], acc[u].y), fmaf(wc, v[2], acc[u].z),
+                             fmaf(wc, v[3], acc[u].w));
+      }
+    }
+  }
+}
+
+// records [r0, r0 + rn) of the launch, all decoded fp32 vectors of n elements
+__device__ __forceinline__ void mixed_flat_run(const FoldArgs& a, int r0, int rn, int64_t n, int64_t t0, int lane,
+                                               float4 acc[4]) {
+  constexpr int kBatch = 4;
+  for (int c0 = 0; c0 < rn; c0 += kBatch) {
+    float4 fv[kBatch][4];
+#pragma unroll
+    for (int i = 0; i < kBatch; ++i) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) fv[i][u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c0 + i < rn) {
+        const float* __restrict__ x = reinterpret_cast<const float*>(a.rec[r0 + c0 + i]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int64_t e = t0 + 4 * (int64_t)(lane + u * kWave);
+          if (e + 4 <= n) {
+            fv[i][u] = *reinterpret_cast<const float4*>(x + e);
+          } else {  // (the vector's last elements; those at or beyond n are never stored)
+            if (e < n) fv[i][u].x = x[e];
+            if (e + 1 < n) fv[i][u].y = x[e + 1];
+            if (e + 2 < n) fv[i][u].z = x[e + 2];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < kBatch; ++i) {
+      if (c0 + i >= rn) continue;  // (uniform)
+      const float wc = a.w[r0 + c0 + i];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        acc[u] = make_float4(fmaf(wc, fv[i][u].x, acc[u].x), fmaf(wc, fv[i][u].y, acc[u].y),
+                             fmaf(wc, fv[i][u].z, acc[u].z), fmaf(wc, fv[i][u].w, acc[u].w));
+    }
+  }
+}
+
+template <class IO>
+__global__ __launch_bounds__(kWave) void mixed_fold_records_kernel(FoldArgs a, MixedDesc d, int nw_all, int64_t n,
+                                                                   int64_t tile0, IO io) {
+  __shared__ __attribute__((aligned(16))) float s_tile[FLC_TILE];
+  __shared__ float s_lvt[kMaxTabs * 128];
+  float4* tile4 = reinterpret_cast<float4*>(s_tile);
+  const int lane = threadIdx.x;
+  for (int tb = 0; tb < d.ntab; ++tb) {  // the launch's level tables (dense_fold_records_kernel's s_lvt, one per codec)
+    const int fmt = d.tab_fmt[tb], s = d.tab_levels[tb];
+    if (fmt == kTabStacked) continue;
+    const int nl = 1 << ((int)d.tab_bits[tb] - 1);
+    const double step = d.tab_step[tb];
+    for (int i = lane; i < nl; i += kWave)
+      s_lvt[tb * 128 + i] =
+          fmt == FLC_Q_STANDARD_DITHER ? (float)level_value<0>(i, s, step) : (float)level_value<1>(i, s, step);
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) tile4[lane + u * kWave] = make_float4(0.f, 0.f, 0.f, 0.f);
+  __syncthreads();
+  // the block's records: the whole launch's, or (a grouped launch) its group's slice of them
+  int nw = nw_all, rec0 = 0;
+  if constexpr (IO::kGrouped) {
+    nw = io.count();
+    rec0 = io.first();
+  }
+  const int64_t t = tile0 + blockIdx.x;
+  const int64_t t0 = t * FLC_TILE;
+  float4 acc[4];
+  io.load(t0, lane, acc);
+  int c = rec0;
+  const int end = rec0 + nw;
+  while (c < end) {
+    const int cls = d.cls[c], rcl = run_class(cls);
+    int e = c + 1;
+    while (e < end && run_class(d.cls[e]) == rcl) ++e;
+    if (rcl == 0) mixed_entry_run(a, d, c, e - c, t, t0, lane, s_tile, acc);
+    else if (cls == kClsQ8) mixed_dense_run<8>(a, d, c, e - c, s_lvt, n, t0, lane, acc);
+    else if (cls == kClsQ4) mixed_dense_run<4>(a, d, c, e - c, s_lvt, n, t0, lane, acc);
+    else if (cls == kClsQ2) mixed_dense_run<2>(a, d, c, e - c, s_lvt, n, t0, lane, acc);
+    else if (cls == kClsN16) mixed_dense_run<16>(a, d, c, e - c, s_lvt, n, t0, lane, acc);
+    else mixed_flat_run(a, c, e - c, n, t0, lane, acc);
+    c = e;
+  }
+  io.store(t0, lane, acc);
+}
+
+template <class IO>
+int launch_mixed_fold(const char* probe, dim3 grid, hipStream_t st, const FoldArgs& a, const MixedDesc& d, int nw,
+                      int64_t n, int64_t tile0, const IO& io) {
+  FLC_LAUNCH(probe, (mixed_fold_records_kernel<IO>), grid, dim3(kWave), 0, st, a, d, nw, n, tile0, io);
+  return FLC_OK;
+}
+
+// A mixed round's descriptor arrays (checked by check_mixed_round) as the impls below take them
+struct MixedRound {
+  const int32_t* kinds;
+  const int64_t* ks;
+  const int32_t* formats;
+  const int32_t* levels;
+  const int32_t* bits;
+};
+
+// every record's own argument rule: its uniform entry point's, record by record
+int check_mixed_round(const char* fn, const void* const* records, const MixedRound& mx, int n_records, int64_t n) {
+  if (n_records > 0 && (!records || !mx.kinds || !mx.ks || !mx.formats || !mx.levels || !mx.bits))
+    return fail(FLC_EINVAL, "%s: a null descriptor table", fn);
+  if (n <= 0 || n >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n must be in [1, 2^31)", fn);
+  for (int c = 0; c < n_records; ++c) {
+    if (!records[c] || !aligned16(records[c]))
+      return fail(FLC_EINVAL, "%s: record %d is null or not 16-B aligned", fn, c);
+    switch (mx.kinds[c]) {
+      case FLC_REC_STACKED:
+        if (mx.levels[c] < 1 || mx.levels[c] > 127)
+          return fail(FLC_EINVAL, "%s: record %d: levels must be in [1, 127]", fn, c);
+        [[fallthrough]];
+      case FLC_REC_SPARSE:
+        if (mx.ks[c] < 1 || mx.ks[c] > n)
+          return fail(FLC_EINVAL, "%s: record %d: k %lld outside [1, n = %lld]", fn, c, (long long)mx.ks[c],
+                      (long long)n);
+        break;
+      case FLC_REC_DENSE:
+        if (int rc = check_dense_format(fn, mx.formats[c], mx.levels[c], mx.bits[c])) return rc;
+        break;
+      case FLC_REC_FLAT:
+        break;
+      default:
+        return fail(FLC_EINVAL, "%s: record %d: unknown kind %d", fn, c, (int)mx.kinds[c]);
+    }
+  }
+  return FLC_OK;
+}
+
+// record `c` of the round as entry `pos` of a launch's descriptor; false when it needs a table entry and none is left
+bool mixed_take(const MixedRound& mx, int c, MixedDesc* d, int pos) {
+  int fmt = -1, lv = 0, bits = 8;
+  uint8_t cls = kClsFlat;
+  d->k[pos] = 0u;
+  switch (mx.kinds[c]) {
+    case FLC_REC_STACKED:
+      cls = kClsStacked;
+      fmt = kTabStacked;
+      lv = mx.levels[c];
+      d->k[pos] = (unsigned)mx.ks[c];
+      break;
+    case FLC_REC_SPARSE:
+      cls = kClsSparse;
+      d->k[pos] = (unsigned)mx.ks[c];
+      break;
+    case FLC_REC_DENSE:
+      if (mx.formats[c] == kFmtNatural) {
+        cls = kClsN16;
+      } else {
+        cls = mx.bits[c] == 8 ? kClsQ8 : mx.bits[c] == 4 ? kClsQ4 : kClsQ2;
+        fmt = mx.formats[c];
+        lv = mx.levels[c];
+        bits = mx.bits[c];
+      }
+      break;
+    default:
+      break;
+  }
+  int slot = 0;
+  if (fmt >= 0) {
+    for (slot = 0; slot < d->ntab; ++slot)
+      if (d->tab_fmt[slot] == fmt && d->tab_levels[slot] == lv && d->tab_bits[slot] == bits) break;
+    if (slot == d->ntab) {
+      if (d->ntab == kMaxTabs) return false;
+      d->tab_fmt[slot] = (uint8_t)fmt;
+      d->tab_levels[slot] = (uint8_t)lv;
+      d->tab_bits[slot] = (uint8_t)bits;
+      d->tab_step[slot] = 1.0 / (double)lv;
+      ++d->ntab;
+    }
+  }
+  d->cls[pos] = cls;
+  d->tab[pos] = (uint8_t)slot;
+  return true;
+}
+
+// the launch's records from round position c0: at most `cap`, fewer when the tables run out; their count (>= 1 for
+// cap >= 1: one record needs at most one table entry)
+int mixed_chunk(const MixedRound& mx, int c0, int cap, MixedDesc* d) {
+  *d = MixedDesc{};
+  int nw = 0;
+  while (nw < cap && mixed_take(mx, c0 + nw, d, nw)) ++nw;
+  return nw;
+}
+
 }  // namespace
 }  // namespace flc
 
@@ -904,16 +1348,20 @@ int flc_fold_sparse_wires(const void* wires, int64_t stride, const int32_t* slot
 // (dense == NULL, kRecSparse: sparse records of (n, k)) and flc_fedopt_fold_dense_records (the records of *dense): one
 // argument check, one chain of launches, the kernel by the records' codec.  `fn` names the entry point in messages,
 // `probe` its launches for flc_probe_set.
+// (mx != NULL: flc_fedopt_fold_mixed_records — the records' own descriptors, checked by the caller, in place of the
+// launch-wide codec; a launch ends at 64 records or where its level tables run out)
 static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec* dense, RecordKind kind,
                             const void* const* records,
                             const float* weights, int n_records, int64_t n, int64_t k, int levels,
                             float* const* delta, float* const* theta, float* const* v, const int64_t* sizes,
-                            int n_tensors, float beta0, int opt, double lr, double beta2, double tau, void* stream) {
+                            int n_tensors, float beta0, int opt, double lr, double beta2, double tau, void* stream,
+                            const MixedRound* mx = nullptr) {
   if (n_records < 0 || (n_records > 0 && (!records || !weights)) || n <= 0 || k < 0 || n_tensors < 1 || !delta ||
       !sizes)
     return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
-  if (dense) {
+  if (mx) {
+  } else if (dense) {
     if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
   } else if (int rc = check_entry_codec(fn, kind, n, k, levels)) {
     return rc;
@@ -944,7 +1392,9 @@ static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec*
   // chunk, one launch per group of <= kRoundT tensors over the tiles their flat range touches
   int c0 = 0;
   do {
-    const int nw = std::min(kMaxWires, n_records - c0);
+    int nw = std::min(kMaxWires, n_records - c0);
+    MixedDesc md;
+    if (mx) nw = mixed_chunk(*mx, c0, nw, &md);
     const bool last = c0 + nw >= n_records;
     FoldArgs a;
     for (int c = 0; c < kMaxWires; ++c) {
@@ -980,7 +1430,9 @@ static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec*
       const dim3 grid((unsigned)(tile_hi - tile_lo));
 #define FLC_FR(O)                                                                                                 \
   do {                                                                                                            \
-    if (dense) {                                                                                                  \
+    if (mx) {                                                                                                     \
+      if (int rc = launch_mixed_fold(probe, grid, st, a, md, nw, n, tile_lo, ModelIO<O>{m})) return rc;           \
+    } else if (dense) {                                                                                           \
       if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, ModelIO<O>{m})) return rc;          \
     } else if (int rc = launch_entry_fold(probe, kind, false, grid, st, a, L, nw, levels, step, tile_lo,          \
                                           ModelIO<O>{m}, (unsigned)k)) {                                          \
@@ -1033,14 +1485,15 @@ static int avg_and_gradient_impl(const char* fn, const char* probe, const DenseC
                                  float* const* params, float* const* grads, const float* const* param_srcs,
                                  const void* const* grad_records, const float* w_params, const float* w_grads,
                                  int n_src, int64_t n, int64_t k, int levels, const int64_t* sizes, int n_tensors,
-                                 float inertia, void* stream) {
+                                 float inertia, void* stream, const MixedRound* mx = nullptr) {
   const bool p_on = param_srcs != nullptr;
   if (n_src < 1 || !grad_records || !w_grads || n <= 0 || k < 0 || n_tensors < 1 || !grads || !sizes ||
       (p_on && (!params || !w_params)))
     return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (n >= (1ll << 31) || k >= (1ll << 31))
     return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
-  if (dense) {
+  if (mx) {
+  } else if (dense) {
     if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
   } else if (int rc = check_entry_codec(fn, kind, n, k, levels)) {
     return rc;
@@ -1073,11 +1526,17 @@ static int avg_and_gradient_impl(const char* fn, const char* probe, const DenseC
   for (int c = 0; c < n_src; ++c) sparse = sparse && std::isfinite(w_grads[c]);
   // launch i of the chain folds records [64 i, 64 i + 64) and parameter sources [16 i, 16 i + 16), each chain
   // continuing from its stored partial result; within it, one launch per group of <= kRoundT tensors
-  const int r_launches = (int)cdiv((int64_t)n_src, (int64_t)kMaxWires);
+  // (a mixed round: a record launch ends at 64 records or where its level tables run out — `cuts` holds the starts)
+  std::vector<int> cuts;
+  MixedDesc md;
+  if (mx)
+    for (int c = 0; c < n_src; c += mixed_chunk(*mx, c, std::min(kMaxWires, n_src - c), &md)) cuts.push_back(c);
+  const int r_launches = mx ? (int)cuts.size() : (int)cdiv((int64_t)n_src, (int64_t)kMaxWires);
   const int p_launches = p_on ? (int)cdiv((int64_t)n_src, (int64_t)kPairSrc) : 0;
   for (int i = 0; i < std::max(r_launches, p_launches); ++i) {
-    const int c0 = i * kMaxWires, s0 = i * kPairSrc;
-    const int nw = i < r_launches ? std::min(kMaxWires, n_src - c0) : 0;
+    const int c0 = mx ? (i < r_launches ? cuts[i] : n_src) : i * kMaxWires, s0 = i * kPairSrc;
+    int nw = i < r_launches ? std::min(kMaxWires, n_src - c0) : 0;
+    if (mx) nw = mixed_chunk(*mx, c0, nw, &md);
     const int ns = i < p_launches ? std::min(kPairSrc, n_src - s0) : 0;
     FoldArgs a;
     for (int c = 0; c < kMaxWires; ++c) {
@@ -1115,7 +1574,9 @@ static int avg_and_gradient_impl(const char* fn, const char* probe, const DenseC
       m.start[m.nt] = off;
       const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
       const dim3 grid((unsigned)(tile_hi - tile_lo));
-      if (dense) {
+      if (mx) {
+        if (int rc = launch_mixed_fold(probe, grid, st, a, md, nw, n, tile_lo, io)) return rc;
+      } else if (dense) {
         if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, io)) return rc;
       } else if (int rc = launch_entry_fold(probe, kind, sparse, grid, st, a, L, nw, levels, step, tile_lo, io,
                                             (unsigned)k)) {
@@ -1160,12 +1621,13 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
                             const void* const* records,
                             const float* weights, const int32_t* group_of, int n_records, int64_t n, int64_t k,
                             int levels, float* const* dsts, int n_groups, const int64_t* sizes, int n_tensors,
-                            void* stream) {
+                            void* stream, const MixedRound* mx = nullptr) {
   if (n_records < 0 || (n_records > 0 && (!records || !weights || !group_of)) || n <= 0 || k < 0 || n_groups < 1 ||
       n_tensors < 1 || !dsts || !sizes)
     return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
-  if (dense) {
+  if (mx) {
+  } else if (dense) {
     if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
   } else if (int rc = check_entry_codec(fn, kind, n, k, levels)) {
     return rc;
@@ -1220,14 +1682,17 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
     GroupTab& m = io.m;
     int gsel[kMaxGroups];
     int nw = 0, ng = 0;
+    MixedDesc md{};
     // Sparse form (only the kept entries are fma'd, a -0 resolved as the dense chain resolves it) whenever every
     // weight of the launch is finite: from ANY stored accumulator a, fmaf(w, +0, a) with a finite w returns a itself
     // unless a is -0 and w's sign bit is clear — exactly skip_clients' rule (NaN stays NaN, ±inf stays ±inf).
     bool sparse = true;
     while (c0 + nw < n_records && nw < kMaxWires) {
       const int c = order[c0 + nw], g = group_of[c];
-      if (ng == 0 || gsel[ng - 1] != g) {
-        if (ng == kMaxGroups) break;
+      const bool opens = ng == 0 || gsel[ng - 1] != g;
+      if (opens && ng == kMaxGroups) break;
+      if (mx && !mixed_take(*mx, c, &md, nw)) break;  // (the launch's level tables are full: the next launch)
+      if (opens) {
         gsel[ng] = g;
         m.first[ng] = nw;
         m.count[ng] = 0;
@@ -1262,7 +1727,9 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
       m.start[m.nt] = off;
       const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
       const dim3 grid((unsigned)(tile_hi - tile_lo), (unsigned)ng);
-      if (dense) {
+      if (mx) {
+        if (int rc = launch_mixed_fold(probe, grid, st, a, md, nw, n, tile_lo, io)) return rc;
+      } else if (dense) {
         if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, io)) return rc;
       } else if (int rc = launch_entry_fold(probe, kind, sparse, grid, st, a, L, nw, levels, step, tile_lo, io,
                                             (unsigned)k)) {
@@ -1294,6 +1761,44 @@ int flc_fold_dense_record_groups(const void* const* records, const float* weight
   const DenseCodec cd{format, levels, bits, n};
   return fold_groups_impl("flc_fold_dense_record_groups", "fold_dense_record_groups", &cd, kRecStacked, records, weights,
                           group_of, n_records, n, 0, levels, dsts, n_groups, sizes, n_tensors, stream);
+}
+
+int flc_fedopt_fold_mixed_records(const void* const* records, const float* weights, int n_records, int64_t n,
+                                  const int32_t* kinds, const int64_t* ks, const int32_t* formats,
+                                  const int32_t* levels, const int32_t* bits, float* const* delta, float* const* theta,
+                                  float* const* v, const int64_t* sizes, int n_tensors, float beta0, int opt, double lr,
+                                  double beta2, double tau, void* stream) {
+  const char* fn = "flc_fedopt_fold_mixed_records";
+  const MixedRound mx{kinds, ks, formats, levels, bits};
+  if (n_records < 0) return fail(FLC_EINVAL, "%s: bad arguments", fn);
+  if (int rc = check_mixed_round(fn, records, mx, n_records, n)) return rc;
+  return fedopt_fold_impl(fn, "fedopt_fold_mixed_records", nullptr, kRecStacked, records, weights, n_records, n, 1, 1,
+                          delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau, stream, &mx);
+}
+
+int flc_fold_mixed_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
+                                 int n_records, int64_t n, const int32_t* kinds, const int64_t* ks,
+                                 const int32_t* formats, const int32_t* levels, const int32_t* bits, float* const* dsts,
+                                 int n_groups, const int64_t* sizes, int n_tensors, void* stream) {
+  const char* fn = "flc_fold_mixed_record_groups";
+  const MixedRound mx{kinds, ks, formats, levels, bits};
+  if (n_records < 0) return fail(FLC_EINVAL, "%s: bad arguments", fn);
+  if (int rc = check_mixed_round(fn, records, mx, n_records, n)) return rc;
+  return fold_groups_impl(fn, "fold_mixed_record_groups", nullptr, kRecStacked, records, weights, group_of, n_records,
+                          n, 1, 1, dsts, n_groups, sizes, n_tensors, stream, &mx);
+}
+
+int flc_avg_and_gradient_mixed_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                       const void* const* grad_records, const float* w_params, const float* w_grads,
+                                       int n_src, int64_t n, const int32_t* kinds, const int64_t* ks,
+                                       const int32_t* formats, const int32_t* levels, const int32_t* bits,
+                                       const int64_t* sizes, int n_tensors, float inertia, void* stream) {
+  const char* fn = "flc_avg_and_gradient_mixed_records";
+  const MixedRound mx{kinds, ks, formats, levels, bits};
+  if (n_src < 1 || !grad_records) return fail(FLC_EINVAL, "%s: bad arguments", fn);
+  if (int rc = check_mixed_round(fn, grad_records, mx, n_src, n)) return rc;
+  return avg_and_gradient_impl(fn, "avg_and_gradient_mixed_records", nullptr, kRecStacked, params, grads, param_srcs,
+                               grad_records, w_params, w_grads, n_src, n, 1, 1, sizes, n_tensors, inertia, stream, &mx);
 }
 
 size_t flc_dense_wire_layout(int64_t n, int format, int bits, int64_t* offsets) {

@@ -384,6 +384,66 @@ int flc_fold_dense_record_groups(const void* const* records, const float* weight
                                  float* const* dsts /* [n_groups][n_tensors] */, int n_groups, const int64_t* sizes,
                                  int n_tensors, void* stream);
 
+/* ------------------------------------------------------------------ mixed rounds (every record its own codec)
+ * A round whose clients chose different codecs — another K, another code width, another record kind, or a client that
+ * sends the decoded vector compressVector returns (compressors.py:267-410) — in ONE pass: each record carries its own
+ * descriptor in parallel HOST arrays of n_records entries,
+ *   records[c]  device pointer to the record, 16-B aligned; for FLC_REC_FLAT the fp32 vector of n elements
+ *   kinds[c]    flc_record_kind: FLC_REC_STACKED (flc_stacked_wire_layout(n, ks[c]), levels[c] in [1, 127]),
+ *               FLC_REC_SPARSE (flc_sparse_wire_layout(n, ks[c])), FLC_REC_DENSE (flc_dense_wire_layout(n, formats[c],
+ *               bits[c]) with levels[c], as flc_fold_dense_wires takes them), FLC_REC_FLAT
+ *   ks[c]       the K of a stacked or sparse record, in [1, n]; ignored otherwise
+ *   formats[c], levels[c], bits[c]   a dense record's; levels[c] a stacked record's too; ignored otherwise.
+ * Every element follows  a = init;  for c in message order:  a = fmaf(w_c, v_c[e], a)  with v_c[e] what record c's own
+ * decoder gives at e (stacked_dequant of the code byte, the sparse value, the dithering level times the norm, the
+ * natural compressor's power of two, the flat vector's element; +0 where a stacked or sparse record has no entry):
+ * bit-identical to decoding every record into a zeroed vector (flc_stacked_decode_tiled / flc_sparse_decode_tiled /
+ * flc_quant_decode / flc_natural_decode) and running the dense entry point named below — -0 accumulators, weights of
+ * either sign or zero, subnormal products, a norm that is 0, +-inf, NaN or negative (code 0 -> +0, any other code ->
+ * NaN) and empty tiles included.  One wave per FLC_TILE tile keeps the accumulator in registers and walks the records in
+ * message order as runs of one class (stacked / sparse entries scattered through an LDS tile; dense codes of one width;
+ * flat vectors), every tile pointer clamped to the record's own k.  Launches chain per 64 records (and per 8 distinct
+ * (format, levels, bits) / stacked levels), each continuing from the stored results.
+ * FLC_EINVAL (nothing launched): a null table or entry, an unknown kind, a record that is not 16-B aligned, k outside
+ * [1, n] (stacked, sparse), levels outside [1, 127] (stacked), a (format, levels, bits) flc_fold_dense_wires refuses,
+ * n >= 2^31, and every refusal of the uniform counterpart. */
+enum flc_record_kind { FLC_REC_STACKED = 0, FLC_REC_SPARSE = 1, FLC_REC_DENSE = 2, FLC_REC_FLAT = 3 };
+/* flc_fedopt_fold_records' contract over a mixed round (replaces FedOptServer.update, _fedopt.py:196-240, when the
+ * clients' messages carry their deltas under different codecs):
+ *   a = delta * beta0;  for c = 0 .. n_records-1:  a = fmaf(weights[c], decode_c(records[c]), a);  delta = a;
+ *   then, if theta != NULL, the optimiser's step (avg / adagrad / yogi / adam, as flc_model_fold), on the last launch.
+ * Bit-identical to decoding every record and running flc_model_fold with init_mode 0 and the step.  Arguments as
+ * flc_fedopt_fold_records', the descriptor arrays in place of (k, levels). */
+int flc_fedopt_fold_mixed_records(const void* const* records, const float* weights, int n_records, int64_t n,
+                                  const int32_t* kinds, const int64_t* ks, const int32_t* formats,
+                                  const int32_t* levels, const int32_t* bits, float* const* delta, float* const* theta,
+                                  float* const* v, const int64_t* sizes, int n_tensors, float beta0, int opt, double lr,
+                                  double beta2, double tau, void* stream);
+/* flc_fold_record_groups' contract over a mixed round (add_parameters' in-place accumulation per group,
+ * nodes.py:1116-1132; SCAFFOLD's two vectors, scaffold/_scaffold.py:160-169 over the messages of _scaffold.py:210-222,
+ * IFCA's clusters, ifca/_ifca.py:186-195 over the messages of _ifca.py:228-240): the records of a group, and the
+ * groups, may differ in codec.  Bit-identical to decoding every record and calling flc_weighted_sum(init_mode 2) per
+ * group and tensor.  Arguments, chaining and FLC_EINVAL cases as flc_fold_record_groups', the descriptor arrays in place
+ * of (k, levels). */
+int flc_fold_mixed_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
+                                 int n_records, int64_t n, const int32_t* kinds, const int64_t* ks,
+                                 const int32_t* formats, const int32_t* levels, const int32_t* bits,
+                                 float* const* dsts /* [n_groups][n_tensors] */, int n_groups, const int64_t* sizes,
+                                 int n_tensors, void* stream);
+/* flc_avg_and_gradient_records' contract over a mixed round of gradients (replaces fedprox/_fedprox.py:163-167 and
+ * 208-217, fedpd/_fedpd.py:197-202 and 252-275, proxskip/_proxskip.py:212-216 and 265-276, pfedmac/_pfedmac.py:158-162
+ * and 203-212, nodes.py:1134-1180, when the messages carry their gradients under different codecs):
+ *   params[t] = params[t] * inertia, then fmaf(w_params[m], param_srcs[m * n_tensors + t], .) for m in order
+ *               (param_srcs == NULL: params is neither read nor written — update_gradients alone);
+ *   grads[t]  = +0, then fmaf(w_grads[m], decode_m(grad_records[m])[e], .) for m in order;
+ * bit-identical to decoding every record and calling flc_avg_and_gradients.  Arguments and chaining as
+ * flc_avg_and_gradient_records', the descriptor arrays in place of (k, levels). */
+int flc_avg_and_gradient_mixed_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                       const void* const* grad_records, const float* w_params, const float* w_grads,
+                                       int n_src, int64_t n, const int32_t* kinds, const int64_t* ks,
+                                       const int32_t* formats, const int32_t* levels, const int32_t* bits,
+                                       const int64_t* sizes, int n_tensors, float inertia, void* stream);
+
 /* ------------------------------------------------------------------ multi-GPU exchange (RCCL over xGMI)
  * For callers outside torch; one process per GPU.  RCCL is the NCCL API on ROCm, looked
  * up on first use: $FLC_RCCL_LIB if set, else an RCCL already loaded in the process (inside a torch process, torch's
