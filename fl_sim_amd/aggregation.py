@@ -176,22 +176,36 @@ def _flat_views(like: Sequence[torch.Tensor], **kw):
     return flat, views
 
 
-def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs, wg: Sequence[float],
+def _round_of(messages: Sequence[Mapping], key: str = "delta_parameters", host: bool = False):
+    """What the record folds take of this key's round, asked once: ``(deltas, mixed)`` — the deltas of a uniform round
+    of records (compressed.record_round; ``mixed`` False), else of a round whose messages differ in codec
+    (compressed.mixed_round: only with compressed.MIXED_FOLD on, read at call time, and never for a ``host``-resident
+    server; ``mixed`` True), else ``(None, False)``.  The pair goes to one fold call: a uniform round whose fold
+    declines is not offered to the mixed fold."""
+    recs = compressed.record_round(messages, key)
+    if recs is not None or host:
+        return recs, False
+    recs = compressed.mixed_round(messages, key)
+    return recs, recs is not None
+
+
+def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], wg: Sequence[float],
                   wp: Optional[Sequence[float]] = None, inertia: float = 0.0) -> Optional[List[torch.Tensor]]:
-    """A round whose ``gradients`` are stacked records (``recs``: compressed.stacked_round(messages, "gradients")),
-    sparse records (compressed.sparse_round) or dense records (compressed.dense_record_round): every record decoded
-    and folded into one flat gradient buffer and, with ``wp``, the dense ``parameters`` folded into the model in the
-    same pass (flc_avg_and_gradient_records / flc_avg_and_gradient_sparse_records /
-    flc_avg_and_gradient_dense_records); the records are never decoded densely.  Sets
+    """A round whose ``gradients`` are records the folds take (_round_of(messages, "gradients")): every record
+    decoded and folded into one flat gradient buffer and, with ``wp``, the dense ``parameters`` folded into the model
+    in the same pass (flc_avg_and_gradient_records and its sparse, dense and mixed counterparts, by the round:
+    compressed.fold_gradient_records); the records are never decoded densely.  Sets
     ``.grad`` of every parameter and returns the gradients; None (nothing launched, nothing changed) when the model
     is not one the launch takes — the caller's dense path follows.  A host-resident model is staged: the records (and
     the messages' parameters) in, the parameters out, the gradients out in one copy."""
     n = len(messages)
+    on_host = hoststage.is_host(mps)
+    recs, mixed = _round_of(messages, "gradients", on_host)
+    if recs is None:
+        return None
     psrc = [m["parameters"] for m in messages] if wp is not None else None
-    # (a compressed.mixed_round: the messages differ in codec — flc_avg_and_gradient_mixed_records, device servers only)
-    mixed = compressed.MIXED_FOLD and any(d.codec_key != recs[0].codec_key for d in recs)
-    if hoststage.is_host(mps):
-        if mixed or not all(isinstance(p, torch.Tensor) and p.is_cpu and p.dtype is torch.float32 for p in mps):
+    if on_host:
+        if not all(isinstance(p, torch.Tensor) and p.is_cpu and p.dtype is torch.float32 for p in mps):
             return None
         rmsgs = [[d.record] for d in recs]
         host = None
@@ -217,14 +231,11 @@ def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs
             grads.append(host[off:off + p.numel()].view(p.shape))
             off += p.numel()
     else:
-        d0 = recs[0]
-        if d0.kind == "sparse":
-            fast, shape = codec._pygsrecs(), (d0.n, d0.k)
-        elif d0.kind in ("quant", "natural"):
-            fast, shape = codec._pygdrecs(), (d0.n, d0.format, d0.levels, d0.bits)
-        else:
-            fast, shape = codec._pygrecs(), (d0.n, d0.k, d0.levels)
-        if fast is not None and not mixed and mps and isinstance(mps[0], torch.Tensor) and mps[0].is_cuda:
+        fast = None
+        if not mixed:
+            shape, entries = compressed._record_entries(recs[0])
+            fast = entries.py_gradient()
+        if fast is not None and mps and isinstance(mps[0], torch.Tensor) and mps[0].is_cuda:
             # one C call: every tensor and record checked in place, the fold, the gradients' buffer and views, and every
             # parameter's `.grad`; a TypeError (a tensor the launch does not take, or messages elsewhere) leaves
             # everything untouched and the ctypes call below decides
@@ -238,8 +249,8 @@ def _record_round(mps: Sequence[torch.Tensor], messages: Sequence[Mapping], recs
             return None
         with torch.cuda.device(ps[0].device):
             _, grads = _flat_views(ps, device=ps[0].device)
-            fold = compressed.fold_mixed_gradient_records if mixed else compressed.fold_gradient_records
-            if not fold(recs, wg, grads, ps if wp is not None else None, psrc, wp, inertia):
+            if not compressed.fold_gradient_records(recs, wg, grads, ps if wp is not None else None, psrc, wp, inertia,
+                                                    mixed=mixed):
                 return None
     for mp, g in zip(mps, grads):
         if isinstance(mp, torch.Tensor):
@@ -256,12 +267,9 @@ def update_gradients(model_params: Sequence[torch.Tensor], messages: Sequence[Ma
         return None
     assert all(["gradients" in m for m in messages]), "some clients have not sent gradients yet"
     model_params = list(model_params)
-    recs = (compressed.record_round(messages, key="gradients")
-            or compressed.mixed_round(messages, key="gradients")
-            if isinstance(messages[0]["gradients"], compressed.CompressedDelta) else None)
-    if recs is not None:
+    if isinstance(messages[0]["gradients"], compressed.CompressedDelta):
         total_samples = sum([m["train_samples"] for m in messages])
-        r = _record_round(model_params, messages, recs, [m["train_samples"] / total_samples for m in messages])
+        r = _record_round(model_params, messages, [m["train_samples"] / total_samples for m in messages])
         if r is not None:
             return r
     if hoststage.is_host(model_params):
@@ -360,11 +368,10 @@ def avg_parameters_and_gradients(model_params: Sequence[torch.Tensor], messages:
     wg = [m["train_samples"] / total for m in messages]
     n = len(messages)
     if isinstance(messages[0]["gradients"], compressed.CompressedDelta):
-        recs = compressed.record_round(messages, key="gradients") or compressed.mixed_round(messages, key="gradients")
-        if recs is not None:  # compressed gradients: the records folded beside the dense parameters, in the same pass
-            r = _record_round(mps, messages, recs, wg, wp, inertia)
-            if r is not None:
-                return r
+        # compressed gradients: the records folded beside the dense parameters, in the same pass
+        r = _record_round(mps, messages, wg, wp, inertia)
+        if r is not None:
+            return r
     if hoststage.is_host(mps):
         with hoststage.staged([mps], [True], [True], [m["parameters"] for m in messages]
                               + [m["gradients"] for m in messages]) as ((dps,), dm):
@@ -415,8 +422,9 @@ def fedopt_update(model_params: Sequence[torch.Tensor], delta_parameters: Sequen
     alpha = (1 - betas[0]) / len(messages) if len(messages) else 0.0
     model_params, delta_parameters = list(model_params), list(delta_parameters)
     vps = None if (v_parameters is None or opt == "avg") else list(v_parameters)
-    recs = compressed.record_round(messages)  # a round of packed stacked or dense records (the codec's call site)
-    if hoststage.is_host(model_params):
+    host = hoststage.is_host(model_params)
+    recs, mixed = _round_of(messages, host=host)  # a round of packed records (the codec's call site)
+    if host:
         groups = [model_params, delta_parameters] + ([vps] if vps is not None else [])
         n = len(groups)
         msgs = [[d.record] for d in recs] if recs is not None else [m["delta_parameters"] for m in messages]
@@ -431,13 +439,9 @@ def fedopt_update(model_params: Sequence[torch.Tensor], delta_parameters: Sequen
         return
     # (the parameters as they are for the one-pass fold: its kernels write θ in place, outside autograd)
     if recs is not None and compressed.fold_records(recs, [alpha] * len(recs), delta_parameters, model_params, vps,
-                                                    betas[0], opt if vps is not None else "avg", lr, betas[1], tau):
-        return  # every record decoded, folded and the optimizer step applied in one pass
-    mixed = compressed.mixed_round(messages) if recs is None else None  # (FLC_MIXED_FOLD=1: the messages' codecs differ)
-    if mixed is not None and compressed.fold_mixed_records(mixed, [alpha] * len(mixed), delta_parameters, model_params,
-                                                           vps, betas[0], opt if vps is not None else "avg", lr,
-                                                           betas[1], tau):
-        return  # the same pass, every message read by its own codec
+                                                    betas[0], opt if vps is not None else "avg", lr, betas[1], tau,
+                                                    mixed=mixed):
+        return  # every record decoded (a mixed round's by its own codec), folded and the optimizer step applied: one pass
     ps = _params(model_params)
     if _fold(delta_parameters, messages, [alpha] * len(messages), 0, betas[0], key="delta_parameters",
              theta=ps, v=vps, opt=opt if vps is not None else "avg", lr=lr, beta2=betas[1], tau=tau):
@@ -473,12 +477,10 @@ def _fold_groups(groups, records=None) -> List[bool]:
     done = [False] * len(groups)
     if (compressed.MIXED_FOLD and records is None
             and len({d.codec_key for ds, _, _ in groups for d in ds}) > 1
-            and compressed.fold_mixed_record_groups(groups)):
+            and compressed.fold_record_groups(groups, mixed=True)):
         return [True] * len(groups)  # (groups of different codecs, or messages within one: one launch for them all)
-    shapes: dict = {}
+    shapes: dict = {}  # (a group whose own messages differ in codec is declined by the uniform fold: the dense path)
     for i, (ds, _, _) in enumerate(groups):
-        if compressed.MIXED_FOLD and (ds[0].kind == "dense" or any(d.codec_key != ds[0].codec_key for d in ds)):
-            continue  # (a compressed.mixed_round the mixed fold did not take: the dense path)
         shapes.setdefault(ds[0].codec_key, []).append(i)
     for ids in shapes.values():
         ok = compressed.fold_record_groups([groups[i] for i in ids],
@@ -503,9 +505,11 @@ def scaffold_update(model_params: Sequence[torch.Tensor], control_variates: Sequ
     ratio_c = 1 / num_clients
     model_params, control_variates = list(model_params), list(control_variates)
     keys = ("parameters_delta", "control_variates_delta")
-    recs = [compressed.record_round(messages, key) for key in keys]
+    host = hoststage.is_host(model_params)
+    # (with FLC_MIXED_FOLD on, a vector whose messages differ in codec joins a device server's grouped fold)
+    recs = [_round_of(messages, key, host)[0] for key in keys]
     n = len(messages)
-    if hoststage.is_host(model_params):
+    if host:
         msgs = [[[d.record] for d in r] if r is not None else [m[key] for m in messages] for key, r in zip(keys, recs)]
         with hoststage.staged([model_params, control_variates], [True, True], [True, True],
                               msgs[0] + msgs[1]) as ((dps, dcvs), dm):
@@ -523,8 +527,6 @@ def scaffold_update(model_params: Sequence[torch.Tensor], control_variates: Sequ
                 _add_round(dst, messages if recs[i] is not None else [{key: d} for d in staged[i]], key, ratio)
         return
     ps, cvs = _params(model_params), list(control_variates)
-    if compressed.MIXED_FOLD:  # (a vector whose messages differ in codec joins the grouped fold)
-        recs = [r if r is not None else compressed.mixed_round(messages, key) for r, key in zip(recs, keys)]
     if recs[0] is None and recs[1] is None:
         if not _fold(ps, messages, [ratio_p] * len(messages), 2, key="parameters_delta"):
             for j, sp in enumerate(ps):
@@ -561,8 +563,8 @@ def ifca_update(cluster_centers: Mapping[int, dict], messages: Sequence[Mapping]
     collected = set(i for v in cluster_centers.values() for i in v["client_ids"])
     for c, v in cluster_centers.items():
         v["client_ids"].extend(i for i in prev[c] if i not in collected)
-    if not ((compressed.record_round(messages) is not None and _ifca_records(cluster_centers, members, sizes))
-            or (compressed.mixed_round(messages) is not None and _ifca_mixed(cluster_centers, members, sizes))):
+    recs, mixed = _round_of(messages)  # (a host-resident centre declines a mixed round in _ifca_records)
+    if not (recs is not None and _ifca_records(cluster_centers, members, sizes, mixed)):
         for c, ms in members.items():
             center = list(cluster_centers[c]["center_model_params"])
             if hoststage.is_host(center):
@@ -576,14 +578,18 @@ def ifca_update(cluster_centers: Mapping[int, dict], messages: Sequence[Mapping]
         cluster_centers[m["cluster_id"]]["client_ids"].append(m["client_id"])
 
 
-def _ifca_records(cluster_centers: Mapping[int, dict], members: Mapping[int, list], sizes: Mapping[int, int]) -> bool:
-    """A round of stacked records: every cluster with messages folded in one grouped pass, each centre in place
-    (host-resident centres staged together: the records in, the centres out).  False: nothing launched."""
+def _ifca_records(cluster_centers: Mapping[int, dict], members: Mapping[int, list], sizes: Mapping[int, int],
+                  mixed: bool = False) -> bool:
+    """A round of records: every cluster with messages folded in one grouped pass, each centre in place
+    (host-resident centres staged together: the records in, the centres out).  ``mixed``: the messages differ in codec
+    (compressed.mixed_round: flc_fold_mixed_record_groups, device-resident centres only).  False: nothing launched."""
     cs = list(members)
     centers = [list(cluster_centers[c]["center_model_params"]) for c in cs]
     deltas = [[m["delta_parameters"] for m in members[c]] for c in cs]
     weights = [[1 / sizes[c]] * len(members[c]) for c in cs]
     host = [hoststage.is_host(center) for center in centers]
+    if any(host) and mixed:
+        return False
     if all(host):
         # every cluster's centre staged together, in the centres' own order (the mixin adopts them so); the idle
         # clusters' are neither copied in nor written back
@@ -602,19 +608,8 @@ def _ifca_records(cluster_centers: Mapping[int, dict], members: Mapping[int, lis
             return compressed.fold_record_groups(list(zip(deltas, weights, dsts)), staged)
     if any(host):
         return False
-    return compressed.fold_record_groups(list(zip(deltas, weights, [_params(center) for center in centers])))
-
-
-def _ifca_mixed(cluster_centers: Mapping[int, dict], members: Mapping[int, list], sizes: Mapping[int, int]) -> bool:
-    """A round whose messages differ in codec (compressed.mixed_round): every cluster with messages folded in one
-    grouped pass (flc_fold_mixed_record_groups), device-resident centres only.  False: nothing launched."""
-    cs = list(members)
-    centers = [list(cluster_centers[c]["center_model_params"]) for c in cs]
-    if any(hoststage.is_host(center) for center in centers):
-        return False
-    return compressed.fold_mixed_record_groups(
-        [([m["delta_parameters"] for m in members[c]], [1 / sizes[c]] * len(members[c]), _params(center))
-         for c, center in zip(cs, centers)])
+    return compressed.fold_record_groups(list(zip(deltas, weights, [_params(center) for center in centers])),
+                                         mixed=mixed)
 
 
 _PROX_KIND = {"l1": "l1", "l2": "l2", "l2squared": "l2squared", "no": "none", "empty": "none", "zero": "none",

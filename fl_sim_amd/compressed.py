@@ -52,6 +52,12 @@ What runs here instead:
   decoded vector among them included (:func:`mixed_round`), is folded in one pass with every record read by its own
   descriptor (``flc_fedopt_fold_mixed_records``, ``flc_fold_mixed_record_groups``,
   ``flc_avg_and_gradient_mixed_records``), on device-resident servers.
+  The folds are written once per server form — :func:`fold_records` (FedOpt), :func:`fold_gradient_records` (the
+  variance-reduced servers), :func:`fold_record_groups` (SCAFFOLD, IFCA) — and each serves every kind of round:
+  :func:`record_round` and its three parts are one classifier (one of these kinds, one ``codec_key``),
+  ``_record_entries`` is the one place that knows a uniform kind's shape arguments, C names and one-call ``_flcfold``
+  entries, ``_server_ok`` the one check of the server tensors, and ``mixed=True`` (the ``fold_mixed_*`` names) swaps
+  the kind's shape for the per-record descriptor columns of ``_mixed_tables``.
 
 The compressors' send statistics advance as ``compressVector`` advances them (``compressors.py:406-408``), per stage.
 
@@ -940,9 +946,12 @@ def _stacked(ls, gs, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compres
     return CompressedDelta(shapes, dev, n, record=rec, k=K, levels=s)
 
 
+_RECORD_KINDS = ("stacked", "quant", "natural", "sparse")
+
+
 def _round_deltas(messages: Sequence, key: str, kinds: Tuple[str, ...]) -> Optional[List[CompressedDelta]]:
-    """The messages' compressed deltas under ``key`` when there are messages and every one carries a
-    :class:`CompressedDelta` of one of ``kinds``, else None."""
+    """The messages' compressed deltas under ``key`` when there are messages, every one carries a
+    :class:`CompressedDelta` of one of ``kinds`` and all share one ``codec_key``, else None."""
     if not messages:
         return None
     ds = []
@@ -951,208 +960,69 @@ def _round_deltas(messages: Sequence, key: str, kinds: Tuple[str, ...]) -> Optio
         if not isinstance(d, CompressedDelta) or d.kind not in kinds:
             return None
         ds.append(d)
+    key0 = ds[0].codec_key
+    for d in ds:
+        if d.codec_key != key0:
+            return None
     return ds
 
 
 def stacked_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
     """The messages' compressed deltas when every one is a stacked record of one (n, k, levels), else None."""
-    ds = _round_deltas(messages, key, ("stacked",))
-    if ds is None:
-        return None
-    d0 = ds[0]
-    if any((d.n, d.k, d.levels) != (d0.n, d0.k, d0.levels) for d in ds):
-        return None
-    return ds
+    return _round_deltas(messages, key, ("stacked",))
 
 
 def dense_record_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
     """The messages' compressed deltas when every one is a dense record (``kind`` "quant" or "natural") of one
     (n, format, levels, bits), else None (a mixed round: each message then decodes itself)."""
-    ds = _round_deltas(messages, key, ("quant", "natural"))
-    if ds is None:
-        return None
-    key0 = ds[0].codec_key
-    if any(d.codec_key != key0 for d in ds):
-        return None
-    return ds
+    return _round_deltas(messages, key, ("quant", "natural"))
 
 
 def sparse_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
     """The messages' compressed deltas when every one is a sparse record (``kind`` "sparse") of one (n, k), else None
     (a mixed round: each message then decodes itself)."""
-    ds = _round_deltas(messages, key, ("sparse",))
-    if ds is None:
-        return None
-    d0 = ds[0]
-    if any((d.n, d.k) != (d0.n, d0.k) for d in ds):
-        return None
-    return ds
+    return _round_deltas(messages, key, ("sparse",))
 
 
 def record_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
     """:func:`stacked_round`, :func:`dense_record_round` or :func:`sparse_round`: a round the record folds take, else
     None."""
-    return stacked_round(messages, key) or dense_record_round(messages, key) or sparse_round(messages, key)
+    return _round_deltas(messages, key, _RECORD_KINDS)
 
 
-def fold_records(deltas: Sequence[CompressedDelta], weights: Sequence[float], delta_params: Sequence[torch.Tensor],
-                 theta: Optional[Sequence[torch.Tensor]], v: Optional[Sequence[torch.Tensor]], beta0: float,
-                 opt: str = "avg", lr: float = 1.0, beta2: float = 0.0, tau: float = 0.0) -> bool:
-    """``δ = β0·δ + Σ_c w_c·decode(record_c)`` in message order, then (``theta``) the server optimiser's step — one
-    ``flc_fedopt_fold_records`` pass (``flc_fedopt_fold_dense_records`` / ``flc_fedopt_fold_sparse_records`` by the
-    records' kind).  False (nothing launched) when the server tensors are not contiguous fp32 tensors
-    of one HIP device holding the records' element count (the caller then takes the dense path)."""
-    dps = list(delta_params)
-    d0 = deltas[0]
-    # (a dense_record_round: flc_fedopt_fold_dense_records; a sparse_round: flc_fedopt_fold_sparse_records — the same
-    # contract)
-    sparse, dense = d0.kind == "sparse", d0.kind in ("quant", "natural")
-    shape = (d0.n, d0.k) if sparse else (d0.n, d0.format, d0.levels, d0.bits) if dense else (d0.n, d0.k, d0.levels)
-    fast = codec._pysrecs() if sparse else codec._pydrecs() if dense else codec._pyrecs()
-    if fast is not None and dps:
-        try:  # one C call: every tensor checked in place; TypeError: nothing launched, the checks below decide
-            fast([d.record for d in deltas], [float(w) for w in weights], *shape, dps,
-                 None if theta is None else list(theta), None if v is None else list(v), float(beta0),
-                 _lib.FLC_OPT[opt], float(lr), float(beta2), float(tau))
-            return True
-        except TypeError:
-            pass
-    if not dps or not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()
-                          for t in dps):
-        return False
-    dev = dps[0].device
-    groups = [dps] + ([list(theta)] if theta is not None else []) + ([list(v)] if v is not None else [])
-    for g in groups:
-        if len(g) != len(dps) or any(not (t.is_cuda and t.device == dev and t.dtype is torch.float32
-                                          and t.is_contiguous() and t.numel() == d.numel()) for t, d in zip(g, dps)):
-            return False
-    d0 = deltas[0]
-    if sum(t.numel() for t in dps) != d0.n:
-        return False
-    recs = [d.record if d.record.device == dev else d.record.to(dev) for d in deltas]
-    m, T = len(recs), len(dps)
-    fn = ("flc_fedopt_fold_sparse_records" if sparse else
-          "flc_fedopt_fold_dense_records" if dense else "flc_fedopt_fold_records")
-    _lib.call(fn, _ptrs(recs),
-              (ctypes.c_float * m)(*[float(w) for w in weights]), m, *shape, _ptrs(dps),
-              _ptrs(groups[1]) if theta is not None else None,
-              _ptrs(groups[2]) if v is not None else None, (ctypes.c_int64 * T)(*[t.numel() for t in dps]), T,
-              float(beta0), _lib.FLC_OPT[opt], float(lr), float(beta2), float(tau), codec._stream(dev))
-    return True
+class _Entries(NamedTuple):
+    """One uniform record kind's entry points, by server form (the FedOpt fold, the variance-reduced servers'
+    gradient fold, the grouped fold): the C names, and the ``codec._py*`` accessor of the form's one-call ``_flcfold``
+    entry (None: the form has none for this kind)."""
+
+    fedopt: str
+    gradient: str
+    groups: str
+    py_fedopt: object
+    py_gradient: object
+    py_groups: object
 
 
-def fold_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequence[float], grads: Sequence[torch.Tensor],
-                          params: Optional[Sequence[torch.Tensor]] = None,
-                          param_srcs: Optional[Sequence[Sequence[torch.Tensor]]] = None,
-                          w_params: Optional[Sequence[float]] = None, inertia: float = 0.0,
-                          records: Optional[Sequence[torch.Tensor]] = None) -> bool:
-    """``grads = Σ_m w_grads[m]·decode(record_m)`` from +0 in message order and, with ``params``,
-    ``θ = θ·inertia + Σ_m w_params[m]·param_srcs[m]`` — one ``flc_avg_and_gradient_records`` pass (``params`` None:
-    ``update_gradients`` alone; ``flc_avg_and_gradient_sparse_records`` / ``flc_avg_and_gradient_dense_records`` by
-    the records' kind).  ``records``: the messages' records where they were staged (default: the deltas' own).
-    False (nothing launched) when a tensor is not a contiguous fp32 tensor of the gradients' HIP device holding the
-    records' element count (the caller then takes the dense path); records and parameter sources elsewhere are moved."""
-    gs = list(grads)
-    ok = lambda t, dev: (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev  # noqa: E731
-                         and t.dtype is torch.float32 and t.is_contiguous())
-    if not gs or not isinstance(gs[0], torch.Tensor) or not gs[0].is_cuda:
-        return False
-    dev = gs[0].device
-    d0 = deltas[0]
-    if not all(ok(g, dev) for g in gs) or sum(g.numel() for g in gs) != d0.n:
-        return False
-    T, m = len(gs), len(deltas)
-    ps = srcs = None
-    if params is not None:
-        ps = [p.data if isinstance(p, torch.nn.Parameter) else p for p in params]
-        if len(ps) != T or not all(ok(p, dev) and p.numel() == g.numel() for p, g in zip(ps, gs)):
-            return False
-        srcs = [[t.detach() if t.device == dev else t.detach().to(dev) for t in r] for r in param_srcs]
-        if len(srcs) != m or any(len(r) != T or not all(ok(t, dev) and t.numel() == g.numel() for t, g in zip(r, gs))
-                                 for r in srcs):
-            return False
-    recs = [d.record for d in deltas] if records is None else list(records)
-    recs = [r if r.device == dev else r.to(dev) for r in recs]
-    fl = lambda ws: (ctypes.c_float * m)(*[float(w) for w in ws])  # noqa: E731
-    # (a sparse_round: flc_avg_and_gradient_sparse_records; a dense_record_round: flc_avg_and_gradient_dense_records —
-    # the same contract)
-    sparse, dense = d0.kind == "sparse", d0.kind in ("quant", "natural")
-    shape = (d0.n, d0.k) if sparse else (d0.n, d0.format, d0.levels, d0.bits) if dense else (d0.n, d0.k, d0.levels)
-    fn = ("flc_avg_and_gradient_sparse_records" if sparse else
-          "flc_avg_and_gradient_dense_records" if dense else "flc_avg_and_gradient_records")
-    with torch.cuda.device(dev):
-        _lib.call(fn, _ptrs(ps) if ps is not None else None, _ptrs(gs),
-                  _ptrs([t for r in srcs for t in r]) if srcs is not None else None, _ptrs(recs),
-                  fl(w_params) if ps is not None else None, fl(w_grads), m, *shape,
-                  (ctypes.c_int64 * T)(*[g.numel() for g in gs]), T, float(inertia), codec._stream(dev))
-    return True
+def _entries(infix: str, *accessors) -> _Entries:
+    return _Entries(f"flc_fedopt_fold_{infix}records", f"flc_avg_and_gradient_{infix}records",
+                    f"flc_fold_{infix}record_groups", *accessors)
 
 
-def fold_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequence[float], Sequence[torch.Tensor]]],
-                       records: Optional[Sequence[Optional[Sequence[torch.Tensor]]]] = None) -> bool:
-    """For every ``(deltas, weights, dst_tensors)`` of ``groups``: ``dst += Σ_c w_c·decode(record_c)`` in place, in
-    the group's message order (``add_parameters``' accumulation) — all groups in one ``flc_fold_record_groups`` pass.
-    A group without deltas is left alone.  ``records[g]``: group ``g``'s records where they were staged (default: the
-    deltas' own).  False (nothing launched) when the records are not of one (n, k, levels), or a destination tensor
-    is not a contiguous fp32 tensor of one HIP device, or the groups' tensors do not all hold the records' element
-    counts tensor by tensor, or two groups share a destination (the caller then takes the dense path); records on
-    another device are moved."""
-    recs_of = list(records) if records is not None else [None] * len(groups)
-    live = [(list(ds), list(ws), [p.data if isinstance(p, torch.nn.Parameter) else p for p in dst], rs)
-            for (ds, ws, dst), rs in zip(groups, recs_of) if len(ds)]
-    if not live:
-        return True
-    d0 = live[0][0][0]
-    if d0.kind == "dense" or any(d.codec_key != d0.codec_key for ds, _, _, _ in live for d in ds):
-        return False
-    if any(len(ws) != len(ds) or (rs is not None and len(rs) != len(ds)) for ds, ws, _, rs in live):
-        return False
-    # (dense and sparse records: flc_fold_dense_record_groups / flc_fold_sparse_record_groups through ctypes, the same
-    # contract)
-    sparse, dense = d0.kind == "sparse", d0.kind in ("quant", "natural")
-    shape = (d0.n, d0.k) if sparse else (d0.n, d0.format, d0.levels, d0.bits) if dense else (d0.n, d0.k, d0.levels)
-    fast = None if (dense or sparse) else codec._pygroups()
-    if fast is not None:
-        try:  # one C call: every tensor checked in place; TypeError: nothing launched, the checks below decide
-            fast([[d.record for d in ds] if rs is None else rs for ds, _, _, rs in live],
-                 [ws for _, ws, _, _ in live], [dst for _, _, dst, _ in live], d0.n, d0.k, d0.levels)
-            return True
-        except TypeError:
-            pass
-    first = live[0][2]
-    if not first or not isinstance(first[0], torch.Tensor) or not first[0].is_cuda:
-        return False
-    dev = first[0].device
-    sizes = [t.numel() for t in first]
-    if sum(sizes) != d0.n:
-        return False
-    seen = set()
-    for ds, ws, dst, rs in live:
-        if len(dst) != len(sizes):
-            return False
-        for t, m in zip(dst, sizes):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype is torch.float32
-                    and t.is_contiguous() and t.numel() == m):
-                return False
-            if m and t.data_ptr() in seen:
-                return False
-            if m:
-                seen.add(t.data_ptr())
-    recs, ws, gof, dsts = [], [], [], []
-    for g, (ds, w, dst, rs) in enumerate(live):
-        rl = [d.record for d in ds] if rs is None else list(rs)
-        recs += [r if r.device == dev else r.to(dev) for r in rl]
-        ws += [float(x) for x in w]
-        gof += [g] * len(ds)
-        dsts += dst
-    m, T = len(recs), len(sizes)
-    with torch.cuda.device(dev):
-        fn = ("flc_fold_sparse_record_groups" if sparse else
-              "flc_fold_dense_record_groups" if dense else "flc_fold_record_groups")
-        _lib.call(fn, _ptrs(recs),
-                  (ctypes.c_float * m)(*ws), (ctypes.c_int32 * m)(*gof), m, *shape, _ptrs(dsts), len(live),
-                  (ctypes.c_int64 * T)(*sizes), T, codec._stream(dev))
-    return True
+_STACKED = _entries("", codec._pyrecs, codec._pygrecs, codec._pygroups)
+_SPARSE = _entries("sparse_", codec._pysrecs, codec._pygsrecs, None)
+_DENSE = _entries("dense_", codec._pydrecs, codec._pygdrecs, None)
+_MIXED = _entries("mixed_", codec._pymrecs, None, None)  # (a mixed_round: every record by its own descriptor)
+
+
+def _record_entries(d0: CompressedDelta) -> Tuple[tuple, _Entries]:
+    """(shape, entries) of a uniform round of ``d0``'s records — the one place that knows a kind's entry points.
+    ``shape`` is what every entry of the kind takes after the record count: (n, k, levels) of stacked records, (n, k)
+    of sparse ones, (n, format, levels, bits) of dense ones."""
+    if d0.kind == "sparse":
+        return (d0.n, d0.k), _SPARSE
+    if d0.kind in ("quant", "natural"):
+        return (d0.n, d0.format, d0.levels, d0.bits), _DENSE
+    return (d0.n, d0.k, d0.levels), _STACKED
 
 
 # Mixed rounds.  A round whose messages do not share one codec_key — another K, another bit width, another record
@@ -1177,9 +1047,11 @@ def mixed_fold_stats(reset: bool = False) -> dict:
     return out
 
 
-def _mixed_done(messages: int) -> bool:
-    _MIXED_STATS["folds"] += 1
-    _MIXED_STATS["messages"] += messages
+def _folded(messages: int, mixed: bool) -> bool:
+    """A fold has run (True); a mixed one is counted."""
+    if mixed:
+        _MIXED_STATS["folds"] += 1
+        _MIXED_STATS["messages"] += messages
     return True
 
 
@@ -1239,106 +1111,95 @@ def _mixed_ctypes(kinds, ks, fmts, lvs, bits):
     return i32(kinds), (ctypes.c_int64 * m)(*ks), i32(fmts), i32(lvs), i32(bits)
 
 
-def _server_ok(groups: Sequence[Sequence[torch.Tensor]], n: int) -> Optional[torch.device]:
+def _round_records(deltas: Sequence[CompressedDelta], dev: torch.device, mixed: bool, records=None):
+    """(the round's records on ``dev``, what the C entries take after the record count, the entries) — a uniform
+    round's shape, or a mixed round's ``n`` and descriptor columns.  ``records``: the records where they were staged
+    (None, or None entries: the deltas' own); records elsewhere are moved."""
+    if mixed:
+        recs, *cols = _mixed_tables(deltas, dev, records)
+        return recs, (deltas[0].n, *_mixed_ctypes(*cols)), _MIXED
+    recs = [d.record if records is None or records[i] is None else records[i] for i, d in enumerate(deltas)]
+    return ([r if r.device == dev else r.to(dev) for r in recs], *_record_entries(deltas[0]))
+
+
+def _server_ok(groups: Sequence[Sequence[torch.Tensor]], n: int, distinct: bool = False) -> Optional[torch.device]:
     """The HIP device of server tensor lists that are, list by list, contiguous fp32 tensors of one device holding the
-    first list's element counts, ``n`` in all; else None."""
+    first list's element counts, ``n`` in all — with ``distinct``, no non-empty tensor in two places; else None."""
     first = list(groups[0]) if groups else []
     if not first or not isinstance(first[0], torch.Tensor) or not first[0].is_cuda:
         return None
     dev = first[0].device
+    seen = set()
     for g in groups:
         if len(g) != len(first) or any(not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev
                                             and t.dtype is torch.float32 and t.is_contiguous()
                                             and t.numel() == f.numel()) for t, f in zip(g, first)):
             return None
+        if distinct:
+            ptrs = [t.data_ptr() for t in g if t.numel()]
+            if len(seen.intersection(ptrs)) or len(set(ptrs)) != len(ptrs):
+                return None
+            seen.update(ptrs)
     return dev if sum(t.numel() for t in first) == n else None
 
 
-def fold_mixed_records(deltas: Sequence[CompressedDelta], weights: Sequence[float],
-                       delta_params: Sequence[torch.Tensor], theta: Optional[Sequence[torch.Tensor]],
-                       v: Optional[Sequence[torch.Tensor]], beta0: float, opt: str = "avg", lr: float = 1.0,
-                       beta2: float = 0.0, tau: float = 0.0) -> bool:
-    """:func:`fold_records` for a :func:`mixed_round`: ``δ = β0·δ + Σ_c w_c·decode_c(message_c)`` in message order,
-    every message by its own codec, then (``theta``) the server optimiser's step — one
-    ``flc_fedopt_fold_mixed_records`` pass.  False (nothing launched) when the server tensors are not contiguous fp32
-    tensors of one HIP device holding the messages' element count."""
+def fold_records(deltas: Sequence[CompressedDelta], weights: Sequence[float], delta_params: Sequence[torch.Tensor],
+                 theta: Optional[Sequence[torch.Tensor]], v: Optional[Sequence[torch.Tensor]], beta0: float,
+                 opt: str = "avg", lr: float = 1.0, beta2: float = 0.0, tau: float = 0.0, mixed: bool = False) -> bool:
+    """``δ = β0·δ + Σ_c w_c·decode(record_c)`` in message order, then (``theta``) the server optimiser's step — one
+    ``flc_fedopt_fold_records`` pass (``flc_fedopt_fold_dense_records`` / ``flc_fedopt_fold_sparse_records`` by the
+    records' kind; ``mixed``, a :func:`mixed_round`: ``flc_fedopt_fold_mixed_records``, every message by its own
+    codec).  False (nothing launched) when the server tensors are not contiguous fp32 tensors of one HIP device
+    holding the records' element count (the caller then takes the dense path)."""
     dps = list(delta_params)
     groups = [dps] + ([list(theta)] if theta is not None else []) + ([list(v)] if v is not None else [])
+    th, vv = groups[1] if theta is not None else None, groups[-1] if v is not None else None
     n = deltas[0].n
-    dev = _server_ok([[p.data if isinstance(p, torch.nn.Parameter) else p for p in g] for g in groups], n)
-    if dev is None:
-        return False
-    ts, kinds, ks, fmts, lvs, bits = _mixed_tables(deltas, dev)
     ws = [float(w) for w in weights]
-    fast = codec._pymrecs()
-    if fast is not None:
-        try:  # one C call: every tensor checked in place; TypeError: nothing launched, the ctypes call below decides
-            fast(ts, ws, n, kinds, ks, fmts, lvs, bits, dps, None if theta is None else groups[1],
-                 None if v is None else groups[-1], float(beta0), _lib.FLC_OPT[opt], float(lr), float(beta2),
-                 float(tau))
-            return _mixed_done(len(ts))
+    step = (float(beta0), _lib.FLC_OPT[opt], float(lr), float(beta2), float(tau))
+    if mixed:  # (the descriptor tables are built on the server's device: its check comes first)
+        dev = _server_ok(groups, n)
+        if dev is None:
+            return False
+        recs, *cols = _mixed_tables(deltas, dev)
+        shape, entries = (n, *cols), _MIXED
+    else:
+        shape, entries = _record_entries(deltas[0])
+        recs = [d.record for d in deltas]
+    fast = entries.py_fedopt()
+    if fast is not None and dps:
+        try:  # one C call: every tensor checked in place; TypeError: nothing launched, the checks below decide
+            fast(recs, ws, *shape, dps, th, vv, *step)
+            return _folded(len(recs), mixed)
         except TypeError:
             pass
-    m, T = len(ts), len(dps)
+    if mixed:
+        shape = (n, *_mixed_ctypes(*cols))
+    else:
+        dev = _server_ok(groups, n)
+        if dev is None:
+            return False
+        recs = [r if r.device == dev else r.to(dev) for r in recs]
+    m, T = len(recs), len(dps)
     with torch.cuda.device(dev):
-        _lib.call("flc_fedopt_fold_mixed_records", _ptrs(ts), (ctypes.c_float * m)(*ws), m, n,
-                  *_mixed_ctypes(kinds, ks, fmts, lvs, bits), _ptrs(dps),
-                  _ptrs(groups[1]) if theta is not None else None, _ptrs(groups[-1]) if v is not None else None,
-                  (ctypes.c_int64 * T)(*[t.numel() for t in dps]), T, float(beta0), _lib.FLC_OPT[opt], float(lr),
-                  float(beta2), float(tau), codec._stream(dev))
-    return _mixed_done(m)
+        _lib.call(entries.fedopt, _ptrs(recs), (ctypes.c_float * m)(*ws), m, *shape, _ptrs(dps),
+                  _ptrs(th) if th is not None else None, _ptrs(vv) if vv is not None else None,
+                  (ctypes.c_int64 * T)(*[t.numel() for t in dps]), T, *step, codec._stream(dev))
+    return _folded(m, mixed)
 
 
-def fold_mixed_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequence[float],
-                                                    Sequence[torch.Tensor]]]) -> bool:
-    """:func:`fold_record_groups` for groups whose messages differ in codec, within a group or between groups: for
-    every ``(deltas, weights, dst_tensors)``, ``dst += Σ_c w_c·decode_c(message_c)`` in place in the group's message
-    order — all groups in one ``flc_fold_mixed_record_groups`` pass.  False (nothing launched) when a destination is
-    not a contiguous fp32 tensor of one HIP device, the groups' tensors do not all hold the messages' element counts
-    tensor by tensor, or two groups share a destination."""
-    live = [(list(ds), [float(w) for w in ws], [p.data if isinstance(p, torch.nn.Parameter) else p for p in dst])
-            for ds, ws, dst in groups if len(ds)]
-    if not live:
-        return True
-    n = live[0][0][0].n
-    if any(d.n != n for ds, _, _ in live for d in ds) or any(len(ws) != len(ds) for ds, ws, _ in live):
-        return False
-    dev = _server_ok([dst for _, _, dst in live], n)
-    if dev is None:
-        return False
-    seen = set()
-    for _, _, dst in live:
-        for t in dst:
-            if t.numel() and t.data_ptr() in seen:
-                return False
-            seen.add(t.data_ptr())
-    ts, ws, gof, dsts = [], [], [], []
-    cols = ([], [], [], [], [])
-    for g, (ds, w, dst) in enumerate(live):
-        t, *desc = _mixed_tables(ds, dev)
-        ts += t
-        for col, x in zip(cols, desc):
-            col += x
-        ws += w
-        gof += [g] * len(ds)
-        dsts += dst
-    m, T = len(ts), len(live[0][2])
-    with torch.cuda.device(dev):
-        _lib.call("flc_fold_mixed_record_groups", _ptrs(ts), (ctypes.c_float * m)(*ws), (ctypes.c_int32 * m)(*gof), m,
-                  n, *_mixed_ctypes(*cols), _ptrs(dsts), len(live),
-                  (ctypes.c_int64 * T)(*[t.numel() for t in live[0][2]]), T, codec._stream(dev))
-    return _mixed_done(m)
-
-
-def fold_mixed_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequence[float],
-                                grads: Sequence[torch.Tensor], params: Optional[Sequence[torch.Tensor]] = None,
-                                param_srcs: Optional[Sequence[Sequence[torch.Tensor]]] = None,
-                                w_params: Optional[Sequence[float]] = None, inertia: float = 0.0) -> bool:
-    """:func:`fold_gradient_records` for a :func:`mixed_round` of gradients: ``grads = Σ_m w_grads[m]·decode_m(message_m)``
-    from +0 in message order and, with ``params``, ``θ = θ·inertia + Σ_m w_params[m]·param_srcs[m]`` — one
-    ``flc_avg_and_gradient_mixed_records`` pass.  False (nothing launched) when a tensor is not a contiguous fp32 tensor
-    of the gradients' HIP device holding the messages' element count; records and parameter sources elsewhere are
-    moved."""
+def fold_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequence[float], grads: Sequence[torch.Tensor],
+                          params: Optional[Sequence[torch.Tensor]] = None,
+                          param_srcs: Optional[Sequence[Sequence[torch.Tensor]]] = None,
+                          w_params: Optional[Sequence[float]] = None, inertia: float = 0.0,
+                          records: Optional[Sequence[torch.Tensor]] = None, mixed: bool = False) -> bool:
+    """``grads = Σ_m w_grads[m]·decode(record_m)`` from +0 in message order and, with ``params``,
+    ``θ = θ·inertia + Σ_m w_params[m]·param_srcs[m]`` — one ``flc_avg_and_gradient_records`` pass (``params`` None:
+    ``update_gradients`` alone; ``flc_avg_and_gradient_sparse_records`` / ``flc_avg_and_gradient_dense_records`` by
+    the records' kind; ``mixed``, a :func:`mixed_round`: ``flc_avg_and_gradient_mixed_records``).  ``records``: the
+    messages' records where they were staged (default: the deltas' own).  False (nothing launched) when a tensor is
+    not a contiguous fp32 tensor of the gradients' HIP device holding the records' element count (the caller then
+    takes the dense path); records and parameter sources elsewhere are moved."""
     gs = list(grads)
     n, m = deltas[0].n, len(deltas)
     ps = srcs = None
@@ -1351,15 +1212,90 @@ def fold_mixed_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequ
         srcs = [[t.detach() if t.device == dev else t.detach().to(dev) for t in r] for r in param_srcs]
         if len(srcs) != m or _server_ok([gs] + srcs, n) is None:
             return False
-    ts, *desc = _mixed_tables(deltas, dev)
+    recs, shape, entries = _round_records(deltas, dev, mixed, records)
     T = len(gs)
     fl = lambda ws: (ctypes.c_float * m)(*[float(w) for w in ws])  # noqa: E731
     with torch.cuda.device(dev):
-        _lib.call("flc_avg_and_gradient_mixed_records", _ptrs(ps) if ps is not None else None, _ptrs(gs),
-                  _ptrs([t for r in srcs for t in r]) if srcs is not None else None, _ptrs(ts),
-                  fl(w_params) if ps is not None else None, fl(w_grads), m, n, *_mixed_ctypes(*desc),
+        _lib.call(entries.gradient, _ptrs(ps) if ps is not None else None, _ptrs(gs),
+                  _ptrs([t for r in srcs for t in r]) if srcs is not None else None, _ptrs(recs),
+                  fl(w_params) if ps is not None else None, fl(w_grads), m, *shape,
                   (ctypes.c_int64 * T)(*[g.numel() for g in gs]), T, float(inertia), codec._stream(dev))
-    return _mixed_done(m)
+    return _folded(m, mixed)
+
+
+def fold_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequence[float], Sequence[torch.Tensor]]],
+                       records: Optional[Sequence[Optional[Sequence[torch.Tensor]]]] = None,
+                       mixed: bool = False) -> bool:
+    """For every ``(deltas, weights, dst_tensors)`` of ``groups``: ``dst += Σ_c w_c·decode(record_c)`` in place, in
+    the group's message order (``add_parameters``' accumulation) — all groups in one ``flc_fold_record_groups`` pass
+    (``flc_fold_sparse_record_groups`` / ``flc_fold_dense_record_groups`` by the records' kind; ``mixed``:
+    ``flc_fold_mixed_record_groups``, the messages differing in codec within a group or between groups).
+    A group without deltas is left alone.  ``records[g]``: group ``g``'s records where they were staged (default: the
+    deltas' own).  False (nothing launched) when the records are not of one codec and shape (``mixed``: of one n), or
+    a destination tensor is not a contiguous fp32 tensor of one HIP device, or the groups' tensors do not all hold the
+    records' element counts tensor by tensor, or two groups share a destination (the caller then takes the dense
+    path); records on another device are moved."""
+    recs_of = list(records) if records is not None else [None] * len(groups)
+    live = [(list(ds), [float(w) for w in ws], [p.data if isinstance(p, torch.nn.Parameter) else p for p in dst], rs)
+            for (ds, ws, dst), rs in zip(groups, recs_of) if len(ds)]
+    if not live:
+        return True
+    d0 = live[0][0][0]
+    if mixed:
+        if any(d.n != d0.n for ds, _, _, _ in live for d in ds):
+            return False
+    elif d0.kind == "dense" or any(d.codec_key != d0.codec_key for ds, _, _, _ in live for d in ds):
+        return False
+    if any(len(ws) != len(ds) or (rs is not None and len(rs) != len(ds)) for ds, ws, _, rs in live):
+        return False
+    shape, entries = ((), _MIXED) if mixed else _record_entries(d0)
+    fast = entries.py_groups() if entries.py_groups is not None else None  # (stacked records only)
+    if fast is not None:
+        try:  # one C call: every tensor checked in place; TypeError: nothing launched, the checks below decide
+            fast([[d.record for d in ds] if rs is None else rs for ds, _, _, rs in live],
+                 [ws for _, ws, _, _ in live], [dst for _, _, dst, _ in live], *shape)
+            return True
+        except TypeError:
+            pass
+    dev = _server_ok([dst for _, _, dst, _ in live], d0.n, distinct=True)
+    if dev is None:
+        return False
+    ds = [d for g, _, _, _ in live for d in g]
+    staged = [r for g, _, _, rs in live for r in (rs if rs is not None else [None] * len(g))]
+    recs, shape, _ = _round_records(ds, dev, mixed, staged)
+    ws = [w for _, g, _, _ in live for w in g]
+    gof = [i for i, (g, _, _, _) in enumerate(live) for _ in g]
+    m, T = len(recs), len(live[0][2])
+    with torch.cuda.device(dev):
+        _lib.call(entries.groups, _ptrs(recs), (ctypes.c_float * m)(*ws), (ctypes.c_int32 * m)(*gof), m, *shape,
+                  _ptrs([t for _, _, dst, _ in live for t in dst]), len(live),
+                  (ctypes.c_int64 * T)(*[t.numel() for t in live[0][2]]), T, codec._stream(dev))
+    return _folded(m, mixed)
+
+
+def fold_mixed_records(deltas: Sequence[CompressedDelta], weights: Sequence[float],
+                       delta_params: Sequence[torch.Tensor], theta: Optional[Sequence[torch.Tensor]],
+                       v: Optional[Sequence[torch.Tensor]], beta0: float, opt: str = "avg", lr: float = 1.0,
+                       beta2: float = 0.0, tau: float = 0.0) -> bool:
+    """:func:`fold_records` for a :func:`mixed_round`: every message by its own codec, one
+    ``flc_fedopt_fold_mixed_records`` pass."""
+    return fold_records(deltas, weights, delta_params, theta, v, beta0, opt, lr, beta2, tau, mixed=True)
+
+
+def fold_mixed_record_groups(groups: Sequence[Tuple[Sequence[CompressedDelta], Sequence[float],
+                                                    Sequence[torch.Tensor]]]) -> bool:
+    """:func:`fold_record_groups` for groups whose messages differ in codec, within a group or between groups: one
+    ``flc_fold_mixed_record_groups`` pass."""
+    return fold_record_groups(groups, mixed=True)
+
+
+def fold_mixed_gradient_records(deltas: Sequence[CompressedDelta], w_grads: Sequence[float],
+                                grads: Sequence[torch.Tensor], params: Optional[Sequence[torch.Tensor]] = None,
+                                param_srcs: Optional[Sequence[Sequence[torch.Tensor]]] = None,
+                                w_params: Optional[Sequence[float]] = None, inertia: float = 0.0) -> bool:
+    """:func:`fold_gradient_records` for a :func:`mixed_round` of gradients: one
+    ``flc_avg_and_gradient_mixed_records`` pass."""
+    return fold_gradient_records(deltas, w_grads, grads, params, param_srcs, w_params, inertia, mixed=True)
 
 
 def _compressors_of(node, name: str = "compressors") -> List[Compressor]:

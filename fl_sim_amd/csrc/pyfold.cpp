@@ -637,60 +637,122 @@ PyObject* stacked_records_round(PyObject*, PyObject* args) {
   Py_RETURN_NONE;
 }
 
+// What a uniform round's records are — flc_record_kind with (k, levels), (k) or (format, levels, bits) — and what the
+// record entries need of it: the layout's size, the C entry of each server form and that entry's name.
+enum ServerForm { kFedOptForm = 0, kGradientForm = 1, kGroupForm = 2 };
+struct RecordShape {
+  int kind;  // FLC_REC_STACKED, FLC_REC_SPARSE or FLC_REC_DENSE
+  long long k;
+  int format, levels, bits;
+
+  // bytes of one record of n elements; 0 for a shape no layout takes (an unknown kind included)
+  size_t stride(long long n) const {
+    int64_t off[4];
+    switch (kind) {
+      case FLC_REC_STACKED: return flc_stacked_wire_layout(n, k, off);
+      case FLC_REC_SPARSE: return flc_sparse_wire_layout(n, k, off);
+      case FLC_REC_DENSE: return flc_dense_wire_layout(n, format, bits, off);
+      default: return 0;
+    }
+  }
+  const char* name(ServerForm form) const {
+    static const char* const kNames[3][3] = {
+        {"flc_fedopt_fold_records", "flc_avg_and_gradient_records", "flc_fold_record_groups"},
+        {"flc_fedopt_fold_sparse_records", "flc_avg_and_gradient_sparse_records", "flc_fold_sparse_record_groups"},
+        {"flc_fedopt_fold_dense_records", "flc_avg_and_gradient_dense_records", "flc_fold_dense_record_groups"}};
+    return kNames[kind][form];
+  }
+  int fedopt(const void* const* recs, const float* w, int nr, long long n, float* const* delta, float* const* theta,
+             float* const* v, const int64_t* sz, int nt, float beta0, int opt, double lr, double beta2, double tau,
+             void* st) const {
+    if (kind == FLC_REC_SPARSE)
+      return flc_fedopt_fold_sparse_records(recs, w, nr, n, k, delta, theta, v, sz, nt, beta0, opt, lr, beta2, tau, st);
+    if (kind == FLC_REC_DENSE)
+      return flc_fedopt_fold_dense_records(recs, w, nr, n, format, levels, bits, delta, theta, v, sz, nt, beta0, opt,
+                                           lr, beta2, tau, st);
+    return flc_fedopt_fold_records(recs, w, nr, n, k, levels, delta, theta, v, sz, nt, beta0, opt, lr, beta2, tau, st);
+  }
+  int gradient(float* const* params, float* const* grads, const float* const* srcs, const void* const* recs,
+               const float* wp, const float* wg, int ns, long long n, const int64_t* sz, int nt, float inertia,
+               void* st) const {
+    if (kind == FLC_REC_SPARSE)
+      return flc_avg_and_gradient_sparse_records(params, grads, srcs, recs, wp, wg, ns, n, k, sz, nt, inertia, st);
+    if (kind == FLC_REC_DENSE)
+      return flc_avg_and_gradient_dense_records(params, grads, srcs, recs, wp, wg, ns, n, format, levels, bits, sz, nt,
+                                                inertia, st);
+    return flc_avg_and_gradient_records(params, grads, srcs, recs, wp, wg, ns, n, k, levels, sz, nt, inertia, st);
+  }
+  int groups(const void* const* recs, const float* w, const int32_t* group_of, int nr, long long n, float* const* dsts,
+             int ng, const int64_t* sz, int nt, void* st) const {
+    if (kind == FLC_REC_SPARSE) return flc_fold_sparse_record_groups(recs, w, group_of, nr, n, k, dsts, ng, sz, nt, st);
+    if (kind == FLC_REC_DENSE)
+      return flc_fold_dense_record_groups(recs, w, group_of, nr, n, format, levels, bits, dsts, ng, sz, nt, st);
+    return flc_fold_record_groups(recs, w, group_of, nr, n, k, levels, dsts, ng, sz, nt, st);
+  }
+};
+inline RecordShape stacked_shape(long long k, int levels) { return {FLC_REC_STACKED, k, 0, levels, 0}; }
+inline RecordShape sparse_shape(long long k) { return {FLC_REC_SPARSE, k, 0, 0, 0}; }
+inline RecordShape dense_shape(int format, int levels, int bits) { return {FLC_REC_DENSE, 0, format, levels, bits}; }
+
+// The FedOpt record entries' front half: the record, weight and server-tensor sequences, one weight per record, the
+// server tensors (δ, then θ / v) of one device holding n elements.  `rows()` — the entry's own per-record tables —
+// runs after the counts and before any tensor is looked at; false from it, or from here, with the error set.
+struct ServerTables {
+  PyObject *recs = nullptr, *weights = nullptr;  // fast sequences of nr items
+  Py_ssize_t nr = 0, nt = 0;
+  int dev = -1;
+  std::vector<float*> dp, tp, vp;
+  std::vector<int64_t> sz;
+  float* const* theta() const { return tp.empty() ? nullptr : tp.data(); }
+  float* const* v() const { return vp.empty() ? nullptr : vp.data(); }
+};
+template <class F>
+bool server_tables(Refs& refs, const char* not_sequences, const char* nothing_to_fold, PyObject* recs,
+                   PyObject* weights, PyObject* delta, PyObject* theta, PyObject* v, long long n, F&& rows,
+                   ServerTables* s) {
+  PyObject* fd = nullptr;
+  if (!(s->recs = refs.fast(recs, not_sequences)) || !(s->weights = refs.fast(weights, not_sequences)) ||
+      !(fd = refs.fast(delta, not_sequences)))
+    return false;
+  s->nr = len(s->recs), s->nt = len(fd);
+  if (len(s->weights) != s->nr) return value_error("one weight per record"), false;
+  if (s->nr < 1 || s->nt < 1) return type_error(nothing_to_fold), false;
+  if (!rows()) return false;
+  s->dp.resize(s->nt);
+  s->sz.resize(s->nt);
+  if (tensor_row(items(fd), s->nt, &s->dev, s->sz.data(), true, s->dp.data()))
+    return type_error("server tensors must be contiguous fp32 HIP tensors on one device"), false;
+  int64_t total = 0;
+  for (int64_t x : s->sz) total += x;
+  if (total != n) return type_error("the server tensors do not hold the records' element count"), false;
+  return optimizer_rows(refs, theta, v, s->nt, &s->dev, s->sz.data(), true, &s->tp, &s->vp);
+}
+
 // fold_records(records, weights, n, k, levels, delta, theta, v, beta0, opt, lr, beta2, tau): the server update of a
 // round of stacked records (flc_fedopt_fold_records) on Python lists.  TypeError (nothing launched) when a tensor is
 // not what the pass takes — the server tensors contiguous fp32 HIP tensors of one device summing to n, the records
 // 16-B aligned uint8 tensors of at least the wire layout's bytes on that device — so the caller can take its other
 // path; theta / v None: the fold alone / no second moment.
-// (format kStackedRecords: stacked records of (n, k, levels); kSparseRecords: sparse records of (n, k), the
-// flc_sparse_wire_layout(n, k) layout; else dense records of (n, format, levels, bits))
-constexpr int kStackedRecords = -1, kSparseRecords = -2;
-PyObject* fold_records_of(PyObject* recs, PyObject* weights, long long n, long long k, int format, int levels, int bits,
-                          PyObject* delta, PyObject* theta, PyObject* v, double beta0, int opt, double lr, double beta2,
-                          double tau) {
+// (fold_records_of: one worker for the three uniform kinds, by the records' RecordShape)
+PyObject* fold_records_of(const RecordShape& shape, PyObject* recs, PyObject* weights, long long n, PyObject* delta,
+                          PyObject* theta, PyObject* v, double beta0, int opt, double lr, double beta2, double tau) {
   Refs refs;
-  PyObject* seqs[3] = {recs, weights, delta};
-  PyObject* f[3];
-  for (int i = 0; i < 3; ++i)
-    if (!(f[i] = refs.fast(seqs[i], "fold_records takes sequences"))) return nullptr;
-  const Py_ssize_t nr = len(f[0]), nt = len(f[2]);
-  if (len(f[1]) != nr) return value_error("one weight per record");
-  if (nr < 1 || nt < 1) return type_error("fold_records needs records and server tensors");
-  int dev = -1;
-  std::vector<float*> dp(nt), tp, vp;
-  std::vector<int64_t> sz(nt);
-  if (tensor_row(items(f[2]), nt, &dev, sz.data(), true, dp.data()))
-    return type_error("server tensors must be contiguous fp32 HIP tensors on one device");
-  int64_t total = 0;
-  for (int64_t s : sz) total += s;
-  if (total != n) return type_error("the server tensors do not hold the records' element count");
-  if (!optimizer_rows(refs, theta, v, nt, &dev, sz.data(), true, &tp, &vp)) return nullptr;
-  int64_t off[4];
-  const size_t stride = format == kSparseRecords    ? flc_sparse_wire_layout(n, k, off)
-                        : format == kStackedRecords ? flc_stacked_wire_layout(n, k, off)
-                                                    : flc_dense_wire_layout(n, format, bits, off);
+  ServerTables s;
+  if (!server_tables(refs, "fold_records takes sequences", "fold_records needs records and server tensors", recs,
+                     weights, delta, theta, v, n, [] { return true; }, &s))
+    return nullptr;
+  const size_t stride = shape.stride(n);
   if (stride == 0) return value_error("bad wire shape");
-  std::vector<const void*> rp(nr);
-  std::vector<float> w(nr);
-  for (Py_ssize_t c = 0; c < nr; ++c) {
-    if (!(rp[c] = record_ptr(items(f[0])[c], stride, &dev)))
+  std::vector<const void*> rp(s.nr);
+  std::vector<float> w(s.nr);
+  for (Py_ssize_t c = 0; c < s.nr; ++c) {
+    if (!(rp[c] = record_ptr(items(s.recs)[c], stride, &s.dev)))
       return type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the server's device");
-    if (!as_f32(items(f[1])[c], &w[c])) return nullptr;
+    if (!as_f32(items(s.weights)[c], &w[c])) return nullptr;
   }
-  float* const* thp = tp.empty() ? nullptr : tp.data();
-  float* const* vvp = vp.empty() ? nullptr : vp.data();
-  const char* fn = format == kSparseRecords    ? "flc_fedopt_fold_sparse_records"
-                   : format == kStackedRecords ? "flc_fedopt_fold_records"
-                                               : "flc_fedopt_fold_dense_records";
-  if (!on_device(dev, fn, [&](void* st) {
-        if (format == kSparseRecords)
-          return flc_fedopt_fold_sparse_records(rp.data(), w.data(), (int)nr, n, k, dp.data(), thp, vvp, sz.data(),
-                                                (int)nt, (float)beta0, opt, lr, beta2, tau, st);
-        return format < 0 ? flc_fedopt_fold_records(rp.data(), w.data(), (int)nr, n, k, levels, dp.data(), thp, vvp,
-                                                    sz.data(), (int)nt, (float)beta0, opt, lr, beta2, tau, st)
-                          : flc_fedopt_fold_dense_records(rp.data(), w.data(), (int)nr, n, format, levels, bits, dp.data(),
-                                                          thp, vvp, sz.data(), (int)nt, (float)beta0, opt, lr, beta2, tau,
-                                                          st);
+  if (!on_device(s.dev, shape.name(kFedOptForm), [&](void* st) {
+        return shape.fedopt(rp.data(), w.data(), (int)s.nr, n, s.dp.data(), s.theta(), s.v(), s.sz.data(), (int)s.nt,
+                            (float)beta0, opt, lr, beta2, tau, st);
       }))
     return nullptr;
   Py_RETURN_NONE;
@@ -703,7 +765,7 @@ PyObject* fold_records(PyObject*, PyObject* args) {
   if (!PyArg_ParseTuple(args, "OOLLiOOOdiddd", &recs, &weights, &n, &k, &levels, &delta, &theta, &v, &beta0, &opt, &lr,
                         &beta2, &tau))
     return nullptr;
-  return fold_records_of(recs, weights, n, k, kStackedRecords, levels, 0, delta, theta, v, beta0, opt, lr, beta2, tau);
+  return fold_records_of(stacked_shape(k, levels), recs, weights, n, delta, theta, v, beta0, opt, lr, beta2, tau);
 }
 // fold_sparse_records(records, weights, n, k, delta, theta, v, beta0, opt, lr, beta2, tau): the same for a round of
 // sparse records (flc_fedopt_fold_sparse_records; the flc_sparse_wire_layout(n, k) layout of a top-k / rand-k message)
@@ -715,7 +777,7 @@ PyObject* fold_sparse_records(PyObject*, PyObject* args) {
   if (!PyArg_ParseTuple(args, "OOLLOOOdiddd", &recs, &weights, &n, &k, &delta, &theta, &v, &beta0, &opt, &lr, &beta2,
                         &tau))
     return nullptr;
-  return fold_records_of(recs, weights, n, k, kSparseRecords, 0, 0, delta, theta, v, beta0, opt, lr, beta2, tau);
+  return fold_records_of(sparse_shape(k), recs, weights, n, delta, theta, v, beta0, opt, lr, beta2, tau);
 }
 // fold_dense_records(records, weights, n, format, levels, bits, delta, theta, v, beta0, opt, lr, beta2, tau): the same
 // for a round of dense records (flc_fedopt_fold_dense_records; the flc_dense_wire_layout(n, format, bits) layout)
@@ -727,8 +789,9 @@ PyObject* fold_dense_records(PyObject*, PyObject* args) {
   if (!PyArg_ParseTuple(args, "OOLiiiOOOdiddd", &recs, &weights, &n, &format, &levels, &bits, &delta, &theta, &v, &beta0,
                         &opt, &lr, &beta2, &tau))
     return nullptr;
-  if (format < 0) return value_error("bad wire shape");
-  return fold_records_of(recs, weights, n, 0, format, levels, bits, delta, theta, v, beta0, opt, lr, beta2, tau);
+  if (format < 0) return value_error("bad wire shape");  // (before anything else is looked at)
+  return fold_records_of(dense_shape(format, levels, bits), recs, weights, n, delta, theta, v, beta0, opt, lr, beta2,
+                         tau);
 }
 
 // A sequence of `want` Python ints into *out; false with the error set (TypeError for another length).
@@ -764,54 +827,38 @@ PyObject* fold_mixed_records(PyObject*, PyObject* args) {
                         &beta0, &opt, &lr, &beta2, &tau))
     return nullptr;
   Refs refs;
-  PyObject* seqs[3] = {recs, weights, delta};
-  PyObject* f[3];
-  for (int i = 0; i < 3; ++i)
-    if (!(f[i] = refs.fast(seqs[i], "fold_mixed_records takes sequences"))) return nullptr;
-  const Py_ssize_t nr = len(f[0]), nt = len(f[2]);
-  if (len(f[1]) != nr) return value_error("one weight per record");
-  if (nr < 1 || nt < 1) return type_error("fold_mixed_records needs records and server tensors");
+  ServerTables s;
   std::vector<int32_t> kd, fm, lv, bt;
   std::vector<int64_t> kk;
-  if (!int_row(refs, kinds, nr, &kd) || !int_row(refs, ks, nr, &kk) || !int_row(refs, fmts, nr, &fm) ||
-      !int_row(refs, lvs, nr, &lv) || !int_row(refs, bts, nr, &bt))
+  auto descriptors = [&] {
+    return int_row(refs, kinds, s.nr, &kd) && int_row(refs, ks, s.nr, &kk) && int_row(refs, fmts, s.nr, &fm) &&
+           int_row(refs, lvs, s.nr, &lv) && int_row(refs, bts, s.nr, &bt);
+  };
+  if (!server_tables(refs, "fold_mixed_records takes sequences", "fold_mixed_records needs records and server tensors",
+                     recs, weights, delta, theta, v, n, descriptors, &s))
     return nullptr;
-  int dev = -1;
-  std::vector<float*> dp(nt), tp, vp;
-  std::vector<int64_t> sz(nt);
-  if (tensor_row(items(f[2]), nt, &dev, sz.data(), true, dp.data()))
-    return type_error("server tensors must be contiguous fp32 HIP tensors on one device");
-  int64_t total = 0;
-  for (int64_t s : sz) total += s;
-  if (total != n) return type_error("the server tensors do not hold the records' element count");
-  if (!optimizer_rows(refs, theta, v, nt, &dev, sz.data(), true, &tp, &vp)) return nullptr;
+  const Py_ssize_t nr = s.nr;
   std::vector<const void*> rp(nr);
   std::vector<float> w(nr);
   for (Py_ssize_t c = 0; c < nr; ++c) {
     if (kd[c] == FLC_REC_FLAT) {
       int64_t want = n;
       const float* x = nullptr;
-      if (take(items(f[0])[c], &dev, &want, false, &x) || reinterpret_cast<uintptr_t>(x) % 16 != 0)
+      if (take(items(s.recs)[c], &s.dev, &want, false, &x) || reinterpret_cast<uintptr_t>(x) % 16 != 0)
         return type_error("a flat record must be a 16-B aligned contiguous fp32 HIP tensor of n elements on the server's device");
       rp[c] = x;
     } else {
-      int64_t off[4];
-      size_t stride = 0;
-      if (kd[c] == FLC_REC_STACKED) stride = flc_stacked_wire_layout(n, kk[c], off);
-      else if (kd[c] == FLC_REC_SPARSE) stride = flc_sparse_wire_layout(n, kk[c], off);
-      else if (kd[c] == FLC_REC_DENSE) stride = flc_dense_wire_layout(n, fm[c], bt[c], off);
+      const size_t stride = RecordShape{kd[c], kk[c], fm[c], lv[c], bt[c]}.stride(n);
       if (stride == 0) return value_error("bad wire shape");
-      if (!(rp[c] = record_ptr(items(f[0])[c], stride, &dev)))
+      if (!(rp[c] = record_ptr(items(s.recs)[c], stride, &s.dev)))
         return type_error("records must be 16-B aligned uint8 HIP tensors of the wire layout on the server's device");
     }
-    if (!as_f32(items(f[1])[c], &w[c])) return nullptr;
+    if (!as_f32(items(s.weights)[c], &w[c])) return nullptr;
   }
-  float* const* thp = tp.empty() ? nullptr : tp.data();
-  float* const* vvp = vp.empty() ? nullptr : vp.data();
-  if (!on_device(dev, "flc_fedopt_fold_mixed_records", [&](void* st) {
+  if (!on_device(s.dev, "flc_fedopt_fold_mixed_records", [&](void* st) {
         return flc_fedopt_fold_mixed_records(rp.data(), w.data(), (int)nr, n, kd.data(), kk.data(), fm.data(), lv.data(),
-                                             bt.data(), dp.data(), thp, vvp, sz.data(), (int)nt, (float)beta0, opt, lr,
-                                             beta2, tau, st);
+                                             bt.data(), s.dp.data(), s.theta(), s.v(), s.sz.data(), (int)s.nt,
+                                             (float)beta0, opt, lr, beta2, tau, st);
       }))
     return nullptr;
   Py_RETURN_NONE;
@@ -836,8 +883,8 @@ PyObject* fold_record_groups(PyObject*, PyObject* args) {
   const Py_ssize_t ng = len(fd);
   if (ng < 1 || len(fr) != ng || len(fw) != ng)
     return type_error("fold_record_groups needs one record list, weight list and tensor list per group");
-  int64_t off[4];
-  const size_t stride = flc_stacked_wire_layout(n, k, off);
+  const RecordShape shape = stacked_shape(k, levels);  // (the grouped fold's only one-call entry)
+  const size_t stride = shape.stride(n);
   if (stride == 0) return value_error("bad wire shape");
   int dev = -1;
   std::vector<float*> dp;
@@ -880,9 +927,9 @@ PyObject* fold_record_groups(PyObject*, PyObject* args) {
       gof.push_back((int32_t)g);
     }
   }
-  if (!on_device(dev, "flc_fold_record_groups", [&](void* st) {
-        return flc_fold_record_groups(rp.data(), w.data(), gof.data(), (int)rp.size(), n, k, levels, dp.data(), (int)ng,
-                                      sz.data(), (int)sz.size(), st);
+  if (!on_device(dev, shape.name(kGroupForm), [&](void* st) {
+        return shape.groups(rp.data(), w.data(), gof.data(), (int)rp.size(), n, dp.data(), (int)ng, sz.data(),
+                            (int)sz.size(), st);
       }))
     return nullptr;
   Py_RETURN_NONE;
@@ -894,12 +941,9 @@ PyObject* fold_record_groups(PyObject*, PyObject* args) {
 // unused); the gradients decoded and folded into one new flat fp32 buffer on the model's device, returned as (list of
 // per-parameter views, flat buffer); with `set_grad` each parameter's `.grad` is set to its view.  TypeError (nothing
 // allocated or launched) when a tensor is not what the pass takes, as fold_records and avg_and_gradients raise it.
-// (format kStackedRecords: stacked records of (n, k, levels) — flc_avg_and_gradient_records; kSparseRecords: sparse
-// records of (n, k) — flc_avg_and_gradient_sparse_records; else dense records of (n, format, levels, bits) —
-// flc_avg_and_gradient_dense_records: one worker, as fold_records_of is the FedOpt entries')
-PyObject* avg_and_gradient_records_of(PyObject* params, PyObject* msgs, PyObject* recs, PyObject* wpar, PyObject* wgrd,
-                                      long long n, long long k, int format, int levels, int bits, double inertia,
-                                      int set_grad) {
+// (avg_and_gradient_records_of: one worker for the three uniform kinds, as fold_records_of is the FedOpt entries')
+PyObject* avg_and_gradient_records_of(const RecordShape& shape, PyObject* params, PyObject* msgs, PyObject* recs,
+                                      PyObject* wpar, PyObject* wgrd, long long n, double inertia, int set_grad) {
   Refs refs;
   const bool p_on = msgs != Py_None;
   PyObject* seqs[5] = {params, recs, wgrd, p_on ? msgs : recs, p_on ? wpar : wgrd};
@@ -919,10 +963,7 @@ PyObject* avg_and_gradient_records_of(PyObject* params, PyObject* msgs, PyObject
   int64_t total = 0;
   for (int64_t s : sz) total += s;
   if (total != n) return type_error("the model tensors do not hold the records' element count");
-  int64_t off4[4];
-  const size_t stride = format == kSparseRecords    ? flc_sparse_wire_layout(n, k, off4)
-                        : format == kStackedRecords ? flc_stacked_wire_layout(n, k, off4)
-                                                    : flc_dense_wire_layout(n, format, bits, off4);
+  const size_t stride = shape.stride(n);
   if (stride == 0) return value_error("bad wire shape");
   std::vector<const void*> rp(ns);
   std::vector<const float*> ps(p_on ? (size_t)ns * nt : 0);
@@ -945,18 +986,9 @@ PyObject* avg_and_gradient_records_of(PyObject* params, PyObject* msgs, PyObject
   float* const* ppp = p_on ? pp.data() : nullptr;
   const float* const* psp = p_on ? ps.data() : nullptr;
   const float* wpp = p_on ? wp.data() : nullptr;
-  const char* fn = format == kSparseRecords    ? "flc_avg_and_gradient_sparse_records"
-                   : format == kStackedRecords ? "flc_avg_and_gradient_records"
-                                               : "flc_avg_and_gradient_dense_records";
-  if (!on_device(dev, fn, [&](void* st) {
-        if (format == kSparseRecords)
-          return flc_avg_and_gradient_sparse_records(ppp, gp.data(), psp, rp.data(), wpp, wg.data(), (int)ns, n, k,
-                                                     sz.data(), (int)nt, (float)inertia, st);
-        return format < 0 ? flc_avg_and_gradient_records(ppp, gp.data(), psp, rp.data(), wpp, wg.data(), (int)ns, n, k,
-                                                         levels, sz.data(), (int)nt, (float)inertia, st)
-                          : flc_avg_and_gradient_dense_records(ppp, gp.data(), psp, rp.data(), wpp, wg.data(), (int)ns,
-                                                               n, format, levels, bits, sz.data(), (int)nt,
-                                                               (float)inertia, st);
+  if (!on_device(dev, shape.name(kGradientForm), [&](void* st) {
+        return shape.gradient(ppp, gp.data(), psp, rp.data(), wpp, wg.data(), (int)ns, n, sz.data(), (int)nt,
+                              (float)inertia, st);
       }))
     return nullptr;
   return views_result(pt, gv, flat, set_grad != 0);
@@ -968,8 +1000,7 @@ PyObject* avg_and_gradient_records(PyObject*, PyObject* args) {
   double inertia;
   if (!PyArg_ParseTuple(args, "OOOOOLLid|p", &params, &msgs, &recs, &wpar, &wgrd, &n, &k, &levels, &inertia, &set_grad))
     return nullptr;
-  return avg_and_gradient_records_of(params, msgs, recs, wpar, wgrd, n, k, kStackedRecords, levels, 0, inertia,
-                                     set_grad);
+  return avg_and_gradient_records_of(stacked_shape(k, levels), params, msgs, recs, wpar, wgrd, n, inertia, set_grad);
 }
 // avg_and_gradient_sparse_records(params, msgs, records, w_params, w_grads, n, k, inertia, set_grad): the same for a
 // round of sparse records (flc_avg_and_gradient_sparse_records; the flc_sparse_wire_layout(n, k) layout)
@@ -980,7 +1011,7 @@ PyObject* avg_and_gradient_sparse_records(PyObject*, PyObject* args) {
   double inertia;
   if (!PyArg_ParseTuple(args, "OOOOOLLd|p", &params, &msgs, &recs, &wpar, &wgrd, &n, &k, &inertia, &set_grad))
     return nullptr;
-  return avg_and_gradient_records_of(params, msgs, recs, wpar, wgrd, n, k, kSparseRecords, 0, 0, inertia, set_grad);
+  return avg_and_gradient_records_of(sparse_shape(k), params, msgs, recs, wpar, wgrd, n, inertia, set_grad);
 }
 // avg_and_gradient_dense_records(params, msgs, records, w_params, w_grads, n, format, levels, bits, inertia, set_grad):
 // the same for a round of dense records (flc_avg_and_gradient_dense_records; the flc_dense_wire_layout(n, format, bits)
@@ -993,8 +1024,9 @@ PyObject* avg_and_gradient_dense_records(PyObject*, PyObject* args) {
   if (!PyArg_ParseTuple(args, "OOOOOLiiid|p", &params, &msgs, &recs, &wpar, &wgrd, &n, &format, &levels, &bits, &inertia,
                         &set_grad))
     return nullptr;
-  if (format < 0) return value_error("bad wire shape");
-  return avg_and_gradient_records_of(params, msgs, recs, wpar, wgrd, n, 0, format, levels, bits, inertia, set_grad);
+  if (format < 0) return value_error("bad wire shape");  // (before anything else is looked at)
+  return avg_and_gradient_records_of(dense_shape(format, levels, bits), params, msgs, recs, wpar, wgrd, n, inertia,
+                                     set_grad);
 }
 
 void release_storage(void* ctx) { delete static_cast<c10::Storage*>(ctx); }

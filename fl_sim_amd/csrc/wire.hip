@@ -53,6 +53,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -1261,6 +1262,65 @@ int mixed_chunk(const MixedRound& mx, int c0, int cap, MixedDesc* d) {
   return nw;
 }
 
+// What a round's records are, as every host-side fold below takes it: entry records (stacked or sparse) of one
+// (n, k, levels), dense records of one DenseCodec, or (mx) a mixed round, every record by its own descriptor.
+struct RoundCodec {
+  int64_t n;
+  RecordKind kind = kRecStacked;  // the entry codec (neither dense nor mixed)
+  int64_t k = 0;
+  int levels = 1;
+  bool is_dense = false;
+  DenseCodec dense{};
+  const MixedRound* mx = nullptr;
+
+  static RoundCodec entry(RecordKind kind, int64_t n, int64_t k, int levels) {
+    RoundCodec c{n};
+    c.kind = kind, c.k = k, c.levels = levels;
+    return c;
+  }
+  static RoundCodec dense_records(int64_t n, int format, int levels, int bits) {
+    RoundCodec c{n};
+    c.is_dense = true, c.dense = DenseCodec{format, levels, bits, n};
+    return c;
+  }
+  static RoundCodec mixed(int64_t n, const MixedRound* mx) {
+    RoundCodec c{n};
+    c.mx = mx;
+    return c;
+  }
+
+  // the codec's own argument rule (a mixed round's is check_mixed_round, run by its entry point before anything else)
+  int check(const char* fn) const {
+    if (mx) return FLC_OK;
+    if (is_dense) return check_dense_format(fn, dense.format, dense.levels, dense.bits);
+    return check_entry_codec(fn, kind, n, k, levels);
+  }
+  // bytes of one record of a uniform round (after check)
+  size_t record_size() const {
+    size_t need = 0;
+    if (is_dense) return dense_wire_size(n, dense.format, dense.bits);
+    record_layout(kind, n, k, &need);
+    return need;
+  }
+  // record `c` of the round as entry `pos` of a launch; false: a mixed launch's level tables are full
+  bool take(int c, MixedDesc* d, int pos) const { return !mx || mixed_take(*mx, c, d, pos); }
+  // how many records the next launch takes from round position c0: `cap`, fewer where a mixed launch's tables run out
+  int chunk(int c0, int cap, MixedDesc* d) const { return mx ? mixed_chunk(*mx, c0, cap, d) : cap; }
+  // one launch of the fold: the kernel by the round's codec (`sparse_form`: entry records only; `d`: mixed rounds only)
+  template <class IO>
+  int launch(const char* probe, bool sparse_form, dim3 grid, hipStream_t st, const FoldArgs& a, const MixedDesc& d,
+             int nw, int64_t tile_lo, const IO& io) const {
+    if constexpr (!std::is_same_v<IO, FlatIO>) {  // (the wire folds have no mixed form)
+      if (mx) return launch_mixed_fold(probe, grid, st, a, d, nw, n, tile_lo, io);
+    }
+    if (is_dense) return launch_dense_fold(probe, dense, grid, st, a, nw, tile_lo, io);
+    size_t need = 0;
+    const WireLayout L = record_layout(kind, n, k, &need);
+    return launch_entry_fold(probe, kind, sparse_form, grid, st, a, L, nw, levels,
+                             1.0 / (double)(levels < 1 ? 1 : levels), tile_lo, io, (unsigned)k);
+  }
+};
+
 }  // namespace
 }  // namespace flc
 
@@ -1293,17 +1353,21 @@ size_t flc_sparse_wire_layout(int64_t n, int64_t k, int64_t* offsets) {
   return total;
 }
 
-// flc_stacked_fold_wires (kRecStacked) and flc_fold_sparse_wires (kRecSparse): one argument check, one chain of
-// launches, the kernel's entry codec by the records' kind
-static int fold_wires_impl(const char* fn, const char* probe, RecordKind kind, const void* wires, int64_t stride,
-                           const int32_t* slots, const float* weights, int n_wires, int64_t n, int64_t k, int levels,
-                           int accumulate, float* out, void* stream) {
+// flc_stacked_fold_wires, flc_fold_sparse_wires and flc_fold_dense_wires: one argument check, one chain of launches
+// (a chained launch continues from the stored out), the kernel by the records' codec
+static int fold_wires_impl(const char* fn, const char* probe, const RoundCodec& codec, const void* wires,
+                           int64_t stride, const int32_t* slots, const float* weights, int n_wires, int accumulate,
+                           float* out, void* stream) {
+  const int64_t n = codec.n, k = codec.k;
   if (!wires || !slots || !weights || !out || n_wires < 1 || n <= 0 || k < 0)
     return fail(FLC_EINVAL, "%s: bad arguments", fn);
-  if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
-  if (int rc = check_entry_codec(fn, kind, n, k, levels)) return rc;
-  size_t need = 0;
-  const WireLayout L = record_layout(kind, n, k, &need);
+  if (codec.is_dense) {
+    if (n >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n must be < 2^31", fn);
+  } else if (n >= (1ll << 31) || k >= (1ll << 31)) {
+    return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
+  }
+  if (int rc = codec.check(fn)) return rc;
+  const size_t need = codec.record_size();
   if (stride < (int64_t)need || stride % 16 != 0)
     return fail(FLC_EINVAL, "%s: stride %lld < record size %zu (or not 16-B aligned)", fn, (long long)stride, need);
   if (!aligned16(wires) || !aligned16(out)) return fail(FLC_EINVAL, "%s: 16-B aligned buffers required", fn);
@@ -1311,12 +1375,12 @@ static int fold_wires_impl(const char* fn, const char* probe, RecordKind kind, c
     if (slots[c] < 0) return fail(FLC_EINVAL, "%s: slot %d is negative", fn, c);
   hipStream_t st = as_stream(stream);
   const int64_t ntiles = cdiv(n, (int64_t)FLC_TILE);
-  const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
-  // Sparse fold (from +0, finite weights): only the kept entries are fma'd, and a final -0 is resolved as the dense
-  // chain would (kernel header).  Otherwise (accumulating into a given vector, or a non-finite weight) every element
-  // takes every client's fma.
+  // Sparse fold (entry records, from +0, finite weights): only the kept entries are fma'd, and a final -0 is resolved
+  // as the dense chain would (kernel header).  Otherwise (accumulating into a given vector, or a non-finite weight)
+  // every element takes every client's fma.
   bool sparse = !accumulate;
   for (int c = 0; c < n_wires; ++c) sparse = sparse && std::isfinite(weights[c]);
+  const MixedDesc none{};
   for (int c0 = 0; c0 < n_wires; c0 += kMaxWires) {
     const int nw = std::min(kMaxWires, n_wires - c0);
     FoldArgs a;
@@ -1325,47 +1389,36 @@ static int fold_wires_impl(const char* fn, const char* probe, RecordKind kind, c
       a.rec[c] = static_cast<const uint8_t*>(wires) + (c < nw ? (int64_t)slots[c0 + c] * stride : 0);
     }
     const FlatIO io{out, n, (c0 > 0 || accumulate) ? 1 : 0};
-    if (int rc = launch_entry_fold(probe, kind, sparse, dim3((unsigned)ntiles), st, a, L, nw, levels, step, (int64_t)0,
-                                   io, (unsigned)k))
-      return rc;
+    if (int rc = codec.launch(probe, sparse, dim3((unsigned)ntiles), st, a, none, nw, (int64_t)0, io)) return rc;
   }
   return FLC_OK;
 }
 
 int flc_stacked_fold_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
                            int64_t n, int64_t k, int levels, int accumulate, float* out, void* stream) {
-  return fold_wires_impl("flc_stacked_fold_wires", "stacked_fold_wires", kRecStacked, wires, stride, slots, weights,
-                         n_wires, n, k, levels, accumulate, out, stream);
+  return fold_wires_impl("flc_stacked_fold_wires", "stacked_fold_wires", RoundCodec::entry(kRecStacked, n, k, levels),
+                         wires, stride, slots, weights, n_wires, accumulate, out, stream);
 }
 
 int flc_fold_sparse_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
                           int64_t n, int64_t k, int accumulate, float* out, void* stream) {
-  return fold_wires_impl("flc_fold_sparse_wires", "fold_sparse_wires", kRecSparse, wires, stride, slots, weights,
-                         n_wires, n, k, 0, accumulate, out, stream);
+  return fold_wires_impl("flc_fold_sparse_wires", "fold_sparse_wires", RoundCodec::entry(kRecSparse, n, k, 0), wires,
+                         stride, slots, weights, n_wires, accumulate, out, stream);
 }
 
-// flc_fedopt_fold_records (dense == NULL, kRecStacked: stacked records of (n, k, levels)), flc_fedopt_fold_sparse_records
-// (dense == NULL, kRecSparse: sparse records of (n, k)) and flc_fedopt_fold_dense_records (the records of *dense): one
-// argument check, one chain of launches, the kernel by the records' codec.  `fn` names the entry point in messages,
-// `probe` its launches for flc_probe_set.
-// (mx != NULL: flc_fedopt_fold_mixed_records — the records' own descriptors, checked by the caller, in place of the
-// launch-wide codec; a launch ends at 64 records or where its level tables run out)
-static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec* dense, RecordKind kind,
-                            const void* const* records,
-                            const float* weights, int n_records, int64_t n, int64_t k, int levels,
-                            float* const* delta, float* const* theta, float* const* v, const int64_t* sizes,
-                            int n_tensors, float beta0, int opt, double lr, double beta2, double tau, void* stream,
-                            const MixedRound* mx = nullptr) {
+// The FedOpt folds (flc_fedopt_fold_records, _sparse_records, _dense_records, _mixed_records): one argument check, one
+// chain of launches, the kernel by the round's codec.  `fn` names the entry point in messages, `probe` its launches
+// for flc_probe_set.  (A mixed launch ends at 64 records or where its level tables run out.)
+static int fedopt_fold_impl(const char* fn, const char* probe, const RoundCodec& codec, const void* const* records,
+                            const float* weights, int n_records, float* const* delta, float* const* theta,
+                            float* const* v, const int64_t* sizes, int n_tensors, float beta0, int opt, double lr,
+                            double beta2, double tau, void* stream) {
+  const int64_t n = codec.n, k = codec.k;
   if (n_records < 0 || (n_records > 0 && (!records || !weights)) || n <= 0 || k < 0 || n_tensors < 1 || !delta ||
       !sizes)
     return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
-  if (mx) {
-  } else if (dense) {
-    if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
-  } else if (int rc = check_entry_codec(fn, kind, n, k, levels)) {
-    return rc;
-  }
+  if (int rc = codec.check(fn)) return rc;
   const bool step_on = theta != nullptr;
   if (step_on && opt != FLC_OPT_AVG && opt != FLC_OPT_ADAGRAD && opt != FLC_OPT_YOGI && opt != FLC_OPT_ADAM)
     return fail(FLC_EINVAL, "%s: unknown optimiser %d", fn, opt);
@@ -1383,18 +1436,14 @@ static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec*
   for (int c = 0; c < n_records; ++c)
     if (!records[c] || !aligned16(records[c]))
       return fail(FLC_EINVAL, "%s: record %d is null or not 16-B aligned", fn, c);
-  size_t need = 0;
-  const WireLayout L = record_layout(kind, n, k, &need);
   hipStream_t st = as_stream(stream);
-  const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   const float omb = (float)(1.0 - beta2), nomb = (float)(-(1.0 - beta2));
   // record chunks in order (the chain continues from the stored δ, the step after the last chunk only); within a
   // chunk, one launch per group of <= kRoundT tensors over the tiles their flat range touches
   int c0 = 0;
   do {
-    int nw = std::min(kMaxWires, n_records - c0);
     MixedDesc md;
-    if (mx) nw = mixed_chunk(*mx, c0, nw, &md);
+    const int nw = codec.chunk(c0, std::min(kMaxWires, n_records - c0), &md);
     const bool last = c0 + nw >= n_records;
     FoldArgs a;
     for (int c = 0; c < kMaxWires; ++c) {
@@ -1428,16 +1477,10 @@ static int fedopt_fold_impl(const char* fn, const char* probe, const DenseCodec*
       m.start[m.nt] = off;
       const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
       const dim3 grid((unsigned)(tile_hi - tile_lo));
-#define FLC_FR(O)                                                                                                 \
-  do {                                                                                                            \
-    if (mx) {                                                                                                     \
-      if (int rc = launch_mixed_fold(probe, grid, st, a, md, nw, n, tile_lo, ModelIO<O>{m})) return rc;           \
-    } else if (dense) {                                                                                           \
-      if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, ModelIO<O>{m})) return rc;          \
-    } else if (int rc = launch_entry_fold(probe, kind, false, grid, st, a, L, nw, levels, step, tile_lo,          \
-                                          ModelIO<O>{m}, (unsigned)k)) {                                          \
-      return rc;                                                                                                  \
-    }                                                                                                             \
+      // (never the sparse form: δ continues from β0·δ, and ModelIO has none)
+#define FLC_FR(O)                                                                                       \
+  do {                                                                                                  \
+    if (int rc = codec.launch(probe, false, grid, st, a, md, nw, tile_lo, ModelIO<O>{m})) return rc;    \
   } while (0)
       if (!step_on || !last) FLC_FR(-1);
       else if (opt == FLC_OPT_AVG) FLC_FR(FLC_OPT_AVG);
@@ -1455,49 +1498,44 @@ int flc_fedopt_fold_records(const void* const* records, const float* weights, in
                             int levels, float* const* delta, float* const* theta, float* const* v,
                             const int64_t* sizes, int n_tensors, float beta0, int opt, double lr, double beta2,
                             double tau, void* stream) {
-  return fedopt_fold_impl("flc_fedopt_fold_records", "fedopt_fold_records", nullptr, kRecStacked, records, weights,
-                          n_records, n, k, levels, delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau, stream);
+  return fedopt_fold_impl("flc_fedopt_fold_records", "fedopt_fold_records",
+                          RoundCodec::entry(kRecStacked, n, k, levels), records, weights, n_records, delta, theta, v,
+                          sizes, n_tensors, beta0, opt, lr, beta2, tau, stream);
 }
 
 int flc_fedopt_fold_sparse_records(const void* const* records, const float* weights, int n_records, int64_t n,
                                    int64_t k, float* const* delta, float* const* theta, float* const* v,
                                    const int64_t* sizes, int n_tensors, float beta0, int opt, double lr, double beta2,
                                    double tau, void* stream) {
-  return fedopt_fold_impl("flc_fedopt_fold_sparse_records", "fedopt_fold_sparse_records", nullptr, kRecSparse, records,
-                          weights, n_records, n, k, 0, delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau,
-                          stream);
+  return fedopt_fold_impl("flc_fedopt_fold_sparse_records", "fedopt_fold_sparse_records",
+                          RoundCodec::entry(kRecSparse, n, k, 0), records, weights, n_records, delta, theta, v, sizes,
+                          n_tensors, beta0, opt, lr, beta2, tau, stream);
 }
 
 int flc_fedopt_fold_dense_records(const void* const* records, const float* weights, int n_records, int64_t n,
                                   int format, int levels, int bits, float* const* delta, float* const* theta,
                                   float* const* v, const int64_t* sizes, int n_tensors, float beta0, int opt,
                                   double lr, double beta2, double tau, void* stream) {
-  const DenseCodec cd{format, levels, bits, n};
-  return fedopt_fold_impl("flc_fedopt_fold_dense_records", "fedopt_fold_dense_records", &cd, kRecStacked, records,
-                          weights, n_records, n, 0, levels, delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau,
-                          stream);
+  return fedopt_fold_impl("flc_fedopt_fold_dense_records", "fedopt_fold_dense_records",
+                          RoundCodec::dense_records(n, format, levels, bits), records, weights, n_records, delta, theta,
+                          v, sizes, n_tensors, beta0, opt, lr, beta2, tau, stream);
 }
 
-// flc_avg_and_gradient_records (dense == NULL, kRecStacked), flc_avg_and_gradient_sparse_records (dense == NULL,
-// kRecSparse) and flc_avg_and_gradient_dense_records (the records of *dense), as fedopt_fold_impl serves the FedOpt
-// folds: one argument check and one chain of launches, the kernel by the records' codec
-static int avg_and_gradient_impl(const char* fn, const char* probe, const DenseCodec* dense, RecordKind kind,
-                                 float* const* params, float* const* grads, const float* const* param_srcs,
+// The variance-reduced servers' folds (flc_avg_and_gradient_records, _sparse_records, _dense_records, _mixed_records),
+// as fedopt_fold_impl serves the FedOpt folds: one argument check and one chain of launches, the kernel by the round's
+// codec
+static int avg_and_gradient_impl(const char* fn, const char* probe, const RoundCodec& codec, float* const* params,
+                                 float* const* grads, const float* const* param_srcs,
                                  const void* const* grad_records, const float* w_params, const float* w_grads,
-                                 int n_src, int64_t n, int64_t k, int levels, const int64_t* sizes, int n_tensors,
-                                 float inertia, void* stream, const MixedRound* mx = nullptr) {
+                                 int n_src, const int64_t* sizes, int n_tensors, float inertia, void* stream) {
+  const int64_t n = codec.n, k = codec.k;
   const bool p_on = param_srcs != nullptr;
   if (n_src < 1 || !grad_records || !w_grads || n <= 0 || k < 0 || n_tensors < 1 || !grads || !sizes ||
       (p_on && (!params || !w_params)))
     return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (n >= (1ll << 31) || k >= (1ll << 31))
     return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
-  if (mx) {
-  } else if (dense) {
-    if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
-  } else if (int rc = check_entry_codec(fn, kind, n, k, levels)) {
-    return rc;
-  }
+  if (int rc = codec.check(fn)) return rc;
   int64_t total = 0;
   for (int t = 0; t < n_tensors; ++t) {
     if (sizes[t] < 0) return fail(FLC_EINVAL, "%s: negative size for tensor %d", fn, t);
@@ -1515,28 +1553,23 @@ static int avg_and_gradient_impl(const char* fn, const char* probe, const DenseC
   for (int c = 0; c < n_src; ++c)
     if (!grad_records[c] || !aligned16(grad_records[c]))
       return fail(FLC_EINVAL, "%s: record %d is null or not 16-B aligned", fn, c);
-  size_t need = 0;
-  const WireLayout L = record_layout(kind, n, k, &need);
   hipStream_t st = as_stream(stream);
-  const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   // the gradient chain starts at +0: with finite weights only the kept entries are fma'd (the sparse form, its -0
   // rule as in flc_stacked_fold_wires); a non-finite weight takes every element through every record's fma.  (Dense
   // records carry a code for every element: their fold has no sparse form and needs no -0 replay.)
   bool sparse = true;
   for (int c = 0; c < n_src; ++c) sparse = sparse && std::isfinite(w_grads[c]);
-  // launch i of the chain folds records [64 i, 64 i + 64) and parameter sources [16 i, 16 i + 16), each chain
-  // continuing from its stored partial result; within it, one launch per group of <= kRoundT tensors
-  // (a mixed round: a record launch ends at 64 records or where its level tables run out — `cuts` holds the starts)
+  // launch i of the chain folds the i-th chunk of records (64; a mixed round's ends earlier where its level tables run
+  // out — `cuts` holds the chunks' starts) and parameter sources [16 i, 16 i + 16), each chain continuing from its
+  // stored partial result; within it, one launch per group of <= kRoundT tensors
   std::vector<int> cuts;
   MixedDesc md;
-  if (mx)
-    for (int c = 0; c < n_src; c += mixed_chunk(*mx, c, std::min(kMaxWires, n_src - c), &md)) cuts.push_back(c);
-  const int r_launches = mx ? (int)cuts.size() : (int)cdiv((int64_t)n_src, (int64_t)kMaxWires);
+  for (int c = 0; c < n_src; c += codec.chunk(c, std::min(kMaxWires, n_src - c), &md)) cuts.push_back(c);
+  const int r_launches = (int)cuts.size();
   const int p_launches = p_on ? (int)cdiv((int64_t)n_src, (int64_t)kPairSrc) : 0;
   for (int i = 0; i < std::max(r_launches, p_launches); ++i) {
-    const int c0 = mx ? (i < r_launches ? cuts[i] : n_src) : i * kMaxWires, s0 = i * kPairSrc;
-    int nw = i < r_launches ? std::min(kMaxWires, n_src - c0) : 0;
-    if (mx) nw = mixed_chunk(*mx, c0, nw, &md);
+    const int c0 = i < r_launches ? cuts[i] : n_src, s0 = i * kPairSrc;
+    const int nw = codec.chunk(c0, i < r_launches ? std::min(kMaxWires, n_src - c0) : 0, &md);
     const int ns = i < p_launches ? std::min(kPairSrc, n_src - s0) : 0;
     FoldArgs a;
     for (int c = 0; c < kMaxWires; ++c) {
@@ -1574,14 +1607,7 @@ static int avg_and_gradient_impl(const char* fn, const char* probe, const DenseC
       m.start[m.nt] = off;
       const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
       const dim3 grid((unsigned)(tile_hi - tile_lo));
-      if (mx) {
-        if (int rc = launch_mixed_fold(probe, grid, st, a, md, nw, n, tile_lo, io)) return rc;
-      } else if (dense) {
-        if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, io)) return rc;
-      } else if (int rc = launch_entry_fold(probe, kind, sparse, grid, st, a, L, nw, levels, step, tile_lo, io,
-                                            (unsigned)k)) {
-        return rc;
-      }
+      if (int rc = codec.launch(probe, sparse, grid, st, a, md, nw, tile_lo, io)) return rc;
     }
   }
   return FLC_OK;
@@ -1591,47 +1617,40 @@ int flc_avg_and_gradient_records(float* const* params, float* const* grads, cons
                                  const void* const* grad_records, const float* w_params, const float* w_grads,
                                  int n_src, int64_t n, int64_t k, int levels, const int64_t* sizes, int n_tensors,
                                  float inertia, void* stream) {
-  return avg_and_gradient_impl("flc_avg_and_gradient_records", "avg_and_gradient_records", nullptr, kRecStacked, params,
-                               grads, param_srcs, grad_records, w_params, w_grads, n_src, n, k, levels, sizes,
-                               n_tensors, inertia, stream);
+  return avg_and_gradient_impl("flc_avg_and_gradient_records", "avg_and_gradient_records",
+                               RoundCodec::entry(kRecStacked, n, k, levels), params, grads, param_srcs, grad_records,
+                               w_params, w_grads, n_src, sizes, n_tensors, inertia, stream);
 }
 
 int flc_avg_and_gradient_sparse_records(float* const* params, float* const* grads, const float* const* param_srcs,
                                         const void* const* grad_records, const float* w_params, const float* w_grads,
                                         int n_src, int64_t n, int64_t k, const int64_t* sizes, int n_tensors,
                                         float inertia, void* stream) {
-  return avg_and_gradient_impl("flc_avg_and_gradient_sparse_records", "avg_and_gradient_sparse_records", nullptr,
-                               kRecSparse, params, grads, param_srcs, grad_records, w_params, w_grads, n_src, n, k, 0,
-                               sizes, n_tensors, inertia, stream);
+  return avg_and_gradient_impl("flc_avg_and_gradient_sparse_records", "avg_and_gradient_sparse_records",
+                               RoundCodec::entry(kRecSparse, n, k, 0), params, grads, param_srcs, grad_records,
+                               w_params, w_grads, n_src, sizes, n_tensors, inertia, stream);
 }
 
 int flc_avg_and_gradient_dense_records(float* const* params, float* const* grads, const float* const* param_srcs,
                                        const void* const* grad_records, const float* w_params, const float* w_grads,
                                        int n_src, int64_t n, int format, int levels, int bits, const int64_t* sizes,
                                        int n_tensors, float inertia, void* stream) {
-  const DenseCodec cd{format, levels, bits, n};
-  return avg_and_gradient_impl("flc_avg_and_gradient_dense_records", "avg_and_gradient_dense_records", &cd, kRecStacked,
-                               params, grads, param_srcs, grad_records, w_params, w_grads, n_src, n, 0, levels, sizes,
-                               n_tensors, inertia, stream);
+  return avg_and_gradient_impl("flc_avg_and_gradient_dense_records", "avg_and_gradient_dense_records",
+                               RoundCodec::dense_records(n, format, levels, bits), params, grads, param_srcs,
+                               grad_records, w_params, w_grads, n_src, sizes, n_tensors, inertia, stream);
 }
 
-// flc_fold_record_groups (dense == NULL, kRecStacked), flc_fold_sparse_record_groups (dense == NULL, kRecSparse) and
-// flc_fold_dense_record_groups (the records of *dense), as fedopt_fold_impl serves the FedOpt folds
-static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec* dense, RecordKind kind,
-                            const void* const* records,
-                            const float* weights, const int32_t* group_of, int n_records, int64_t n, int64_t k,
-                            int levels, float* const* dsts, int n_groups, const int64_t* sizes, int n_tensors,
-                            void* stream, const MixedRound* mx = nullptr) {
+// The grouped folds (flc_fold_record_groups, _sparse_record_groups, _dense_record_groups, _mixed_record_groups), as
+// fedopt_fold_impl serves the FedOpt folds
+static int fold_groups_impl(const char* fn, const char* probe, const RoundCodec& codec, const void* const* records,
+                            const float* weights, const int32_t* group_of, int n_records, float* const* dsts,
+                            int n_groups, const int64_t* sizes, int n_tensors, void* stream) {
+  const int64_t n = codec.n, k = codec.k;
   if (n_records < 0 || (n_records > 0 && (!records || !weights || !group_of)) || n <= 0 || k < 0 || n_groups < 1 ||
       n_tensors < 1 || !dsts || !sizes)
     return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (n >= (1ll << 31) || k >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n and k must be < 2^31", fn);
-  if (mx) {
-  } else if (dense) {
-    if (int rc = check_dense_format(fn, dense->format, dense->levels, dense->bits)) return rc;
-  } else if (int rc = check_entry_codec(fn, kind, n, k, levels)) {
-    return rc;
-  }
+  if (int rc = codec.check(fn)) return rc;
   int64_t total = 0;
   for (int t = 0; t < n_tensors; ++t) {
     if (sizes[t] < 0) return fail(FLC_EINVAL, "%s: negative size for tensor %d", fn, t);
@@ -1665,10 +1684,7 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
       return fail(FLC_EINVAL, "%s: groups %d and %d share a destination", fn, owners[i - 1].second,
                   owners[i].second);
   if (n_records == 0) return FLC_OK;
-  size_t need = 0;
-  const WireLayout L = record_layout(kind, n, k, &need);
   hipStream_t st = as_stream(stream);
-  const double step = 1.0 / (double)(levels < 1 ? 1 : levels);
   // the records ordered by group, each group's in message order
   std::vector<int> order(n_records);
   for (int c = 0; c < n_records; ++c) order[c] = c;
@@ -1691,7 +1707,7 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
       const int c = order[c0 + nw], g = group_of[c];
       const bool opens = ng == 0 || gsel[ng - 1] != g;
       if (opens && ng == kMaxGroups) break;
-      if (mx && !mixed_take(*mx, c, &md, nw)) break;  // (the launch's level tables are full: the next launch)
+      if (!codec.take(c, &md, nw)) break;  // (a mixed launch's level tables are full: the next launch)
       if (opens) {
         gsel[ng] = g;
         m.first[ng] = nw;
@@ -1727,14 +1743,7 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
       m.start[m.nt] = off;
       const int64_t tile_lo = m.start[0] / FLC_TILE, tile_hi = cdiv(off, (int64_t)FLC_TILE);
       const dim3 grid((unsigned)(tile_hi - tile_lo), (unsigned)ng);
-      if (mx) {
-        if (int rc = launch_mixed_fold(probe, grid, st, a, md, nw, n, tile_lo, io)) return rc;
-      } else if (dense) {
-        if (int rc = launch_dense_fold(probe, *dense, grid, st, a, nw, tile_lo, io)) return rc;
-      } else if (int rc = launch_entry_fold(probe, kind, sparse, grid, st, a, L, nw, levels, step, tile_lo, io,
-                                            (unsigned)k)) {
-        return rc;
-      }
+      if (int rc = codec.launch(probe, sparse, grid, st, a, md, nw, tile_lo, io)) return rc;
     }
     c0 += nw;
   }
@@ -1744,25 +1753,27 @@ static int fold_groups_impl(const char* fn, const char* probe, const DenseCodec*
 int flc_fold_record_groups(const void* const* records, const float* weights, const int32_t* group_of, int n_records,
                            int64_t n, int64_t k, int levels, float* const* dsts, int n_groups, const int64_t* sizes,
                            int n_tensors, void* stream) {
-  return fold_groups_impl("flc_fold_record_groups", "fold_record_groups", nullptr, kRecStacked, records, weights,
-                          group_of, n_records, n, k, levels, dsts, n_groups, sizes, n_tensors, stream);
+  return fold_groups_impl("flc_fold_record_groups", "fold_record_groups", RoundCodec::entry(kRecStacked, n, k, levels),
+                          records, weights, group_of, n_records, dsts, n_groups, sizes, n_tensors, stream);
 }
 
 int flc_fold_sparse_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
                                   int n_records, int64_t n, int64_t k, float* const* dsts, int n_groups,
                                   const int64_t* sizes, int n_tensors, void* stream) {
-  return fold_groups_impl("flc_fold_sparse_record_groups", "fold_sparse_record_groups", nullptr, kRecSparse, records,
-                          weights, group_of, n_records, n, k, 0, dsts, n_groups, sizes, n_tensors, stream);
+  return fold_groups_impl("flc_fold_sparse_record_groups", "fold_sparse_record_groups",
+                          RoundCodec::entry(kRecSparse, n, k, 0), records, weights, group_of, n_records, dsts, n_groups,
+                          sizes, n_tensors, stream);
 }
 
 int flc_fold_dense_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
                                  int n_records, int64_t n, int format, int levels, int bits, float* const* dsts,
                                  int n_groups, const int64_t* sizes, int n_tensors, void* stream) {
-  const DenseCodec cd{format, levels, bits, n};
-  return fold_groups_impl("flc_fold_dense_record_groups", "fold_dense_record_groups", &cd, kRecStacked, records, weights,
-                          group_of, n_records, n, 0, levels, dsts, n_groups, sizes, n_tensors, stream);
+  return fold_groups_impl("flc_fold_dense_record_groups", "fold_dense_record_groups",
+                          RoundCodec::dense_records(n, format, levels, bits), records, weights, group_of, n_records,
+                          dsts, n_groups, sizes, n_tensors, stream);
 }
 
+// The mixed entry points: the descriptor tables' own check first (check_mixed_round), then the uniform folds' impl
 int flc_fedopt_fold_mixed_records(const void* const* records, const float* weights, int n_records, int64_t n,
                                   const int32_t* kinds, const int64_t* ks, const int32_t* formats,
                                   const int32_t* levels, const int32_t* bits, float* const* delta, float* const* theta,
@@ -1772,8 +1783,8 @@ int flc_fedopt_fold_mixed_records(const void* const* records, const float* weigh
   const MixedRound mx{kinds, ks, formats, levels, bits};
   if (n_records < 0) return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (int rc = check_mixed_round(fn, records, mx, n_records, n)) return rc;
-  return fedopt_fold_impl(fn, "fedopt_fold_mixed_records", nullptr, kRecStacked, records, weights, n_records, n, 1, 1,
-                          delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau, stream, &mx);
+  return fedopt_fold_impl(fn, "fedopt_fold_mixed_records", RoundCodec::mixed(n, &mx), records, weights, n_records,
+                          delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau, stream);
 }
 
 int flc_fold_mixed_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
@@ -1784,8 +1795,8 @@ int flc_fold_mixed_record_groups(const void* const* records, const float* weight
   const MixedRound mx{kinds, ks, formats, levels, bits};
   if (n_records < 0) return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (int rc = check_mixed_round(fn, records, mx, n_records, n)) return rc;
-  return fold_groups_impl(fn, "fold_mixed_record_groups", nullptr, kRecStacked, records, weights, group_of, n_records,
-                          n, 1, 1, dsts, n_groups, sizes, n_tensors, stream, &mx);
+  return fold_groups_impl(fn, "fold_mixed_record_groups", RoundCodec::mixed(n, &mx), records, weights, group_of,
+                          n_records, dsts, n_groups, sizes, n_tensors, stream);
 }
 
 int flc_avg_and_gradient_mixed_records(float* const* params, float* const* grads, const float* const* param_srcs,
@@ -1797,8 +1808,8 @@ int flc_avg_and_gradient_mixed_records(float* const* params, float* const* grads
   const MixedRound mx{kinds, ks, formats, levels, bits};
   if (n_src < 1 || !grad_records) return fail(FLC_EINVAL, "%s: bad arguments", fn);
   if (int rc = check_mixed_round(fn, grad_records, mx, n_src, n)) return rc;
-  return avg_and_gradient_impl(fn, "avg_and_gradient_mixed_records", nullptr, kRecStacked, params, grads, param_srcs,
-                               grad_records, w_params, w_grads, n_src, n, 1, 1, sizes, n_tensors, inertia, stream, &mx);
+  return avg_and_gradient_impl(fn, "avg_and_gradient_mixed_records", RoundCodec::mixed(n, &mx), params, grads,
+                               param_srcs, grad_records, w_params, w_grads, n_src, sizes, n_tensors, inertia, stream);
 }
 
 size_t flc_dense_wire_layout(int64_t n, int format, int bits, int64_t* offsets) {
@@ -1816,31 +1827,8 @@ size_t flc_dense_wire_layout(int64_t n, int format, int bits, int64_t* offsets) 
 
 int flc_fold_dense_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
                          int64_t n, int format, int levels, int bits, int accumulate, float* out, void* stream) {
-  const char* fn = "flc_fold_dense_wires";
-  if (!wires || !slots || !weights || !out || n_wires < 1 || n <= 0) return fail(FLC_EINVAL, "%s: bad arguments", fn);
-  if (n >= (1ll << 31)) return fail(FLC_EINVAL, "%s: n must be < 2^31", fn);
-  if (int rc = check_dense_format(fn, format, levels, bits)) return rc;
-  const size_t need = dense_wire_size(n, format, bits);
-  if (stride < (int64_t)need || stride % 16 != 0)
-    return fail(FLC_EINVAL, "%s: stride %lld < record size %zu (or not 16-B aligned)", fn, (long long)stride, need);
-  if (!aligned16(wires) || !aligned16(out)) return fail(FLC_EINVAL, "%s: 16-B aligned buffers required", fn);
-  for (int c = 0; c < n_wires; ++c)
-    if (slots[c] < 0) return fail(FLC_EINVAL, "%s: slot %d is negative", fn, c);
-  hipStream_t st = as_stream(stream);
-  const DenseCodec cd{format, levels, bits, n};
-  const int64_t ntiles = cdiv(n, (int64_t)FLC_TILE);
-  for (int c0 = 0; c0 < n_wires; c0 += kMaxWires) {  // (a chained launch continues from the stored out)
-    const int nw = std::min(kMaxWires, n_wires - c0);
-    FoldArgs a;
-    for (int c = 0; c < kMaxWires; ++c) {
-      a.w[c] = c < nw ? weights[c0 + c] : 0.0f;
-      a.rec[c] = static_cast<const uint8_t*>(wires) + (c < nw ? (int64_t)slots[c0 + c] * stride : 0);
-    }
-    const FlatIO io{out, n, (c0 > 0 || accumulate) ? 1 : 0};
-    if (int rc = launch_dense_fold("fold_dense_wires", cd, dim3((unsigned)ntiles), st, a, nw, (int64_t)0, io))
-      return rc;
-  }
-  return FLC_OK;
+  return fold_wires_impl("flc_fold_dense_wires", "fold_dense_wires", RoundCodec::dense_records(n, format, levels, bits),
+                         wires, stride, slots, weights, n_wires, accumulate, out, stream);
 }
 
 }  // extern "C"
