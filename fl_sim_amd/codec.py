@@ -274,8 +274,6 @@ def quant_encode_round(xs: Sequence[torch.Tensor], kind: int, levels: int, bits:
     or a sequence of C records; ``norm_p``: FLC_NORM_INF or FLC_NORM_L2; ``counts``: None, or one one-element device
     int64 tensor per message (a contiguous ``[C]`` tensor also) that receives the message's count of nonzero
     elements."""
-    import ctypes
-
     C = len(xs)
     if C == 0:
         return
@@ -286,6 +284,38 @@ def quant_encode_round(xs: Sequence[torch.Tensor], kind: int, levels: int, bits:
         if any(x.numel() != n or x.device != dev for x in xs):
             raise ValueError("a round encode takes messages of one size on one device")
         xp = [x.data_ptr() for x in xs]
+    _quant_round_call("flc_quant_encode_round", xp, n, dev, kind, levels, bits, norm_p, seeds, counters, records,
+                      counts)
+
+
+def quant_encode_residual_round(mems: Sequence[torch.Tensor], kind: int, levels: int, bits: int, norm_p: int,
+                                seeds: Sequence[int], counters: Sequence[int], records, counts=None) -> None:
+    """:func:`quant_encode_round` with error feedback in the encode's own pass (flc_quant_encode_residual_round):
+    message c's input is the error memory ``mems[c]``, holding ``a``; the records, norms and counts are those of
+    ``quant_encode_round(mems, ...)`` bit for bit, and each memory is left holding ``a − decode(records[c])`` — what
+    ``dense_record_decode`` into a fresh vector and :func:`ef_residual_dense` leave — with no decode, no temporary and
+    no further launch.  The memories are written in place, so nothing is copied for them: each must be a contiguous,
+    16-B aligned float32 tensor of one size on one HIP device, and no two may share elements."""
+    C = len(mems)
+    if C == 0:
+        return
+    if not isinstance(mems[0], torch.Tensor) or mems[0].device.type != "cuda":
+        raise TypeError("the memories must be float32 tensors on a HIP device")
+    n, dev = mems[0].numel(), mems[0].device
+    ep = _batch_ptrs(mems, n, dev)
+    if ep is None:
+        raise ValueError("the memories must be contiguous, 16-B aligned float32 tensors of one size on one device")
+    _quant_round_call("flc_quant_encode_residual_round", ep, n, dev, kind, levels, bits, norm_p, seeds, counters,
+                      records, counts)
+
+
+def _quant_round_call(entry: str, xp: List[int], n: int, dev, kind: int, levels: int, bits: int, norm_p: int, seeds,
+                      counters, records, counts) -> None:
+    """The record views, tables and workspace of a round's quantizer encode, then the call (``entry``: the plain or
+    the residual form; ``xp``: the messages' input pointers)."""
+    import ctypes
+
+    C = len(xp)
     if len(seeds) != C or len(counters) != C:
         raise ValueError("one seed and one counter per message")
     if isinstance(records, torch.Tensor) and records.dim() == 2:  # one record block: the rows' views by arithmetic
@@ -306,7 +336,7 @@ def quant_encode_round(xs: Sequence[torch.Tensor], kind: int, levels: int, bits:
     P = ctypes.c_void_p * C
     vp = lambda a: None if a is None else ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
     ws = workspace(dev, _ws_size(dev, "flc_quant_encode_round_workspace_size", n, C), "quant_round")
-    call("flc_quant_encode_round", vp(P(*xp)), C, n, kind, levels, bits, norm_p,
+    call(entry, vp(P(*xp)), C, n, kind, levels, bits, norm_p,
          vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), vp(ctr), vp(P(*cps)), vp(P(*nps)), vp(cnt), _p(ws),
          ws.numel(), _stream(dev))
 

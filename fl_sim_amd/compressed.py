@@ -24,8 +24,8 @@ What runs here instead:
   message then carries the quantizer's own wire as a dense record (``flc_dense_wire_layout``: the fp32 norm and the
   packed 2-, 4- or 8-bit codes, or one uint16 per element), written by the compressor's encoder straight into the
   record with nothing decoded, the RNG streams and send statistics advancing as ``compressVector`` advances them.
-  In philox mode a dithering quantizer's records of up to 2^20 elements (device norm, p = ∞ or 2, no error feedback)
-  are deferred like the stacked ones: the round's messages are encoded by one ``flc_quant_encode_round`` when a record
+  In philox mode a dithering quantizer's records of up to 2^20 elements (device norm, p = ∞ or 2; with error feedback
+  only under ``FLC_EF_DENSE_DEFER=1``, :data:`EF_DENSE_DEFER`) are deferred like the stacked ones: the round's messages are encoded by one ``flc_quant_encode_round`` when a record
   or a statistic is first read (:func:`deferred_dense_stats` counts these batches).
   With ``sparse_records`` on (a switch of its own, looked up the same way; ``sparse=True`` on the three compress
   functions; off by default) a compressor list that is one float32 top-k or rand-k compressor with 0 < K < n whose
@@ -94,7 +94,9 @@ batch item's flat input (no snapshot), and after the batch's ``flc_stacked_encod
 stays pending with its memories holding ``a``; a memory still waiting in a batch when its client communicates again
 has that batch run first).  The immediate stacked paths encode the memory and run the residual with one client; any
 other compressor chain runs on the memory's values, then ``flc_ef_residual_dense`` (with ``wire`` on, on the decoded
-dense record, which the message does not keep).  A sparse record's residual is K entries too
+dense record, which the message does not keep — or, with ``FLC_EF_DENSE_DEFER=1`` (:data:`EF_DENSE_DEFER`, off by
+default), a dithering quantizer's dense-record message waits in the round's batch with the memory as its flat input and
+one ``flc_quant_encode_residual_round`` writes the records and the residuals in the encode's own pass).  A sparse record's residual is K entries too
 (``flc_ef_residual_sparse_round``: once per deferred batch after its encode succeeded, with one client on the immediate
 paths).  ``feedback=None`` is the path above, untouched.
 """
@@ -573,7 +575,13 @@ def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torc
         return d
     dc = dense_wire_codec(compressors) if wire else None
     if dc is not None:  # the message carries the record; the memory takes a − decode(record) (these quantizers are
-        d = _dense_record(e, shapes, n, compressors[0], dc, dev)  # unbiased: the plain dense residual)
+        # unbiased: the plain dense residual) — from the round's batched encode itself with EF_DENSE_DEFER on
+        if (EF_DENSE_DEFER and DEFER_ENCODE and n <= _DEFER_EF_DENSE_MAX_N and dc[0] != FLC_WIRE_NATURAL
+                and _all_f32(local, cached)):  # (the messages _compress defers, no others)
+            r = _defer_dense(e, shapes, n, compressors[0], dc, dev, mem)
+            if r is not None:
+                return r
+        d = _dense_record(e, shapes, n, compressors[0], dc, dev)
         codec.ef_residual_dense(e, codec.dense_record_decode(d._record, n, dc[0], dc[1], dc[2]))
         return d
     K = sparse_wire_codec(compressors, n) if sparse and _all_f32(local, cached) else None
@@ -728,21 +736,40 @@ class _Batch:
 # form, which reads the vector once, beats two streaming launches — so larger messages keep the immediate path.
 _DEFER_DENSE_MAX_N = 1 << 20
 
+# With error feedback such a message is encoded at once — flc_ef_accumulate, flc_quant_encode_auto, a dense decode into
+# a fresh vector and flc_ef_residual_dense — unless FLC_EF_DENSE_DEFER=1 (EF_DENSE_DEFER, off by default): then it
+# waits like the others with the error memory's tensor as the encoder's input, in a batch of its own kind (the key's
+# last element), and one flc_quant_encode_residual_round writes the round's records and leaves every memory holding
+# a − decode(record) from the encode's own pass: nothing decoded, no temporary, no further launch.  Records, memories,
+# statistics and counters are bit-identical to the immediate path's.  The size bound is this kind's own: the immediate
+# chain makes three more dense passes per message than without feedback, so the batched form wins further up —
+# measured (profiles/ef_dense_round.json, encodes only), ten messages take 72 us against 316 us at 417,482 elements,
+# 104 against 316 us at 1 M and 163 against 319 us at 2 M; eight messages of 4 M take 253 against 289 us, the ranges
+# apart in one run and touching in another, and of 8 M 482 against 467 us.  The bound is the largest size at which the
+# ranges stayed apart in every run.
+EF_DENSE_DEFER = os.environ.get("FLC_EF_DENSE_DEFER", "0") == "1"
+_DEFER_EF_DENSE_MAX_N = 2_000_000
+
 
 class _DenseBatch(_Batch):
-    """The waiting dense-record messages of one (device, "quant", n, format, levels, bits, norm_p); an item's count
-    slot and compressor are None for natural dithering, whose send count does not depend on the data."""
+    """The waiting dense-record messages of one (device, "quant", n, format, levels, bits, norm_p, feedback); an
+    item's count slot and compressor are None for natural dithering, whose send count does not depend on the data.
+    In a feedback batch every item's ``flat`` is its error memory's tensor."""
 
     stats = _DENSE_STATS
 
     def _encode_rows(self, items, dev):
-        _, _, n, fmt, levels, bits, pk = self.key
+        _, _, n, fmt, levels, bits, pk, fed = self.key
         stride, _ = codec.dense_wire_layout(n, fmt, bits)
         recs = torch.empty(len(items), stride, dtype=torch.uint8, device=dev)
-        codec.quant_encode_round([it.flat for it in items], fmt, levels, bits, pk, [it.seed for it in items],
-                                 [it.counter for it in items], recs,
-                                 [it.count for it in items] if fmt == FLC_Q_STANDARD_DITHER else None)
-        return recs.unbind(0)
+        rows = recs.unbind(0)
+        # error feedback: the encode's own pass leaves e = a − decode(record) in the memories.  The call is the last
+        # thing here that can raise: a batch that failed has written no memory, and the retry encodes the same a
+        encode = codec.quant_encode_residual_round if fed else codec.quant_encode_round
+        encode([it.flat for it in items], fmt, levels, bits, pk, [it.seed for it in items],
+               [it.counter for it in items], recs,
+               [it.count for it in items] if fmt == FLC_Q_STANDARD_DITHER else None)
+        return rows
 
 
 # Deferred sparse records (`sparse` on, one top-k compressor, any rng_mode: top-k draws no random numbers).  The
@@ -834,29 +861,32 @@ def _defer(flat: torch.Tensor, shapes, n: int, K: int, s: int, tk: Compressor, s
 
 
 def _defer_dense(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[int, int, int],
-                 dev) -> Optional[CompressedDelta]:
-    """The dense-record message of the flat vector ``x`` (a snapshot) joins the round's batched quantizer encode; the
-    Philox stream and the send statistics advance here exactly as :func:`_dense_record` advances them.  None (nothing
-    advanced: the immediate path takes the message) outside philox mode with the device norm of p = inf or 2 on a
-    float32 vector."""
+                 dev, mem: Optional[ErrorMemory] = None) -> Optional[CompressedDelta]:
+    """The dense-record message of the flat vector ``x`` (a snapshot, or — ``mem`` — that error memory's tensor, which
+    the batched encode leaves holding the residual) joins the round's batched quantizer encode; the Philox stream and
+    the send statistics advance here exactly as :func:`_dense_record` advances them.  None (nothing advanced: the
+    immediate path takes the message) outside philox mode with the device norm of p = inf or 2 on a float32 vector."""
     fmt, s, bits = dc
     if comp.rng_mode != "philox" or comp._wants_host_norm(device_input=True):
         return None
     pk = _norm_kind(comp.p)
     if pk is None or x.dtype != torch.float32 or x.device != dev:
         return None
-    x = codec._dev_f32(x).reshape(-1)
+    if mem is None:
+        x = codec._dev_f32(x).reshape(-1)
+    elif x.dim() != 1 or not x.is_contiguous() or x.data_ptr() % 16:  # (written in place: never a copy)
+        return None
     std = fmt == FLC_Q_STANDARD_DITHER
     st = torch.cuda.current_stream(dev)
     cnt = comp._count_slot(dev, st) if std else None  # (before the batch is looked up and the _finish calls, as in _defer)
-    b = _waiting(_DenseBatch, (dev.index, "quant", n, fmt, s, bits, pk))
+    b = _waiting(_DenseBatch, (dev.index, "quant", n, fmt, s, bits, pk, mem is not None))
     seed, ctr = comp.philox.next()
     d = CompressedDelta(shapes, dev, n, levels=s, batch=b, format=fmt, bits=bits)
     if std:
         comp._finish_pending(n, cnt, _norm_stage_send(comp, None), _code_fraction(s))
     else:
         comp._finish(n, n * _code_fraction(s))
-    return _enqueue(b, _Item(d, x, seed, ctr, cnt, comp if std else None, st, st.cuda_stream, None))
+    return _enqueue(b, _Item(d, x, seed, ctr, cnt, comp if std else None, st, st.cuda_stream, mem))
 
 
 def _defer_sparse(flat: torch.Tensor, shapes, n: int, K: int, tk: Compressor, dev,

@@ -14,6 +14,8 @@
 //                  algorithmic bytes: 4 read + BITS/8 written per element.
 //   quant_round_*  a round's messages (each its own vector, Philox (seed, counter), record and count slot) in two
 //                  launches: norm partials over (part, message), encode over (block, message); flc_quant_encode_round.
+//                  flc_quant_encode_residual_round: the vectors are error memories, and the encode launch stores
+//                  a - decode(code) back in place (4 more bytes written per element, nothing decoded afterwards).
 //   quant_decode   v = fp32(fp32(lv) * sign) * norm, optionally fmaf-accumulated with a row weight.
 //                  algorithmic bytes: BITS/8 read + 4 written (+4 read when accumulating).
 // Each thread owns GROUP = 8 consecutive elements (two 16-B loads, one 2..8-B code store): a wave
@@ -23,7 +25,9 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdint>
 #include <cstdlib>
+#include <vector>
 
 #include "flc_device.hpp"
 #include "flc_runtime.hpp"
@@ -393,7 +397,8 @@ __global__ __launch_bounds__(kThreads) void quant_encode_kernel(
 // One group of 8 elements (flat index e0, `valid` of them real) in Philox mode: the common case — a full group inside
 // one row — takes one norm lookup and, for standard dithering, a branch-light fp32 level decision; groups straddling a
 // row boundary or the end take the per-element path.  norm_of(r): row r's norm; nnz_add(r, count) when counting.
-// DEC also writes the decoded values (flc_quant_encode_decode).
+// MODE kEncDecode also writes the decoded values to `out` (flc_quant_encode_decode); kEncResidual writes input minus
+// decoded value there instead — `out` is then the vector the group was loaded from (flc_quant_encode_residual_round).
 // the group's 8 Philox words (element e: word e & 3 of counter group e >> 2)
 __device__ __forceinline__ void group_words(int64_t e0, uint64_t seed, uint64_t counter, uint32_t (&wd)[kGroup]) {
   const U4 a = philox_group((uint64_t)e0 >> 2, seed, counter);
@@ -402,12 +407,25 @@ __device__ __forceinline__ void group_words(int64_t e0, uint64_t seed, uint64_t 
   wd[4] = b.x; wd[5] = b.y; wd[6] = b.z; wd[7] = b.w;
 }
 
-template <int KIND, int BITS, bool DEC, class NormOf, class NnzAdd>
+// a - v as the hardware subtracts them, whatever the compiler knows of v: where v is a constant (the NaN of a norm
+// that is not regular) a folded a - NaN is the canonical NaN, not the bits the subtraction gives — and the residual
+// is defined as flc_ef_residual_dense's subtraction of the decoded vector, which sees only values
+__device__ __forceinline__ float residual_of(float a, float v) {
+  asm volatile("" : "+v"(v));  // (no instruction: v becomes a register value the optimiser cannot look through)
+  return a - v;
+}
+
+constexpr int kEncOnly = 0, kEncDecode = 1, kEncResidual = 2;
+static_assert(kEncOnly == (int)false && kEncDecode == (int)true, "a caller's bool DEC converts to the first two");
+
+template <int KIND, int BITS, int MODE, class NormOf, class NnzAdd>
 __device__ __forceinline__ void philox_group_encode(const float (&v)[kGroup], const uint32_t (&wd)[kGroup], int64_t e0,
                                                     int valid, int64_t d, int s, double step,
                                                     uint8_t* __restrict__ codes, float* __restrict__ out, bool count,
                                                     NormOf norm_of, NnzAdd nnz_add, bool nt = false,
                                                     const float* lvt = nullptr) {
+  constexpr bool DEC = MODE != kEncOnly;
+  constexpr bool RES = MODE == kEncResidual;
   const int64_t r0 = e0 / d;
   const int64_t r_end = (r0 + 1) * d;
   uint64_t packed = 0;
@@ -449,6 +467,7 @@ __device__ __forceinline__ void philox_group_encode(const float (&v)[kGroup], co
         } else {
           o[j] = dequant<KIND, BITS>(c, nr0, s, step);
         }
+        if (RES) o[j] = residual_of(v[j], o[j]);  // (every element: a zero code's a - 0 keeps a, -0 included)
       }
     }
   } else if (whole) {
@@ -457,6 +476,7 @@ __device__ __forceinline__ void philox_group_encode(const float (&v)[kGroup], co
       const uint32_t c = quant_code<KIND, BITS>(v[j], nr0, s, step, u01(wd[j]));
       packed |= (uint64_t)c << (j * BITS);
       if (DEC) o[j] = dequant<KIND, BITS>(c, nr0, s, step);
+      if (RES) o[j] = residual_of(v[j], o[j]);
     }
   } else {
     for (int j = 0; j < valid; ++j) {
@@ -465,6 +485,7 @@ __device__ __forceinline__ void philox_group_encode(const float (&v)[kGroup], co
       const uint32_t c = quant_code<KIND, BITS>(v[j], nr, s, step, u01(wd[j]));
       packed |= (uint64_t)c << (j * BITS);
       if (DEC) o[j] = dequant<KIND, BITS>(c, nr, s, step);
+      if (RES) o[j] = residual_of(v[j], o[j]);
       if (count && v[j] != 0.0f) nnz_add(r, 1);
     }
   }
@@ -585,7 +606,10 @@ __global__ __launch_bounds__(kThreads) void quant_round_norm_kernel(RoundTable t
 }
 
 // grid (blocks of kThreads groups, messages)
-template <int KIND, int BITS, int NORM>
+// MODE kEncResidual (flc_quant_encode_residual_round): message c's vector is its error memory holding a, and the thread
+// that loaded a group stores a - decode(code) back to the positions it loaded from (two plain 16-B stores, scalar
+// stores in the tail; cached: the next round's accumulate reads them).  The norm launch before this one has read a.
+template <int KIND, int BITS, int NORM, int MODE = kEncOnly>
 __global__ __launch_bounds__(kThreads) void quant_round_encode_kernel(RoundTable tab, int64_t n, int s, double step,
                                                                       QuantWs ws, int parts, int msg0) {
   __shared__ unsigned long long s_nnz;
@@ -608,8 +632,9 @@ __global__ __launch_bounds__(kThreads) void quant_round_encode_kernel(RoundTable
     load_group(m.x, e0, valid, v);
     uint32_t wd[kGroup];
     group_words(e0, m.seed, m.counter, wd);
-    philox_group_encode<KIND, BITS, false>(
-        v, wd, e0, valid, n, s, step, m.codes, nullptr, count, [&](int64_t) { return s_norm; },
+    philox_group_encode<KIND, BITS, MODE>(
+        v, wd, e0, valid, n, s, step, m.codes, MODE == kEncResidual ? const_cast<float*>(m.x) : nullptr, count,
+        [&](int64_t) { return s_norm; },
         [&](int64_t, int cnt) { atomicAdd(&s_nnz, (unsigned long long)cnt); });
   }
   if (count) {  // (uniform: the message's)
@@ -1020,12 +1045,13 @@ int launch_auto(const float* x, int64_t rows, int64_t d, int levels, int norm_p,
 }
 
 // the round's two launches per table of up to kRoundMsgs messages, chained on the stream
-template <int KIND, int BITS>
+template <int KIND, int BITS, int MODE = kEncOnly>
 int launch_round(const float* const* xs, int n_msgs, int64_t n, int levels, int norm_p, const uint64_t* seeds,
                  const uint64_t* counters, uint8_t* const* codes, float* const* norms, int64_t* const* counts,
                  const QuantWs& w, int64_t parts, int64_t chunk, hipStream_t st) {
   const double step = level_step(levels);
   const unsigned nb1 = (unsigned)cdiv(n, (int64_t)kGroup * kThreads);
+  const char* name = MODE == kEncResidual ? "quant_round_encode_residual" : "quant_round_encode";
   for (int c0 = 0; c0 < n_msgs; c0 += kRoundMsgs) {
     const int m = std::min(n_msgs - c0, kRoundMsgs);
     RoundTable tab{};
@@ -1036,12 +1062,12 @@ int launch_round(const float* const* xs, int n_msgs, int64_t n, int levels, int 
     if (norm_p == FLC_NORM_INF) {
       FLC_LAUNCH("quant_round_norm", quant_round_norm_kernel<FLC_NORM_INF>, dim3((unsigned)parts, (unsigned)m),
                  dim3(kThreads), 0, st, tab, n, chunk, w, c0);
-      FLC_LAUNCH("quant_round_encode", (quant_round_encode_kernel<KIND, BITS, FLC_NORM_INF>), dim3(nb1, (unsigned)m),
+      FLC_LAUNCH(name, (quant_round_encode_kernel<KIND, BITS, FLC_NORM_INF, MODE>), dim3(nb1, (unsigned)m),
                  dim3(kThreads), 0, st, tab, n, levels, step, w, (int)parts, c0);
     } else {
       FLC_LAUNCH("quant_round_norm", quant_round_norm_kernel<FLC_NORM_L2>, dim3((unsigned)parts, (unsigned)m),
                  dim3(kThreads), 0, st, tab, n, chunk, w, c0);
-      FLC_LAUNCH("quant_round_encode", (quant_round_encode_kernel<KIND, BITS, FLC_NORM_L2>), dim3(nb1, (unsigned)m),
+      FLC_LAUNCH(name, (quant_round_encode_kernel<KIND, BITS, FLC_NORM_L2, MODE>), dim3(nb1, (unsigned)m),
                  dim3(kThreads), 0, st, tab, n, levels, step, w, (int)parts, c0);
     }
   }
@@ -1115,6 +1141,54 @@ int flc_quant_encode_round(const float* const* xs, int n_msgs, int64_t n, int ki
   hipStream_t st = as_stream(stream);
 #define FLC_ROUND(K, B) \
   return launch_round<K, B>(xs, n_msgs, n, levels, norm_p, seeds, counters, codes, norms, counts, w, parts, chunk, st)
+  if (kind == FLC_Q_STANDARD_DITHER) {
+    if (bits == 8) FLC_ROUND(0, 8);
+    if (bits == 4) FLC_ROUND(0, 4);
+    FLC_ROUND(0, 2);
+  } else {
+    if (bits == 8) FLC_ROUND(1, 8);
+    if (bits == 4) FLC_ROUND(1, 4);
+    FLC_ROUND(1, 2);
+  }
+#undef FLC_ROUND
+}
+
+int flc_quant_encode_residual_round(float* const* es, int n_msgs, int64_t n, int kind, int levels, int bits,
+                                    int norm_p, const uint64_t* seeds, const uint64_t* counters,
+                                    uint8_t* const* codes, float* const* norms, int64_t* const* counts, void* ws,
+                                    size_t ws_bytes, void* stream) {
+  const char* fn = "flc_quant_encode_residual_round";
+  if (!es || !seeds || !counters || !codes || !norms) return fail(FLC_EINVAL, "%s: null table", fn);
+  if (n_msgs < 1) return fail(FLC_EINVAL, "%s: n_msgs %d < 1", fn, n_msgs);
+  if (n < 1 || n >= (int64_t)1 << 31) return fail(FLC_EINVAL, "%s: n must be in [1, 2^31)", fn);
+  if (norm_p != FLC_NORM_INF && norm_p != FLC_NORM_L2) return fail(FLC_EINVAL, "%s: p must be inf(0) or 2", fn);
+  if (int rc = check_quant_args(kind, levels, bits)) return rc;
+  for (int c = 0; c < n_msgs; ++c) {
+    if (!es[c] || !codes[c] || !norms[c] || (counts && !counts[c]))
+      return fail(FLC_EINVAL, "%s: null entry for message %d", fn, c);
+    if (!aligned16(es[c]) || !aligned16(codes[c]))
+      return fail(FLC_EINVAL, "%s: es[%d] and codes[%d] must be 16-B aligned", fn, c, c);
+  }
+  {  // every message writes its own memory: no two may share elements
+    std::vector<uintptr_t> at(n_msgs);
+    for (int c = 0; c < n_msgs; ++c) at[c] = reinterpret_cast<uintptr_t>(es[c]);
+    std::sort(at.begin(), at.end());
+    for (int c = 1; c < n_msgs; ++c)
+      if (at[c] - at[c - 1] < (uintptr_t)n * sizeof(float))
+        return fail(FLC_EINVAL, "%s: two messages share the memory at %p", fn, reinterpret_cast<void*>(at[c]));
+  }
+  const size_t need = flc_quant_encode_round_workspace_size(n, n_msgs);
+  if (need > ws_bytes || !ws) return fail(FLC_EWORKSPACE, "%s: workspace %zu < %zu", fn, ws_bytes, need);
+  QuantWs w{};
+  w.partials = Carver(ws, ws_bytes).take<unsigned long long>((size_t)n_msgs * kNormMaxParts);
+  // flc_quant_encode_round's partition
+  int64_t parts = std::min<int64_t>(cdiv(n, kNormChunk), kNormMaxParts);
+  const int64_t chunk = align_up((size_t)cdiv(n, parts), 4);
+  parts = cdiv(n, chunk);
+  hipStream_t st = as_stream(stream);
+#define FLC_ROUND(K, B)                                                                                             \
+  return launch_round<K, B, kEncResidual>(es, n_msgs, n, levels, norm_p, seeds, counters, codes, norms, counts, w, \
+                                          parts, chunk, st)
   if (kind == FLC_Q_STANDARD_DITHER) {
     if (bits == 8) FLC_ROUND(0, 8);
     if (bits == 4) FLC_ROUND(0, 4);

@@ -14,6 +14,9 @@ record, or the decoded flat vector), with the same statistics and RNG advance; t
 :class:`ErrorMemory` owns ``e``.  It *is* the flat input of the encoders: ``flc_ef_accumulate`` writes ``a`` into it in
 place, the (deferred, batched) stacked encode reads it, and ``flc_ef_residual_round`` subtracts what the round's records
 carry at their K kept entries — ``e'`` equals ``a`` everywhere else bit for bit, so no dense pass follows the encode.
+A dithering quantizer's dense record changes every element; there the batched encode itself
+(``flc_quant_encode_residual_round``, opt-in: ``compressed.EF_DENSE_DEFER``) stores ``a − decode(code)`` back to the
+positions it read, so again nothing is decoded and no pass follows.
 A NaN or inf that enters the memory stays there, as the expression says; :meth:`ErrorMemory.reset` is the way out.
 """
 

@@ -124,6 +124,23 @@ size_t flc_quant_encode_round_workspace_size(int64_t n, int n_msgs);
 int flc_quant_encode_round(const float* const* xs, int n_msgs, int64_t n, int kind, int levels, int bits, int norm_p,
                            const uint64_t* seeds, const uint64_t* counters, uint8_t* const* codes,
                            float* const* norms, int64_t* const* counts, void* ws, size_t ws_bytes, void* stream);
+/* flc_quant_encode_round with error feedback in the encode's own pass: message c's input is its error memory es[c],
+ * already holding a (flc_ef_accumulate), and the call leaves es[c][i] = fp32(a_i - v_i) for every i < n, v_i the value
+ * flc_quant_decode(codes[c], 1, n, kind, levels, bits, norms[c], NULL, 0, .) gives element i.  codes[c], *norms[c]
+ * and *counts[c] are bit-identical to flc_quant_encode_round's for xs[c] = es[c], and the memories to that call
+ * followed by flc_quant_decode into a fresh vector and flc_ef_residual_dense: every element is subtracted (a zero
+ * code's a_i - 0 keeps a_i, -0 included; under a norm of 0, +-inf or NaN any other code gives NaN).  Each thread of
+ * the encode launch computes the decoder's value of its codes from registers and stores the residual to the positions
+ * it loaded: no decode, no temporary, no further launch.  Launches as flc_quant_encode_round (one norm and one encode
+ * launch per 64 messages, capturable); only the encode launch writes a memory, so if a launch cannot be enqueued
+ * (FLC_EHIP) the memories of that link of 64 messages and of every later link still hold a, while those of earlier
+ * links already hold the residual.  FLC_EINVAL (nothing launched): flc_quant_encode_round's cases, an es[c] that is
+ * null or not 16-B aligned, two messages whose memories share elements.  FLC_EWORKSPACE: ws_bytes <
+ * flc_quant_encode_round_workspace_size(n, n_msgs). */
+int flc_quant_encode_residual_round(float* const* es, int n_msgs, int64_t n, int kind, int levels, int bits,
+                                    int norm_p, const uint64_t* seeds, const uint64_t* counters,
+                                    uint8_t* const* codes, float* const* norms, int64_t* const* counts, void* ws,
+                                    size_t ws_bytes, void* stream);
 /* the quantizer workspace's sticky error word (4: a one-launch encode's grid exchange timed out, i.e. its blocks were
  * not all resident — the outputs of that call are invalid); copied to *err_out (device uint64), zeroed with reset */
 int flc_quant_status(void* ws, uint64_t* err_out, int reset, void* stream);
