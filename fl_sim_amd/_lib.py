@@ -71,6 +71,10 @@ SIGNATURES = {
         c_int, [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     ),
     "flc_natural_decode": (c_int, [c_void_p, c_int64, c_float, c_int, c_void_p, c_void_p]),
+    "flc_natural_encode_round": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "flc_natural_encode_residual_round": (
+        c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    ),
     "flc_topk_workspace_size": (c_size_t, [c_int64, c_int64]),
     "flc_topk_status": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "flc_topk_select_plan": (c_int, [c_int64, c_int64, c_int, c_int, POINTER(c_int64)]),

@@ -341,6 +341,74 @@ def _quant_round_call(entry: str, xp: List[int], n: int, dev, kind: int, levels:
          ws.numel(), _stream(dev))
 
 
+def natural_encode_round(xs: Sequence[torch.Tensor], seeds: Sequence[int], counters: Sequence[int], records) -> None:
+    """A round's natural-compressor messages in one call (flc_natural_encode_round, philox mode): message c — the flat
+    fp32 vector ``xs[c]``, all of one size on one device — is encoded with its own Philox ``(seeds[c], counters[c])``
+    into the codes view of the dense record ``records[c]`` (dense_wire_views with FLC_WIRE_NATURAL), bit-identical to
+    ``flc_natural_encode`` of that vector alone.  ``records``: a ``[C, >= stride]`` uint8 block or a sequence of C
+    records.  One launch per 64 messages, no workspace."""
+    C = len(xs)
+    if C == 0:
+        return
+    n, dev = xs[0].numel(), xs[0].device
+    xp = _batch_ptrs(xs, n, dev) if dev.type == "cuda" else None
+    if xp is None:  # (the slow path: checks with messages, copies of misaligned inputs)
+        xs = [_dev_f32(x).reshape(-1) for x in xs]
+        if any(x.numel() != n or x.device != dev for x in xs):
+            raise ValueError("a round encode takes messages of one size on one device")
+        xp = [x.data_ptr() for x in xs]
+    _natural_round_call("flc_natural_encode_round", xp, n, dev, seeds, counters, records)
+
+
+def natural_encode_residual_round(mems: Sequence[torch.Tensor], seeds: Sequence[int], counters: Sequence[int],
+                                  records) -> None:
+    """:func:`natural_encode_round` with error feedback in the encode's own pass (flc_natural_encode_residual_round):
+    message c's input is the error memory ``mems[c]``, holding ``a``; the records are those of
+    ``natural_encode_round(mems, ...)`` bit for bit, and each memory is left holding ``a − decode(records[c])`` — what
+    ``dense_record_decode`` into a fresh vector and :func:`ef_residual_dense` leave — with no decode, no temporary and
+    no further launch.  The memories are written in place, so nothing is copied for them: each must be a contiguous,
+    16-B aligned float32 tensor of one size on one HIP device, and no two may share elements."""
+    C = len(mems)
+    if C == 0:
+        return
+    if not isinstance(mems[0], torch.Tensor) or mems[0].device.type != "cuda":
+        raise TypeError("the memories must be float32 tensors on a HIP device")
+    n, dev = mems[0].numel(), mems[0].device
+    ep = _batch_ptrs(mems, n, dev)
+    if ep is None:
+        raise ValueError("the memories must be contiguous, 16-B aligned float32 tensors of one size on one device")
+    _natural_round_call("flc_natural_encode_residual_round", ep, n, dev, seeds, counters, records)
+
+
+def _natural_round_call(entry: str, xp: List[int], n: int, dev, seeds, counters, records) -> None:
+    """The code views and tables of a round's natural-compressor encode, then the call (``entry``: the plain or the
+    residual form; ``xp``: the messages' input pointers).  The record-view arithmetic of :func:`_quant_round_call`."""
+    import ctypes
+
+    C = len(xp)
+    if len(seeds) != C or len(counters) != C:
+        raise ValueError("one seed and one counter per message")
+    fmt = _lib.FLC_WIRE_NATURAL
+    if isinstance(records, torch.Tensor) and records.dim() == 2:  # one record block: the rows' views by arithmetic
+        stride, off = dense_wire_layout(n, fmt, 16)
+        if records.shape[0] != C or records.shape[1] % 16 or records.device != dev:
+            raise ValueError(f"records must be a [{C}, >= {stride}] uint8 block (16-B rows) on {dev}")
+        dense_wire_views(records[0], n, fmt, 16)  # (dtype, size and alignment, checked on one row for all)
+        cps = [records.data_ptr() + c * records.shape[1] + off["codes"] for c in range(C)]
+    else:
+        if len(records) != C:
+            raise ValueError("one record per message")
+        views = [dense_wire_views(r, n, fmt, 16) for r in records]
+        if any(r.device != dev for r in records):
+            raise ValueError(f"the records must be on {dev}")
+        cps = [v[1].data_ptr() for v in views]
+    P = ctypes.c_void_p * C
+    U = ctypes.c_uint64 * C
+    vp = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+    call(entry, vp(P(*xp)), C, n, vp(U(*[int(s_) for s_ in seeds])), vp(U(*[int(t) for t in counters])), vp(P(*cps)),
+         _stream(dev))
+
+
 def fold_dense_wires(wires: torch.Tensor, slots: Sequence[int], weights: Sequence[float], n: int, fmt: int,
                      levels: int, bits: int, out: Optional[torch.Tensor] = None,
                      accumulate: bool = False) -> torch.Tensor:

@@ -521,6 +521,10 @@ def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]
             r = _defer_dense(out, shapes, n, compressors[0], dc, dev)  # (out: a new vector, the snapshot)
             if r is not None:
                 return r
+        if NATURAL_DEFER and DEFER_ENCODE and dc[0] == FLC_WIRE_NATURAL and n <= _DEFER_NATURAL_MAX_N:
+            r = _defer_natural(out, shapes, n, compressors[0], dev)
+            if r is not None:
+                return r
         return _dense_record(out, shapes, n, compressors[0], dc, dev)
     K = sparse_wire_codec(compressors, n) if sparse and _all_f32(local, cached) else None
     if K is not None:  # the sparsifier's own wire as the message: (idx, val, tiles) written into the record
@@ -581,6 +585,11 @@ def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torc
             r = _defer_dense(e, shapes, n, compressors[0], dc, dev, mem)
             if r is not None:
                 return r
+        if (NATURAL_DEFER and DEFER_ENCODE and dc[0] == FLC_WIRE_NATURAL and n <= _DEFER_EF_NATURAL_MAX_N
+                and _all_f32(local, cached)):  # (the messages _compress defers, no others)
+            r = _defer_natural(e, shapes, n, compressors[0], dev, mem)
+            if r is not None:
+                return r
         d = _dense_record(e, shapes, n, compressors[0], dc, dev)
         codec.ef_residual_dense(e, codec.dense_record_decode(d._record, n, dc[0], dc[1], dc[2]))
         return d
@@ -635,7 +644,8 @@ def deferred_stats(reset: bool = False) -> dict:
 
 
 def deferred_dense_stats(reset: bool = False) -> dict:
-    """:func:`deferred_stats` for the dense records' batched encodes (flc_quant_encode_round), counted apart."""
+    """:func:`deferred_stats` for the dense records' batched encodes (flc_quant_encode_round, flc_natural_encode_round
+    and their residual forms), counted apart."""
     return _read_stats(_DENSE_STATS, reset)
 
 
@@ -772,6 +782,44 @@ class _DenseBatch(_Batch):
         return rows
 
 
+# Deferred natural-compressor records (philox mode, `wire` on, the natural compressor's uint16 wire), behind
+# FLC_NATURAL_DEFER=1 (NATURAL_DEFER, off by default).  The compressor has no norm, so a round is one streaming launch
+# per 64 messages with no workspace (flc_natural_encode_round), each message with its own (seed, counter) and record,
+# bit-identical to the per-message flc_natural_encode.  With error feedback the message waits in a batch of its own
+# kind (the key's last element) with the error memory's tensor as the encoder's input, and one
+# flc_natural_encode_residual_round writes the round's records and leaves every memory holding a − decode(record) from
+# the encode's own pass — the immediate chain's flc_natural_decode into a fresh vector and flc_ef_residual_dense are not
+# run.  Records, memories, statistics and counters are bit-identical to the immediate path's.  The same switch
+# (FLC_DEFER_ENCODE) and pending bounds as the other batches, which share _PENDING with these.  The size bounds are
+# measured (profiles/natural_defer_round.json, encodes only, two runs, device events): each is the largest size at which
+# the round call's min–max range lay below the per-message chain's in both runs.  One streaming launch has no mid-size
+# dip like the dithering round's two: ten plain messages take 37 us against 81 us at 417,482 elements and eight take
+# 107 against 133 us at 8 M (at 16 M 178 against 198 us, the ranges touching in one run); with feedback ten take 40
+# against 254 us at 417,482 and eight 244 against 567 us at 16 M, apart in both runs at every size.
+NATURAL_DEFER = os.environ.get("FLC_NATURAL_DEFER", "0") == "1"
+_DEFER_NATURAL_MAX_N = 8_000_000
+_DEFER_EF_NATURAL_MAX_N = 16_000_000
+
+
+class _NaturalBatch(_Batch):
+    """The waiting natural-compressor messages of one (device, "natural", n, feedback); an item has no count slot and
+    no compressor (the send count is 9/32 n whatever the data).  In a feedback batch every item's ``flat`` is its error
+    memory's tensor."""
+
+    stats = _DENSE_STATS
+
+    def _encode_rows(self, items, dev):
+        _, _, n, fed = self.key
+        stride, _ = codec.dense_wire_layout(n, FLC_WIRE_NATURAL, 16)
+        recs = torch.empty(len(items), stride, dtype=torch.uint8, device=dev)
+        rows = recs.unbind(0)
+        # error feedback: the encode's own pass leaves e = a − decode(record) in the memories.  The call is the last
+        # thing here that can raise: a batch that failed has written no memory, and the retry encodes the same a
+        encode = codec.natural_encode_residual_round if fed else codec.natural_encode_round
+        encode([it.flat for it in items], [it.seed for it in items], [it.counter for it in items], recs)
+        return rows
+
+
 # Deferred sparse records (`sparse` on, one top-k compressor, any rng_mode: top-k draws no random numbers).  The
 # model-sized select is the same fixed latency as the stacked pipeline's, so these messages wait like the stacked ones
 # — the flat delta snapshotted (or the error memory's tensor itself), the send statistics advanced at `communicate` —
@@ -887,6 +935,26 @@ def _defer_dense(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[in
     else:
         comp._finish(n, n * _code_fraction(s))
     return _enqueue(b, _Item(d, x, seed, ctr, cnt, comp if std else None, st, st.cuda_stream, mem))
+
+
+def _defer_natural(x: torch.Tensor, shapes, n: int, comp: Compressor, dev,
+                   mem: Optional[ErrorMemory] = None) -> Optional[CompressedDelta]:
+    """The natural-compressor message of the flat vector ``x`` (a snapshot, or — ``mem`` — that error memory's tensor,
+    which the batched encode leaves holding the residual) joins the round's batched encode; the Philox stream and the
+    send statistics advance here exactly as :func:`_dense_record` advances them (compressors.py:302-325).  None
+    (nothing advanced: the immediate path takes the message) outside philox mode on a float32 vector."""
+    if comp.rng_mode != "philox" or x.dtype != torch.float32 or x.device != dev:
+        return None
+    if mem is None:
+        x = codec._dev_f32(x).reshape(-1)
+    elif x.dim() != 1 or not x.is_contiguous() or x.data_ptr() % 16:  # (written in place: never a copy)
+        return None
+    st = torch.cuda.current_stream(dev)
+    b = _waiting(_NaturalBatch, (dev.index, "natural", n, mem is not None))
+    seed, ctr = comp.philox.next()
+    d = CompressedDelta(shapes, dev, n, levels=0, batch=b, format=FLC_WIRE_NATURAL, bits=16)
+    comp._finish(n, 9.0 / 32.0 * n)  # compressors.py:325
+    return _enqueue(b, _Item(d, x, seed, ctr, None, None, st, st.cuda_stream, mem))
 
 
 def _defer_sparse(flat: torch.Tensor, shapes, n: int, K: int, tk: Compressor, dev,

@@ -164,6 +164,32 @@ int flc_natural_encode(const float* x, int64_t n, uint64_t seed, uint64_t counte
                        void* stream);
 int flc_natural_decode(const uint16_t* codes, int64_t n, float weight, int accumulate, float* out,
                        void* stream);
+/* a round's messages in one call (philox mode only; compat mode's sequential uniforms stay with flc_natural_encode;
+ * compressors.py:302-325): message c is the flat vector xs[c] of n elements with its own Philox (seeds[c],
+ * counters[c]) and its own code stream codes[c] (2n bytes); the element index restarts at 0 in every message, so
+ * codes[c] is bit-identical to flc_natural_encode(xs[c], n, seeds[c], counters[c], NULL, codes[c], NULL, ...).  The
+ * compressor has no norm: ONE ordinary streaming launch per 64 messages over (block of 8192 elements, message), no
+ * workspace, no counts (the send count is 9/32 n whatever the data), no grid-wide wait and no status word; the message
+ * table travels in the kernel arguments, so nothing is copied from the host arrays and the call is capturable; more
+ * than 64 messages chain launches.  Code bytes past 2n are never written.  xs, seeds, counters and codes are HOST
+ * arrays of n_msgs entries.  FLC_EINVAL (nothing launched): a null table or entry, n_msgs < 1, n < 1 or n >= 2^31, an
+ * xs[c] or codes[c] not 16-B aligned. */
+int flc_natural_encode_round(const float* const* xs, int n_msgs, int64_t n, const uint64_t* seeds,
+                             const uint64_t* counters, uint16_t* const* codes, void* stream);
+/* flc_natural_encode_round with error feedback in the encode's own pass: message c's input is its error memory es[c],
+ * already holding a (flc_ef_accumulate), and the call leaves es[c][i] = fp32(a_i - v_i) for every i < n, v_i the value
+ * flc_natural_decode(codes[c], n, 1, 0, .) gives element i.  codes[c] is bit-identical to flc_natural_encode_round's
+ * for xs[c] = es[c], and the memories to that call followed by flc_natural_decode into a fresh vector and
+ * flc_ef_residual_dense: every element is subtracted (a zero code's a_i - 0 keeps a_i, -0 included; a NaN's code
+ * 0x7fff gives a_i - NaN, +-inf gives a_i - (+-inf)).  Each thread computes the decoder's value of the codes it has
+ * just formed and stores the residual to the positions it loaded (plain stores: the next round's accumulate reads
+ * them): no decode, no temporary, no further launch.  Elements at or past n are never written.  Only the encode
+ * launch writes a memory, so if a launch cannot be enqueued (FLC_EHIP) the memories of that link of 64 messages and
+ * of every later link still hold a, while those of earlier links already hold the residual.  FLC_EINVAL (nothing
+ * launched): flc_natural_encode_round's cases, an es[c] that is null or not 16-B aligned, two messages whose
+ * memories [es[c], es[c] + n) share elements. */
+int flc_natural_encode_residual_round(float* const* es, int n_msgs, int64_t n, const uint64_t* seeds,
+                                      const uint64_t* counters, uint16_t* const* codes, void* stream);
 
 /* ------------------------------------------------------------------ top-k sparsifier
  * (compressors.py:293-296): keeps the k largest *signed* values (NaN largest, -0 == +0); among values
