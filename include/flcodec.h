@@ -257,9 +257,12 @@ int flc_tile_index(const int32_t* idx, int64_t k, int64_t n, uint32_t* tiles, vo
  * three pointers inside it. */
 int flc_topk_encode_tiled(const float* x, int64_t n, int64_t k, int32_t* idx, float* val, uint32_t* tiles,
                           void* ws, size_t ws_bytes, void* stream);
-/* dense decode of an ascending sparse stream: out[idx[j]] = scale * val[j], zeros elsewhere
- * (compressors.py:289-291, 294-295); out = weight * v, or with accumulate out = fmaf(weight, v, out)
- * over the whole vector (the fused aggregation).  Workspace: a per-tile index of the stream. */
+/* dense decode of an ascending sparse stream of unique indices below n: v[idx[j]] = fl(scale * val[j]), v = +0
+ * elsewhere (compressors.py:289-291, 294-295); then, over the whole vector (the fused aggregation),
+ *   out = accumulate ? fmaf(weight, v, out) : (weight != 1 ? fl(weight * v) : v)
+ * An unkept position takes the weight like a kept one: -0 under a negative weight, NaN under an infinite or NaN one.
+ * 0 <= k <= n: k == 0 (idx and val may be NULL) decodes the all-zero vector and still writes every element of out,
+ * k == n keeps every element.  Nothing outside out[0, n) is written.  Workspace: a per-tile index of the stream. */
 size_t flc_sparse_decode_workspace_size(int64_t n);
 int flc_sparse_decode(const int32_t* idx, const float* val, int64_t k, float scale, int64_t n,
                       float weight, int accumulate, float* out, void* ws, size_t ws_bytes, void* stream);
@@ -276,6 +279,10 @@ int flc_stacked_encode(const float* x, int64_t n, int64_t k, int levels, uint64_
 int flc_stacked_encode_tiled(const float* x, int64_t n, int64_t k, int levels, uint64_t seed,
                              uint64_t counter, const double* compat_u, int32_t* idx, uint8_t* codes,
                              float* norm, uint32_t* tiles, void* ws, size_t ws_bytes, void* stream);
+/* dense decode: v[idx[j]] = fp32(fp32(lv) * sign) * norm with lv = level * (1 / levels) in fp64 and lv = 1 at level ==
+ * levels (compressors.py:157, 357; a set sign bit with level 0 gives -0), v = +0 elsewhere; a norm that is 0, negative,
+ * +-inf or NaN decodes code 0 to +0 and every other code to NaN.  The output rule over the whole vector, 0 <= k <= n
+ * and the extent are flc_sparse_decode's. */
 int flc_stacked_decode(const int32_t* idx, const uint8_t* codes, int64_t k, int levels,
                        const float* norm, int64_t n, float weight, int accumulate, float* out,
                        void* ws, size_t ws_bytes, void* stream);  /* ws: flc_sparse_decode_workspace_size */
@@ -632,7 +639,11 @@ int flc_sparse_gather(const float* x, int64_t n, const int32_t* idx, int64_t k, 
  *   flc_quant_norm_f64     p = inf: max |x|; p = 2: sqrt of an fp64 sum of squares (fixed order)
  *   flc_quant_f64          standard / natural dithering (compressors.py:339-357, 376-393) with the given norm:
  *                          8-bit codes (sign << 7 | level) and / or the decoded vector lv * sign * norm; nnz =
- *                          count(x != 0) when non-NULL
+ *                          count(x != 0) when non-NULL.  A norm that is not a positive finite double encodes as the
+ *                          float32 codec's does (code 0 for x == 0, else 1) and decodes code 0 to +0, any other to NaN
+ *   flc_natural_decode_f64 / flc_quant_decode_f64   the decoded vectors of those codes (natural: fields 1..2099,
+ *                          2^(field - 1075), 2^1024 being +-inf; dithering: the level tables of flc_quant_kind in fp64,
+ *                          standard lv = i * (1 / levels) with lv[levels] = 1)
  *   flc_topk_dense_f64     out = x on the K largest (ties: the highest indices), +0 elsewhere (293-296), 0 < k < n
  * Workspace: flc_f64_workspace_size(n, k) bytes (compat mode, the norm and top-k with that k; not needed by the
  * element-wise forms or by the Philox-mode encoders). */
