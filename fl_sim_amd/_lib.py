@@ -65,6 +65,40 @@ SIGNATURES = {
     "flc_quant_decode": (
         c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     ),
+    "flc_bucket_wire_layout": (c_size_t, [c_int64, c_int, c_int, c_int64, c_void_p]),
+    "flc_bucket_encode": (
+        c_int,
+        [c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p],
+    ),
+    "flc_bucket_encode_round": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p],
+    ),
+    "flc_bucket_decode": (
+        c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_void_p, c_float, c_int, c_void_p, c_void_p]
+    ),
+    "flc_fold_bucket_wires": (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int64, c_int, c_void_p,
+         c_void_p],
+    ),
+    "flc_fedopt_fold_bucket_records": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_int, c_float, c_int, c_double, c_double, c_double, c_void_p],
+    ),
+    "flc_avg_and_gradient_bucket_records": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int64,
+         c_void_p, c_int, c_float, c_void_p],
+    ),
+    "flc_fold_bucket_record_groups": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_int,
+         c_void_p],
+    ),
     "flc_count_consumers": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "flc_natural_workspace_size": (c_size_t, [c_int64]),
     "flc_natural_encode": (

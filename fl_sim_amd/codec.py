@@ -409,6 +409,122 @@ def _natural_round_call(entry: str, xp: List[int], n: int, dev, seeds, counters,
          _stream(dev))
 
 
+# --------------------------------------------------------------------------------------- bucket records
+BUCKET_SIZES = (64, 128, 256, 512, 1024, 2048, 4096)
+_BUCKET_LAYOUT: Dict[tuple, tuple] = {}
+
+
+def _norm_kind(p) -> int:
+    if isinstance(p, int) and p in (_lib.FLC_NORM_INF, _lib.FLC_NORM_L2):
+        return p
+    if math.isinf(p):
+        return _lib.FLC_NORM_INF
+    if p == 2:
+        return _lib.FLC_NORM_L2
+    raise ValueError(f"p must be inf or 2 (got {p})")
+
+
+def bucket_wire_layout(n: int, fmt: int, bits: int, bucket: int):
+    """(record bytes, {"norms", "codes"} byte offsets) of a bucket record (flc_bucket_wire_layout): the
+    ``ceil(n / bucket)`` fp32 norms of a bucketed dithering quantizer, then its ``bits``-bit codes."""
+    import ctypes
+
+    key = (int(n), int(fmt), int(bits), int(bucket))
+    r = _BUCKET_LAYOUT.get(key)
+    if r is None:
+        off = (ctypes.c_int64 * 2)()
+        total = _lib.size("flc_bucket_wire_layout", key[0], key[1], key[2], key[3], ctypes.cast(off, ctypes.c_void_p))
+        if total == 0:
+            raise ValueError(f"bad bucket record shape n={n}, format={fmt}, bits={bits}, bucket={bucket}")
+        r = _BUCKET_LAYOUT[key] = (int(total), {"norms": int(off[0]), "codes": int(off[1])})
+    return r
+
+
+def bucket_wire_views(record: torch.Tensor, n: int, fmt: int, bits: int, bucket: int):
+    """(norms, codes) views into a bucket record (a contiguous uint8 HIP tensor of at least
+    ``bucket_wire_layout(...)[0]`` bytes, 16-B aligned): the per-bucket fp32 norms and the uint8 code stream."""
+    stride, off = bucket_wire_layout(n, fmt, bits, bucket)
+    if record.dtype != torch.uint8 or record.device.type != "cuda" or not record.is_contiguous():
+        raise TypeError("a wire record is a contiguous uint8 HIP tensor")
+    rec = record.reshape(-1)
+    if rec.numel() < stride or rec.data_ptr() % 16 != 0:
+        raise ValueError(f"a bucket record needs {stride} bytes, 16-B aligned")
+    nb = (n + bucket - 1) // bucket
+    return (rec[off["norms"]:off["norms"] + 4 * nb].view(torch.float32),
+            rec[off["codes"]:off["codes"] + (n * bits + 7) // 8])
+
+
+def bucket_encode(x: torch.Tensor, kind: int, levels: int, bucket: int, p=math.inf, seed: int = 0, counter: int = 0,
+                  record: Optional[torch.Tensor] = None, norms: Optional[torch.Tensor] = None,
+                  want_nnz: bool = False, decode: bool = False):
+    """One message as a bucket record in one launch that reads ``x`` once (flc_bucket_encode, philox mode): the
+    dithering quantizer applied to every ``bucket`` consecutive elements with that bucket's own norm.  ``norms``: given
+    per-bucket norms (``ceil(n / bucket)`` floats) used instead of the device's.  Returns
+    ``(record, nnz or None, decoded or None)``; ``record`` is allocated when not given."""
+    x = _dev_f32(x).reshape(-1)
+    n, dev = x.numel(), x.device
+    bits = code_bits(levels)
+    stride, _ = bucket_wire_layout(n, kind, bits, bucket)
+    if record is None:
+        record = torch.empty(stride, dtype=torch.uint8, device=dev)
+    nv, cv = bucket_wire_views(record, n, kind, bits, bucket)
+    if norms is not None:
+        if norms.numel() != nv.numel():
+            raise ValueError(f"{nv.numel()} bucket norms expected (got {norms.numel()})")
+        nv.copy_(norms.reshape(-1).to(device=dev, dtype=torch.float32))
+    nnz = torch.empty(1, dtype=torch.int64, device=dev) if want_nnz else None
+    out = torch.empty(n, dtype=torch.float32, device=dev) if decode else None
+    call("flc_bucket_encode", _p(x), n, kind, levels, bits, bucket, _norm_kind(p), int(norms is not None), seed,
+         counter, _p(nv), _p(cv), _p(nnz), _p(out), _stream(dev))
+    return record, nnz, out
+
+
+def bucket_encode_round(xs: Sequence[torch.Tensor], kind: int, levels: int, bits: int, bucket: int, norm_p: int,
+                        seeds: Sequence[int], counters: Sequence[int], records, counts=None,
+                        norms_given: bool = False) -> None:
+    """A round's messages as bucket records in one launch per 64 messages (flc_bucket_encode_round): message c — the
+    flat fp32 vector ``xs[c]``, all of one size on one device — is encoded with its own Philox
+    ``(seeds[c], counters[c])`` into ``records[c]``, bit-identical to :func:`bucket_encode` of that vector alone.
+    ``records``: a ``[C, >= stride]`` uint8 block or a sequence of C records; ``counts``: None, or one one-element
+    device int64 tensor per message (a contiguous ``[C]`` tensor also)."""
+    import ctypes
+
+    C = len(xs)
+    if C == 0:
+        return
+    if len(seeds) != C or len(counters) != C:
+        raise ValueError("one seed and one counter per message")
+    xs = [_dev_f32(x).reshape(-1) for x in xs]
+    n, dev = xs[0].numel(), xs[0].device
+    if any(x.numel() != n or x.device != dev for x in xs):
+        raise ValueError("a round encode takes messages of one size on one device")
+    if len(records) != C:
+        raise ValueError("one record per message")
+    views = [bucket_wire_views(r, n, kind, bits, bucket) for r in records]
+    if counts is not None and len(counts) != C:
+        raise ValueError("one count slot per message")
+    P, U = ctypes.c_void_p * C, ctypes.c_uint64 * C
+    vp = lambda a: None if a is None else ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+    cnt = None if counts is None else P(*[c.data_ptr() for c in counts])
+    call("flc_bucket_encode_round", vp(P(*[x.data_ptr() for x in xs])), C, n, kind, levels, bits, bucket,
+         _norm_kind(norm_p), int(norms_given), vp(U(*[int(s_) for s_ in seeds])), vp(U(*[int(t) for t in counters])),
+         vp(P(*[v[0].data_ptr() for v in views])), vp(P(*[v[1].data_ptr() for v in views])), vp(cnt), _stream(dev))
+
+
+def bucket_decode(record: torch.Tensor, n: int, kind: int, levels: int, bits: int, bucket: int,
+                  out: Optional[torch.Tensor] = None, weight: float = 1.0, accumulate: bool = False) -> torch.Tensor:
+    """The decoded flat vector of a bucket record (flc_bucket_decode): ``v = fp32(fp32(level) * sign) * norm[e // B]``;
+    ``out = fmaf(weight, v, out)`` when accumulating, ``weight * v`` otherwise."""
+    nv, cv = bucket_wire_views(record, n, kind, bits, bucket)
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs an out tensor")
+        out = torch.empty(n, dtype=torch.float32, device=record.device)
+    call("flc_bucket_decode", _p(cv), n, kind, levels, bits, bucket, _p(nv), float(weight), int(accumulate), _p(out),
+         _stream(out.device))
+    return out
+
+
 def fold_dense_wires(wires: torch.Tensor, slots: Sequence[int], weights: Sequence[float], n: int, fmt: int,
                      levels: int, bits: int, out: Optional[torch.Tensor] = None,
                      accumulate: bool = False) -> torch.Tensor:

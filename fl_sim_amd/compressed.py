@@ -152,20 +152,25 @@ class CompressedDelta(_abc.Sequence):
     sign | level codes, the kept set's norm, tile pointers); ``kind == "sparse"`` (``sparse=True``): the sparse record
     of a top-k or rand-k compressor (ascending int32 indices, the decoded fp32 values, tile pointers); ``kind == "quant"`` / ``"natural"`` (``wire=True``): the
     dense record of a dithering quantizer (its norm and packed ``bits``-bit codes) or of the natural compressor (one
-    uint16 per element), ``format`` being flc_dense_wire_layout's; ``kind == "dense"``: the decoded flat delta.
+    uint16 per element), ``format`` being flc_dense_wire_layout's; ``kind == "bucket"`` (``wire=True`` with a bucket
+    size): the bucket record of a bucketed dithering quantizer (one norm per ``bucket`` elements, then the packed codes;
+    flc_bucket_wire_layout); ``kind == "dense"``: the decoded flat delta.
     Indexing gives tensor ``j`` of the model's shapes (the decoded values, one flat decode on first access), so code
     written for a list of delta tensors reads it unchanged."""
 
     def __init__(self, shapes: Sequence[torch.Size], device: torch.device, n: int, *, record=None, k: int = 0,
                  levels: int = 0, flat: Optional[torch.Tensor] = None, batch: Optional["_Batch"] = None,
-                 format: Optional[int] = None, bits: int = 0, sparse: bool = False):
+                 format: Optional[int] = None, bits: int = 0, sparse: bool = False, bucket: int = 0):
         self.shapes = [torch.Size(s) for s in shapes]
         self.device = device
         self.n = int(n)
         self._record, self.k, self.levels = record, int(k), int(levels)
         self._batch = batch  # (a deferred encode: the record is made by the batch's launch on first access)
         self.format, self.bits = format, int(bits)
-        if format is not None:
+        self.bucket = int(bucket)  # a bucket record's bucket size (flc_bucket_wire_layout), else 0
+        if format is not None and self.bucket:
+            self.kind = "bucket"
+        elif format is not None:
             self.kind = "natural" if format == FLC_WIRE_NATURAL else "quant"
         elif sparse:  # (a top-k / rand-k record, flc_sparse_wire_layout(n, k): levels 0, no format)
             self.kind = "sparse"
@@ -184,7 +189,7 @@ class CompressedDelta(_abc.Sequence):
     @property
     def codec_key(self) -> tuple:
         """What a round's records must share to be folded together."""
-        return (self.kind, self.n, self.k, self.levels, self.format, self.bits)
+        return (self.kind, self.n, self.k, self.levels, self.format, self.bits, self.bucket)
 
     def __getstate__(self):
         """A copied or pickled message carries its record (a deferred encode runs first); a dense record travels
@@ -193,9 +198,13 @@ class CompressedDelta(_abc.Sequence):
             self._batch.run()
         d = self.__dict__.copy()
         d["_batch"] = None
-        if self.kind in ("quant", "natural"):
+        if self.kind in ("quant", "natural", "bucket"):
             d["_flat"] = d["_views"] = None
         return d
+
+    def __setstate__(self, d):
+        self.__dict__.update(d)
+        self.__dict__.setdefault("bucket", 0)  # (a delta pickled before bucket records existed)
 
     @property
     def nbytes(self) -> int:
@@ -206,7 +215,9 @@ class CompressedDelta(_abc.Sequence):
         """The decoded flat delta (flc_stacked_decode_tiled, flc_sparse_decode_tiled, flc_quant_decode or
         flc_natural_decode of the record, once)."""
         if self._flat is None:
-            if self.kind in ("quant", "natural"):
+            if self.kind == "bucket":
+                self._flat = codec.bucket_decode(self.record, self.n, self.format, self.levels, self.bits, self.bucket)
+            elif self.kind in ("quant", "natural"):
                 self._flat = codec.dense_record_decode(self.record, self.n, self.format, self.levels, self.bits)
             elif self.kind == "sparse":
                 self._flat = codec.sparse_record_decode(self.record, self.n, self.k)
@@ -291,7 +302,7 @@ def _norm_stage_send(sd: Compressor, norm: torch.Tensor) -> float:
 
 def compress_delta(local: Sequence[torch.Tensor], cached: Sequence[torch.Tensor],
                    compressors: Sequence[Compressor], feedback: Optional[ErrorMemory] = None,
-                   wire: bool = False, sparse: bool = False) -> CompressedDelta:
+                   wire: bool = False, sparse: bool = False, bucket: int = 0) -> CompressedDelta:
     """The client's compressed delta ``compressors(cat(local − cached))`` (see the module docstring); every compressor's
     RNG stream and send statistics advance as its own ``compressVector`` call would advance them.  ``feedback``: the
     client's :class:`~fl_sim_amd.feedback.ErrorMemory` ``e`` for this vector — the message is then that of the input
@@ -299,24 +310,28 @@ def compress_delta(local: Sequence[torch.Tensor], cached: Sequence[torch.Tensor]
     one float32 dithering quantizer or natural compressor (:func:`dense_wire_codec`) sends its dense record — the norm
     and the packed codes — instead of the decoded vector; any other compressor list is sent as without it.  ``sparse``:
     one top-k or rand-k compressor (:func:`sparse_wire_codec`) sends its sparse record — the kept indices, their decoded
-    values and the tile pointers — instead of the decoded vector; any other compressor list is sent as without it."""
+    values and the tile pointers — instead of the decoded vector; any other compressor list is sent as without it.
+    ``bucket`` (a power of two in [64, 4096]; 0: the compressor's own ``bucket``): a float32 dithering quantizer
+    quantizes every ``bucket`` consecutive elements under that bucket's own norm (``Compressor.bucket``); with ``wire``
+    the message carries the bucket record (``kind == "bucket"``), without it the decoded vector."""
     if feedback is not None:
-        return _compress_feedback(list(local), cached, compressors, feedback, wire, sparse)
-    return _compress(list(local), cached, compressors, wire, sparse)
+        return _compress_feedback(list(local), cached, compressors, feedback, wire, sparse, bucket)
+    return _compress(list(local), cached, compressors, wire, sparse, bucket)
 
 
 def compress_tensors(tensors: Sequence[torch.Tensor], compressors: Sequence[Compressor],
                      feedback: Optional[ErrorMemory] = None, wire: bool = False,
-                     sparse: bool = False) -> CompressedDelta:
+                     sparse: bool = False, bucket: int = 0) -> CompressedDelta:
     """``compressors(cat(tensors))`` — :func:`compress_delta` with nothing subtracted (a client's gradient list): the
     stacked pipeline gives a packed record, any other compressor the decoded flat vector (``wire``: a dithering
     quantizer's or the natural compressor's dense record; ``sparse``: a top-k or rand-k compressor's sparse record);
     the compressors' RNG streams
     and send statistics advance alike, and in philox mode a deferred message joins the round's batched encode with the
-    flat vector as its snapshot.  ``feedback``: as for :func:`compress_delta` (``a = e + cat(tensors)``)."""
+    flat vector as its snapshot.  ``feedback``: as for :func:`compress_delta` (``a = e + cat(tensors)``); ``bucket``
+    likewise."""
     if feedback is not None:
-        return _compress_feedback(list(tensors), None, compressors, feedback, wire, sparse)
-    return _compress(list(tensors), None, compressors, wire, sparse)
+        return _compress_feedback(list(tensors), None, compressors, feedback, wire, sparse, bucket)
+    return _compress(list(tensors), None, compressors, wire, sparse, bucket)
 
 
 def dense_wire_codec(compressors: Sequence[Compressor]) -> Optional[Tuple[int, int, int]]:
@@ -406,6 +421,132 @@ def _dense_record(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[i
     return CompressedDelta(shapes, dev, n, record=rec, levels=s, format=fmt, bits=bits)
 
 
+_DITHER_F32 = (CompressorType.STANDARD_DITHERING_FP32, CompressorType.NATURAL_DITHERING_FP32)
+
+
+def _bucket_of(compressors: Sequence[Compressor], bucket: int) -> int:
+    """The bucket size a message of ``compressors`` is quantized with: ``bucket`` (the client's ``quant_bucket``), or
+    the one compressor's own ``bucket``; 0 unless the list is one float32 dithering quantizer."""
+    if len(compressors) != 1 or not isinstance(compressors[0], Compressor):
+        return 0
+    c = compressors[0]
+    if c.compressorType not in _DITHER_F32:
+        return 0
+    B = int(bucket or c.bucket or 0)
+    if B and B not in codec.BUCKET_SIZES:
+        raise ValueError(f"bucket must be 0 or a power of two in [64, 4096] (got {B})")
+    return B
+
+
+class _bucketed:
+    """``comp.bucket = B`` for the length of a ``compressVector`` call (the message's bucket size on a compressor
+    whose own is another)."""
+
+    def __init__(self, comp: Compressor, B: int):
+        self.comp, self.B = comp, B
+
+    def __enter__(self):
+        self.old = self.comp.bucket
+        self.comp.bucket = self.B
+
+    def __exit__(self, *exc):
+        self.comp.bucket = self.old
+
+
+def _bucket_stats(comp: Compressor, n: int, B: int, std: bool, cnt) -> None:
+    """The send statistics of the slice-wise compressVector calls (Compressor._compress_bucketed's), with a standard
+    dithering's nonzero count still on the device in ``cnt``: nb norms through the identical norm compressor, then one
+    code fraction per nonzero element; natural dithering: n code fractions."""
+    per = _code_fraction(comp.s)
+    if not std:
+        comp._finish(n, n * per)
+        return
+    nb = -(-n // B)
+    nc = comp.vectorNormCompressor
+    nc.last_input_advance = 1
+    nc.last_need_to_send_advance = 1
+    nc.total_input_components += nb
+    nc.really_need_to_send_components += nb
+    comp._finish_pending(n, cnt, nb, per)
+
+
+def _bucket_record(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[int, int, int], B: int,
+                   dev) -> CompressedDelta:
+    """The bucket record of the flat fp32 vector ``x`` under ``comp`` with bucket size ``B``, encoded at once.  Philox
+    mode: one flc_bucket_encode (the norms from the device, or — ``norm_mode`` "reference" — the host's per-slice
+    ``np.linalg.norm``), the nonzero count left in the compressor's pending slab.  Compat mode: the existing per-row
+    entry points over the ``[n // B, B]`` head and the tail, as ``Compressor._compress_bucketed`` composes them, with
+    flc_quant_encode writing each piece's codes at its place in the record's code stream (a whole bucket's codes start
+    16-B aligned) and the interpreter's draws consumed in index order."""
+    fmt, s, bits = dc
+    x = codec._dev_f32(x).reshape(-1)
+    std = fmt == FLC_Q_STANDARD_DITHER
+    if comp.rng_mode == "philox":
+        pk = _norm_kind(comp.p)
+        if pk is None:
+            raise ValueError(f"p must be inf or 2 (got {comp.p})")
+        given = None
+        if comp._wants_host_norm(device_input=True):
+            with _bucketed(comp, B):
+                given = torch.from_numpy(comp._reference_norm(x.detach().cpu().numpy())).to(dev)
+        seed, ctr = comp.philox.next()
+        cnt = comp._count_slot(dev) if std else None
+        stride, _ = codec.bucket_wire_layout(n, fmt, bits, B)
+        rec = torch.empty(stride, dtype=torch.uint8, device=dev)
+        nv, cv = codec.bucket_wire_views(rec, n, fmt, bits, B)
+        if given is not None:
+            nv.copy_(given)
+        _lib.call("flc_bucket_encode", x.data_ptr(), n, fmt, s, bits, B, pk, int(given is not None), seed, ctr,
+                  nv.data_ptr(), cv.data_ptr(), codec._p(cnt), None, codec._stream(dev))
+        _bucket_stats(comp, n, B, std, cnt)
+        return CompressedDelta(shapes, dev, n, record=rec, levels=s, format=fmt, bits=bits, bucket=B)
+    pk = _norm_kind(comp.p)
+    given = None
+    if comp._wants_host_norm(device_input=True):
+        with _bucketed(comp, B):
+            given = torch.from_numpy(comp._reference_norm(x.detach().cpu().numpy())).to(dev)
+    elif pk is None:
+        raise ValueError(f"p must be inf or 2 (got {comp.p})")
+    seed, ctr = comp.philox.next()
+    stride, _ = codec.bucket_wire_layout(n, fmt, bits, B)
+    rec = torch.empty(stride, dtype=torch.uint8, device=dev)
+    nv, cv = codec.bucket_wire_views(rec, n, fmt, bits, B)
+    if given is not None:
+        nv.copy_(given)
+    st = codec._stream(dev)
+    pieces = [(lo, min(65535, n // B - lo // B), B) for lo in range(0, (n // B) * B, 65535 * B)]
+    if n % B:
+        pieces.append(((n // B) * B, 1, n % B))
+    nnz_total = 0
+    for lo, rows, d in pieces:
+        x2 = x[lo:lo + rows * d].reshape(rows, d)
+        nrm = nv[lo // B:lo // B + rows]
+        ws = codec.workspace(dev, codec._ws_size(dev, "flc_quant_workspace_size", rows, d), "quant")
+        if given is None:
+            _lib.call("flc_quant_norm", x2.data_ptr(), rows, d, pk, nrm.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        consumers = int(codec.count_consumers(x2, nrm).item())
+        for r in (nrm == 0).nonzero().reshape(-1).tolist():  # (a p = 2 norm that underflowed: the reference fails)
+            comp._check_bracket(0.0, int(torch.count_nonzero(x2[r]).item()))
+        u = comp._uniforms(consumers, dev)
+        nnz = torch.empty(rows, dtype=torch.int64, device=dev) if std else None
+        _lib.call("flc_quant_encode", x2.data_ptr(), rows, d, fmt, s, bits, nrm.data_ptr(), seed, ctr, u.data_ptr(),
+                  cv.data_ptr() + lo * bits // 8, codec._p(nnz), ws.data_ptr(), ws.numel(), st)
+        if std:
+            nnz_total += int(nnz.sum().item())
+    per = _code_fraction(s)
+    if std:
+        nb = -(-n // B)
+        nc = comp.vectorNormCompressor
+        nc.last_input_advance = 1
+        nc.last_need_to_send_advance = 1
+        nc.total_input_components += nb
+        nc.really_need_to_send_components += nb
+        comp._finish(n, nb + nnz_total * per)
+    else:
+        comp._finish(n, n * per)
+    return CompressedDelta(shapes, dev, n, record=rec, levels=s, format=fmt, bits=bits, bucket=B)
+
+
 def sparse_wire_codec(compressors: Sequence[Compressor], n: Optional[int] = None) -> Optional[int]:
     """``K`` of the sparse record ``compressors`` sends with ``sparse`` on for a float32 vector of ``n`` elements
     (default: the compressor's own ``D``) — one top-k or rand-k compressor (compressors.py:284-296) with 0 < K < n (a
@@ -476,7 +617,8 @@ def _flatten(ts: Sequence[torch.Tensor], dev: torch.device) -> torch.Tensor:
 
 
 def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
-              compressors: Sequence[Compressor], wire: bool = False, sparse: bool = False) -> CompressedDelta:
+              compressors: Sequence[Compressor], wire: bool = False, sparse: bool = False,
+              bucket: int = 0) -> CompressedDelta:
     """``compressors(cat(local − cached))``, or (``cached`` None) ``compressors(cat(local))``."""
     dev = local[0].device if local[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
     shapes = [t.shape for t in local]
@@ -516,6 +658,15 @@ def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]
             return _stacked(ls, gs, shapes, n, pipe[0], pipe[1], compressors[0], compressors[1], dev, seed_ctr)
         out = codec.delta_flatten(ls, gs)
     dc = dense_wire_codec(compressors) if wire else None
+    B = _bucket_of(compressors, bucket)
+    if B and dc is not None and out.dtype == torch.float32:  # a bucket record: one norm per B elements, then the codes
+        if DEFER_ENCODE and n <= _DEFER_BUCKET_MAX_N:
+            r = _defer_bucket(out, shapes, n, compressors[0], dc, B, dev)  # (out: a new vector, the snapshot)
+            if r is not None:
+                return r
+        return _bucket_record(out, shapes, n, compressors[0], dc, B, dev)
+    if B:
+        dc = None  # (a bucketed quantizer never sends the whole-vector dense record)
     if dc is not None:  # the quantizer's own wire as the message: codes written into the record, nothing decoded
         if DEFER_ENCODE and n <= _DEFER_DENSE_MAX_N and dc[0] != FLC_WIRE_NATURAL:
             r = _defer_dense(out, shapes, n, compressors[0], dc, dev)  # (out: a new vector, the snapshot)
@@ -531,6 +682,9 @@ def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]
         if DEFER_ENCODE and n <= _DEFER_MAX_N and compressors[0].compressorType == CompressorType.TOPK_COMPRESSOR:
             return _defer_sparse(out, shapes, n, K, compressors[0], dev, None)  # (out: a new vector, the snapshot)
         return _sparse_record(out, shapes, n, compressors[0], K, dev)
+    if B:  # the bucketed compressVector's decoded vector
+        with _bucketed(compressors[0], B):
+            return CompressedDelta(shapes, dev, n, flat=compressors[0].compressVector(out))
     for comp in compressors:  # the drop-in compressors on the device, in order
         out = comp.compressVector(out)
     return CompressedDelta(shapes, dev, n, flat=out)
@@ -551,7 +705,7 @@ def _accumulate(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tenso
 
 def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
                        compressors: Sequence[Compressor], mem: ErrorMemory, wire: bool = False,
-                       sparse: bool = False) -> CompressedDelta:
+                       sparse: bool = False, bucket: int = 0) -> CompressedDelta:
     """:func:`_compress` of ``a = e + (local − cached)`` with the memory ``e`` of ``mem`` as the encoders' flat input,
     then ``e = a − c`` (fl_sim_amd/feedback.py): the K-entry residual of a stacked record (after the batched encode
     when the message is deferred), the K-entry residual of a sparse record likewise (flc_ef_residual_sparse_round),
@@ -578,6 +732,15 @@ def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torc
         codec.ef_residual_round([d._record], [e], n, pipe[0], pipe[1])
         return d
     dc = dense_wire_codec(compressors) if wire else None
+    B = _bucket_of(compressors, bucket)
+    if B:  # bucketed: encoded at once from the memory's values, then the plain dense residual of the decoded record
+        if dc is not None:
+            d = _bucket_record(e, shapes, n, compressors[0], dc, B, dev)
+        else:
+            with _bucketed(compressors[0], B):
+                d = CompressedDelta(shapes, dev, n, flat=compressors[0].compressVector(e))
+        codec.ef_residual_dense(e, d.flat())
+        return d
     if dc is not None:  # the message carries the record; the memory takes a − decode(record) (these quantizers are
         # unbiased: the plain dense residual) — from the round's batched encode itself with EF_DENSE_DEFER on
         if (EF_DENSE_DEFER and DEFER_ENCODE and n <= _DEFER_EF_DENSE_MAX_N and dc[0] != FLC_WIRE_NATURAL
@@ -780,6 +943,58 @@ class _DenseBatch(_Batch):
                [it.counter for it in items], recs,
                [it.count for it in items] if fmt == FLC_Q_STANDARD_DITHER else None)
         return rows
+
+
+# Deferred bucket records (philox mode, `wire` on, a bucket size, the device norms, no error feedback): the messages
+# wait like the dense ones and one flc_bucket_encode_round — one launch per 64 messages, each message with its own
+# (seed, counter), record and count slot — writes the round's records, bit-identical to the per-message
+# flc_bucket_encode.  The same switch (FLC_DEFER_ENCODE) and pending bounds; deferred_bucket_stats() counts them apart.
+_DEFER_BUCKET_MAX_N = 1 << 20
+_BUCKET_STATS = {"batches": 0, "messages": 0}
+
+
+def deferred_bucket_stats(reset: bool = False) -> dict:
+    """:func:`deferred_stats` for the bucket records' batched encodes (flc_bucket_encode_round), counted apart."""
+    return _read_stats(_BUCKET_STATS, reset)
+
+
+class _BucketBatch(_Batch):
+    """The waiting bucket-record messages of one (device, "bucket", n, format, levels, bits, bucket, norm_p); an item's
+    count slot and compressor are None for natural dithering."""
+
+    stats = _BUCKET_STATS
+
+    def _encode_rows(self, items, dev):
+        _, _, n, fmt, levels, bits, B, pk = self.key
+        stride, _ = codec.bucket_wire_layout(n, fmt, bits, B)
+        recs = torch.empty(len(items), stride, dtype=torch.uint8, device=dev)
+        rows = recs.unbind(0)
+        codec.bucket_encode_round([it.flat for it in items], fmt, levels, bits, B, pk, [it.seed for it in items],
+                                  [it.counter for it in items], rows,
+                                  [it.count for it in items] if fmt == FLC_Q_STANDARD_DITHER else None)
+        return rows
+
+
+def _defer_bucket(x: torch.Tensor, shapes, n: int, comp: Compressor, dc: Tuple[int, int, int], B: int,
+                  dev) -> Optional[CompressedDelta]:
+    """The bucket-record message of the flat vector ``x`` (a snapshot) joins the round's batched encode; the Philox
+    stream and the send statistics advance here exactly as :func:`_bucket_record` advances them.  None (nothing
+    advanced: the immediate path takes the message) outside philox mode with the device norm of p = inf or 2."""
+    fmt, s, bits = dc
+    if comp.rng_mode != "philox" or comp._wants_host_norm(device_input=True):
+        return None
+    pk = _norm_kind(comp.p)
+    if pk is None or x.dtype != torch.float32 or x.device != dev:
+        return None
+    x = codec._dev_f32(x).reshape(-1)
+    std = fmt == FLC_Q_STANDARD_DITHER
+    st = torch.cuda.current_stream(dev)
+    cnt = comp._count_slot(dev, st) if std else None  # (before the batch is looked up, as in _defer)
+    b = _waiting(_BucketBatch, (dev.index, "bucket", n, fmt, s, bits, B, pk))
+    seed, ctr = comp.philox.next()
+    d = CompressedDelta(shapes, dev, n, levels=s, batch=b, format=fmt, bits=bits, bucket=B)
+    _bucket_stats(comp, n, B, std, cnt)
+    return _enqueue(b, _Item(d, x, seed, ctr, cnt, comp if std else None, st, st.cuda_stream, None))
 
 
 # Deferred natural-compressor records (philox mode, `wire` on, the natural compressor's uint16 wire), behind
@@ -1044,7 +1259,7 @@ def _stacked(ls, gs, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compres
     return CompressedDelta(shapes, dev, n, record=rec, k=K, levels=s)
 
 
-_RECORD_KINDS = ("stacked", "quant", "natural", "sparse")
+_RECORD_KINDS = ("stacked", "quant", "natural", "sparse", "bucket")
 
 
 def _round_deltas(messages: Sequence, key: str, kinds: Tuple[str, ...]) -> Optional[List[CompressedDelta]]:
@@ -1109,15 +1324,18 @@ def _entries(infix: str, *accessors) -> _Entries:
 _STACKED = _entries("", codec._pyrecs, codec._pygrecs, codec._pygroups)
 _SPARSE = _entries("sparse_", codec._pysrecs, codec._pygsrecs, None)
 _DENSE = _entries("dense_", codec._pydrecs, codec._pygdrecs, None)
+_BUCKET = _entries("bucket_", lambda: None, lambda: None, None)  # (the C entries; no one-call _flcfold form)
 _MIXED = _entries("mixed_", codec._pymrecs, None, None)  # (a mixed_round: every record by its own descriptor)
 
 
 def _record_entries(d0: CompressedDelta) -> Tuple[tuple, _Entries]:
     """(shape, entries) of a uniform round of ``d0``'s records — the one place that knows a kind's entry points.
     ``shape`` is what every entry of the kind takes after the record count: (n, k, levels) of stacked records, (n, k)
-    of sparse ones, (n, format, levels, bits) of dense ones."""
+    of sparse ones, (n, format, levels, bits) of dense ones, (n, format, levels, bits, bucket) of bucket ones."""
     if d0.kind == "sparse":
         return (d0.n, d0.k), _SPARSE
+    if d0.kind == "bucket":
+        return (d0.n, d0.format, d0.levels, d0.bits, d0.bucket), _BUCKET
     if d0.kind in ("quant", "natural"):
         return (d0.n, d0.format, d0.levels, d0.bits), _DENSE
     return (d0.n, d0.k, d0.levels), _STACKED
@@ -1167,7 +1385,7 @@ def mixed_round(messages: Sequence, key: str = "delta_parameters") -> Optional[L
             return None
         ds.append(d)
     d0 = ds[0]
-    if any(d.n != d0.n for d in ds) or all(d.kind == "dense" for d in ds):
+    if any(d.n != d0.n for d in ds) or all(d.kind in ("dense", "bucket") for d in ds):
         return None
     if all(d.codec_key == d0.codec_key for d in ds):
         return None
@@ -1185,6 +1403,8 @@ def _mixed_tables(deltas: Sequence[CompressedDelta], dev: torch.device, records=
     for i, d in enumerate(deltas):
         if d.kind == "dense":
             t, desc = d._flat, (_REC_FLAT, 0, 0, 0, 0)
+        elif d.kind == "bucket":  # (not in the mixed fold's descriptor tables: read as its decoded vector)
+            t, desc = d.flat(), (_REC_FLAT, 0, 0, 0, 0)
         else:
             t = d.record
             desc = ((_REC_STACKED, d.k, 0, d.levels, 0) if d.kind == "stacked" else
@@ -1414,6 +1634,15 @@ def _wire_records(node) -> bool:
     return bool(v)
 
 
+def _quant_bucket(node) -> int:
+    """``quant_bucket`` looked up on the client, then on its config (as ``wire_records`` is); absent or 0: the
+    dithering quantizers scale the whole vector by one norm (or by their own ``Compressor.bucket``)."""
+    v = getattr(node, "quant_bucket", None)
+    if v is None:
+        v = getattr(getattr(node, "config", None), "quant_bucket", None)
+    return int(v or 0)
+
+
 def _sparse_records(node) -> bool:
     """``sparse_records`` looked up on the client, then on its config (as ``wire_records`` is); absent or false: the
     top-k and rand-k compressors send their decoded vectors."""
@@ -1437,7 +1666,7 @@ class CompressedFedOptClientMixin(ErrorFeedbackClientMixin):
         params = list(self.model.parameters())
         delta = compress_delta(params, self._cached_parameters, _compressors_of(self),
                                self._feedback_for("delta_parameters", params), wire=_wire_records(self),
-                               sparse=_sparse_records(self))
+                               sparse=_sparse_records(self), bucket=_quant_bucket(self))
         target._received_messages.append(
             client_message_class()(
                 **{
@@ -1468,13 +1697,13 @@ class CompressedSCAFFOLDClientMixin(ErrorFeedbackClientMixin):
         params = list(self.model.parameters())
         if cs:
             pd = compress_delta(params, self._cached_parameters, cs, self._feedback_for("parameters_delta", params),
-                                wire=_wire_records(self), sparse=_sparse_records(self))
+                                wire=_wire_records(self), sparse=_sparse_records(self), bucket=_quant_bucket(self))
         else:
             pd = [mp.detach().sub(cp) for mp, cp in zip(params, self._cached_parameters)]
         if ccs:
             ucvs = list(self._updated_control_variates)
             cd = compress_delta(ucvs, self._control_variates, ccs, self._feedback_for("control_variates_delta", ucvs),
-                                wire=_wire_records(self), sparse=_sparse_records(self))
+                                wire=_wire_records(self), sparse=_sparse_records(self), bucket=_quant_bucket(self))
         else:
             cd = [ucv.sub(cv) for ucv, cv in zip(self._updated_control_variates, self._control_variates)]
         target._received_messages.append(
@@ -1505,7 +1734,7 @@ class CompressedIFCAClientMixin(ErrorFeedbackClientMixin):
         params = list(self.model.parameters())
         delta = compress_delta(params, self._cached_parameters, _compressors_of(self),
                                self._feedback_for("delta_parameters", params), wire=_wire_records(self),
-                               sparse=_sparse_records(self))
+                               sparse=_sparse_records(self), bucket=_quant_bucket(self))
         target._received_messages.append(
             client_message_class()(
                 **{
@@ -1520,7 +1749,7 @@ class CompressedIFCAClientMixin(ErrorFeedbackClientMixin):
 
 
 def compress_message_gradients(message, compressors: Sequence[Compressor], feedback=None, wire: bool = False,
-                               sparse: bool = False) -> None:
+                               sparse: bool = False, bucket: int = 0) -> None:
     """Replace ``message["gradients"]`` (a list of tensors) with the :class:`CompressedDelta` made from them
     (:func:`compress_tensors`); no compressors, no gradients or gradients already compressed: the message as it is.
     ``feedback``: the client's error memory for the vector, or a callable that makes it from the gradient list (called
@@ -1530,7 +1759,7 @@ def compress_message_gradients(message, compressors: Sequence[Compressor], feedb
         return
     gs = list(gs)
     message["gradients"] = compress_tensors(gs, compressors, feedback(gs) if callable(feedback) else feedback, wire,
-                                            sparse)
+                                            sparse, bucket)
 
 
 class CompressedGradientsClientMixin(ErrorFeedbackClientMixin):
@@ -1556,4 +1785,4 @@ class CompressedGradientsClientMixin(ErrorFeedbackClientMixin):
         for m in target._received_messages[before if target._received_messages is received else 0:]:
             if isinstance(m, dict) and "gradients" in m:
                 compress_message_gradients(m, cs, lambda gs: self._feedback_for("gradients", gs), _wire_records(self),
-                                           _sparse_records(self))
+                                           _sparse_records(self), _quant_bucket(self))

@@ -92,13 +92,20 @@ def natural_levels(levels: int) -> np.ndarray:
 class Compressor:
     """MI355X-native drop-in for the reference ``Compressor`` (compressors.py:35-419)."""
 
+    bucket = 0  # (objects pickled before the attribute existed)
+
     def __init__(self, compressorName: str = "", rng: str = "compat", seed: int = 0, extended_levels: bool = False,
-                 norm: str = "auto"):
+                 norm: str = "auto", bucket: int = 0):
         if rng not in ("compat", "philox"):
             raise ValueError("rng must be 'compat' or 'philox'")
         if norm not in ("auto", "device", "reference"):
             raise ValueError("norm must be 'auto', 'device' or 'reference'")
+        if bucket and bucket not in codec.BUCKET_SIZES:
+            raise ValueError(f"bucket must be 0 or a power of two in [64, 4096] (got {bucket})")
         self.norm_mode = norm
+        # bucketed dithering: 0 = the whole vector under one norm (the reference's literal compressVector); B = the
+        # float32 dithering types quantize every B consecutive elements under that bucket's own norm
+        self.bucket = int(bucket)
         # extension: standard dithering with 11..127 levels (8-bit codes); off by default, where such level
         # counts fail the reference's assertion exactly as they do there
         self.extended_levels = bool(extended_levels)
@@ -426,6 +433,9 @@ class Compressor:
 
     def _reference_norm(self, arr: np.ndarray):
         # compressors.py:332 / 372, evaluated as the reference evaluates it (numpy on this host), in x's dtype
+        if self.bucket and arr.dtype == np.float32:  # one norm per slice, as the slice-wise calls compute them
+            B = self.bucket
+            return np.array([np.linalg.norm(arr[lo:lo + B], self.p) for lo in range(0, arr.size, B)], dtype=np.float32)
         return arr.dtype.type(np.linalg.norm(arr, self.p))
 
     def _check_bracket(self, norm: float, consumers: int) -> None:
@@ -450,6 +460,8 @@ class Compressor:
         if x.dim() != 1:
             raise ValueError("compressVector expects a 1-D vector (d = max(x.shape) in the reference)")
         if x.dtype == torch.float64:
+            if self.bucket and (self.compressorType in _STD or self.compressorType in _NATD):
+                raise ValueError("bucketed dithering takes float32 vectors")
             return self._compress_device_f64(x, host_norm)
         d = x.numel()
         t = self.compressorType
@@ -507,6 +519,8 @@ class Compressor:
             if not 1 <= self.s <= 127:
                 raise ValueError(f"the device dithering codec takes 1..127 levels (8-bit codes); s = {self.s}")
             kind = FLC_Q_STANDARD_DITHER if t in _STD else FLC_Q_NATURAL_DITHER
+            if self.bucket:
+                return self._compress_bucketed(x, kind, host_norm)
             x2 = x.reshape(1, d)
             if host_norm is not None:  # the reference's np.linalg.norm (see the module docstring)
                 norms = torch.tensor([host_norm], dtype=torch.float32).to(x.device, non_blocking=True)
@@ -536,6 +550,65 @@ class Compressor:
                 self._finish(d, d * (1.0 + np.ceil(math.log2(self.s))) / den)
             return out
         raise ValueError(f"unknown compressor type {t}")
+
+    def _compress_bucketed(self, x: torch.Tensor, kind: int, host_norms) -> torch.Tensor:
+        """Bucketed dithering: compressVector (compressors.py:327-404) applied to the consecutive slices of
+        ``self.bucket`` elements in index order on this one object, the outputs concatenated.  Philox mode: one launch
+        that reads x once (flc_bucket_encode with out).  Compat mode: the existing entry points over the
+        ``[n // B, B]`` head and the tail, the interpreter's draws consumed in index order across buckets."""
+        B, n, t = self.bucket, x.numel(), self.compressorType
+        if B not in codec.BUCKET_SIZES:
+            raise ValueError(f"bucket must be 0 or a power of two in [64, 4096] (got {B})")
+        if t in _STD and self.vectorNormCompressor.compressorType != CompressorType.IDENTICAL:
+            raise ValueError("bucketed standard dithering takes an identical norm compressor")
+        nb = -(-n // B)
+        given = None
+        if host_norms is not None:
+            given = torch.from_numpy(np.ascontiguousarray(host_norms, dtype=np.float32)).to(x.device)
+        seed, ctr = self.philox.next()  # (one per vector)
+        if self.rng_mode == "philox":
+            _, nnz_t, out = codec.bucket_encode(x, kind, self.s, B, self.p, seed, ctr, norms=given,
+                                                want_nnz=(t in _STD), decode=True)
+            nnz = int(nnz_t.item()) if t in _STD else 0
+        else:
+            x = codec._dev_f32(x)
+            out = torch.empty(n, dtype=torch.float32, device=x.device)
+            nnz = 0
+            # pieces of whole buckets (at most 65535 rows per call), then the short tail as one row
+            pieces = [(lo, min(65535, n // B - lo // B), B) for lo in range(0, (n // B) * B, 65535 * B)]
+            if n % B:
+                pieces.append(((n // B) * B, 1, n % B))
+            for lo, rows, d in pieces:
+                x2 = x[lo:lo + rows * d].reshape(rows, d)
+                if x2.data_ptr() % 16:
+                    x2 = x2.clone()
+                norms = given[lo // B:lo // B + rows] if given is not None else codec.quant_norm(x2, self.p)
+                cnt = int(codec.count_consumers(x2, norms).item())
+                zero = (norms == 0).nonzero().reshape(-1).tolist()
+                for r in zero:  # (a p = 2 norm whose squares underflowed: the reference fails in that slice)
+                    self._check_bracket(0.0, int(torch.count_nonzero(x2[r]).item()))
+                compat_u = self._uniforms(cnt, x.device)
+                o2 = out[lo:lo + rows * d].reshape(rows, d)
+                pkt, dec = codec.quant_encode_decode(x2, kind, self.s, norms.contiguous(), seed, ctr, compat_u,
+                                                     want_nnz=(t in _STD), out=o2 if o2.data_ptr() % 16 == 0 else None)
+                if dec.data_ptr() != o2.data_ptr():
+                    o2.copy_(dec)
+                if t in _STD:
+                    nnz += int(pkt.nnz.sum().item())
+        den = 64.0 if t in (CompressorType.STANDARD_DITHERING_FP64, CompressorType.NATURAL_DITHERING_FP64) else 32.0
+        per = (1.0 + np.ceil(math.log2(self.s))) / den
+        if t in _STD:
+            # every slice sends its norm through the identical norm compressor (compressors.py:334-337): nb calls of
+            # one component each; then one `per` for every nonzero element (multiples of 1/64: the sums are exact)
+            nc = self.vectorNormCompressor
+            nc.last_input_advance = 1
+            nc.last_need_to_send_advance = 1
+            nc.total_input_components += nb
+            nc.really_need_to_send_components += nb
+            self._finish(n, nb + nnz * per)
+        else:
+            self._finish(n, n * per)
+        return out
 
     def _compress_device_f64(self, x: torch.Tensor, host_norm=None) -> torch.Tensor:
         """The float64 forms (f64.hip): the reference keeps every step in float64 when x is float64

@@ -22,6 +22,14 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// log2 of a bucket size of the bucketed dithering codec (a power of two in [64, 4096]); -1 for any other value
+inline int bucket_log2(int64_t bucket) {
+  if (bucket < 64 || bucket > 4096 || (bucket & (bucket - 1))) return -1;
+  int l = 6;
+  while (((int64_t)1 << l) < bucket) ++l;
+  return l;
+}
+
 // ---- persistent launches (runtime.cpp) --------------------------------------------------------------------------
 // The top-k encoders and the fused quantizer run one block per CU and hand data between blocks inside the launch, so
 // every block must be resident at once: one such launch per device at a time.  While every call comes on one stream,

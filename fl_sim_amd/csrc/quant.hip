@@ -18,6 +18,9 @@
 //                  a - decode(code) back in place (4 more bytes written per element, nothing decoded afterwards).
 //   quant_decode   v = fp32(fp32(lv) * sign) * norm, optionally fmaf-accumulated with a row weight.
 //                  algorithmic bytes: BITS/8 read + 4 written (+4 read when accumulating).
+//   bucket_*       bucketed dithering (flc_bucket_encode / _encode_round / _decode, at the end of this file): the
+//                  quantizer per bucket of B elements with that bucket's own norm, norm and encode in one launch that
+//                  reads x once.  algorithmic bytes: 4 + BITS/8 + 4/B per element (+ 4 with the decoded output).
 // Each thread owns GROUP = 8 consecutive elements (two 16-B loads, one 2..8-B code store): a wave
 // touches 2 KiB of x per step, fully coalesced.
 #include <hip/hip_runtime.h>
@@ -1245,6 +1248,299 @@ int flc_quant_decode(const uint8_t* codes, int64_t rows, int64_t d, int kind, in
     FLC_DEC(1, 2);
   }
 #undef FLC_DEC
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Bucketed dithering (flc_bucket_*): the vector is quantized per bucket of B consecutive elements (B a power of two,
+// 64..4096), each bucket with its own norm — compressVector (compressors.py:327-404) on the slices x[0:B], x[B:2B], ...
+// One launch, one read of x.  A 512-thread block owns 4096 consecutive elements (the largest bucket), thread t the group
+// of 8 at (block * 512 + t) * 8, loaded once and kept in registers: a bucket is B / 8 consecutive lanes.
+//   B <= 512   the bucket's lanes sit inside one wave: an xor butterfly over min(B / 8, 64) lanes (every lane of the
+//              bucket gets the result; the sub-wave groups of one wave reduce side by side).
+//   B >= 1024  B / 512 consecutive waves: each wave's butterfly, one LDS word per wave, and every thread folds its
+//              bucket's waves in wave order after one barrier.
+// p = inf is the max of the |x| bits (exact in any order).  p = 2: each lane's fp64 fma chain over its 8 elements in
+// index order from 0, the butterfly (xor 1, 2, 4, ...: a + b on both partners, so all lanes agree), then the waves in
+// order — a function of B and the position in the bucket only.  Elements past n count as +0.  The level decision is
+// philox_group_encode with d = B (a group of 8 never crosses a bucket), element e on Philox word e & 3 of group e >> 2
+// of the whole message.  Grid (blocks, messages): the message table travels in the kernel arguments as in the round
+// encode above; flc_bucket_encode is a table of one.
+// ------------------------------------------------------------------------------------------------
+namespace flc {
+namespace {
+
+constexpr int kBT = 512;                    // threads per block
+constexpr int kBNW = kBT / kWave;           // waves per block
+constexpr int kBSpan = kBT * kGroup;        // elements per block = the largest bucket
+static_assert(kBSpan == 4096, "bucket_log2's largest bucket is one block's span");
+
+struct BucketMsg {
+  const float* x;
+  uint8_t* codes;
+  float* norms;               // [ceil(n / B)]
+  unsigned long long* count;  // nonzero elements of the message, added to (nullptr: not counted)
+  uint64_t seed, counter;
+};
+struct BucketTable {
+  BucketMsg m[kRoundMsgs];
+};
+static_assert(sizeof(BucketTable) <= 3072, "the table and the scalars fit the 4 KB kernel argument segment");
+
+template <int KIND, int BITS, bool DEC>
+__global__ __launch_bounds__(kBT) void bucket_encode_kernel(BucketTable tab, int64_t n, int logb, int norm_p, int given,
+                                                            int s, double step, float* __restrict__ out) {
+  __shared__ unsigned long long s_red[kBNW];
+  __shared__ unsigned long long s_nnz;
+  const BucketMsg& m = tab.m[blockIdx.y];
+  const int64_t e0 = ((int64_t)blockIdx.x * kBT + threadIdx.x) * kGroup;
+  const int valid = e0 >= n ? 0 : (n - e0 < kGroup ? (int)(n - e0) : kGroup);
+  const int wave = threadIdx.x >> 6;
+  const int lanes = 1 << (logb - 3);  // lanes per bucket
+  const bool count = m.count != nullptr;
+  if (count && threadIdx.x == 0) s_nnz = 0ull;
+  float v[kGroup];
+  load_group(m.x, e0, valid, v);  // (lanes past n hold +0: they take part in the reductions and barriers)
+
+  float nrm;
+  if (given) {
+    nrm = valid ? m.norms[e0 >> logb] : 0.0f;
+  } else {
+    const int width = lanes < kWave ? lanes : kWave;
+    unsigned long long part;
+    if (norm_p == FLC_NORM_INF) {
+      uint32_t mx = 0;
+#pragma unroll
+      for (int j = 0; j < kGroup; ++j) {
+        const uint32_t a = __float_as_uint(v[j]) & 0x7fffffffu;  // |v| bits; NaN > inf > finite (norm_part's rule)
+        mx = a > mx ? a : mx;
+      }
+      for (int o = 1; o < width; o <<= 1) {
+        const uint32_t t = (uint32_t)__shfl_xor((int)mx, o, kWave);
+        mx = t > mx ? t : mx;
+      }
+      part = mx;
+    } else {
+      double ss = 0.0;
+#pragma unroll
+      for (int j = 0; j < kGroup; ++j) {
+        const double dv = (double)v[j];
+        ss = fma(dv, dv, ss);
+      }
+      for (int o = 1; o < width; o <<= 1) ss += __shfl_xor(ss, o, kWave);
+      part = (unsigned long long)__double_as_longlong(ss);
+    }
+    if (lanes > kWave) {  // (uniform: a kernel argument)
+      if ((threadIdx.x & (kWave - 1)) == 0) s_red[wave] = part;
+      __syncthreads();
+      const int nw = lanes >> 6, w0 = wave & ~(nw - 1);
+      if (norm_p == FLC_NORM_INF) {
+        uint32_t r = 0;
+        for (int w = 0; w < nw; ++w) r = (uint32_t)s_red[w0 + w] > r ? (uint32_t)s_red[w0 + w] : r;
+        part = r;
+      } else {
+        double r = 0.0;
+        for (int w = 0; w < nw; ++w) r += __longlong_as_double((long long)s_red[w0 + w]);
+        part = (unsigned long long)__double_as_longlong(r);
+      }
+    }
+    nrm = norm_p == FLC_NORM_INF ? __uint_as_float((uint32_t)part)
+                                 : (float)sqrt(__longlong_as_double((long long)part));
+    if (valid && (e0 & (((int64_t)1 << logb) - 1)) == 0) m.norms[e0 >> logb] = nrm;
+  }
+  if (count) __syncthreads();  // (uniform: the message's; s_nnz is zero before any wave adds)
+
+  if (valid) {
+    uint32_t wd[kGroup];
+    group_words(e0, m.seed, m.counter, wd);
+    philox_group_encode<KIND, BITS, DEC ? kEncDecode : kEncOnly>(
+        v, wd, e0, valid, (int64_t)1 << logb, s, step, m.codes, out, false, [&](int64_t) { return nrm; },
+        [](int64_t, int) {});
+  }
+  if (count) {
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < kGroup; ++j) cnt += v[j] != 0.0f;
+    cnt = wave_sum(cnt);
+    if ((threadIdx.x & (kWave - 1)) == 0 && cnt) atomicAdd(&s_nnz, (unsigned long long)cnt);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_nnz != 0) atomicAdd(m.count, s_nnz);
+  }
+}
+
+// v = fp32(fp32(level) * sign) * norm[e >> logb]; out = acc ? fmaf(w, v, out) : w * v  (w = 1: v itself)
+template <int KIND, int BITS, bool ACC>
+__global__ __launch_bounds__(kThreads) void bucket_decode_kernel(const uint8_t* __restrict__ codes, int64_t n, int logb,
+                                                                 int s, double step, const float* __restrict__ norms,
+                                                                 float w, float* __restrict__ out) {
+  const int64_t ngroups = (n + kGroup - 1) / kGroup;
+  for (int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * kThreads) {
+    const int64_t e0 = g * kGroup;
+    const int valid = n - e0 < kGroup ? (int)(n - e0) : kGroup;
+    const float nrm = norms[e0 >> logb];  // (a group of 8 lies in one bucket)
+    const uint64_t packed = load_codes<BITS>(codes, e0, valid);
+    float o[kGroup];
+#pragma unroll
+    for (int j = 0; j < kGroup; ++j)
+      o[j] = dequant<KIND, BITS>((uint32_t)(packed >> (j * BITS)) & ((1u << BITS) - 1u), nrm, s, step);
+    if (ACC) {
+      float prev[kGroup];
+      load_group(out, e0, valid, prev);
+#pragma unroll
+      for (int j = 0; j < kGroup; ++j) o[j] = fmaf(w, o[j], prev[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < kGroup; ++j) o[j] = w * o[j];
+    }
+    if (valid == kGroup) {
+      *reinterpret_cast<float4*>(out + e0) = make_float4(o[0], o[1], o[2], o[3]);
+      *reinterpret_cast<float4*>(out + e0 + 4) = make_float4(o[4], o[5], o[6], o[7]);
+    } else {
+      for (int j = 0; j < valid; ++j) out[e0 + j] = o[j];
+    }
+  }
+}
+
+template <int KIND, int BITS, bool DEC>
+int launch_bucket(const BucketTable& tab, int n_msgs, int64_t n, int logb, int norm_p, int given, int levels,
+                  float* out, hipStream_t st) {
+  const unsigned nb1 = (unsigned)cdiv(n, kBSpan);
+  FLC_LAUNCH(DEC ? "bucket_encode_decode" : "bucket_encode", (bucket_encode_kernel<KIND, BITS, DEC>),
+             dim3(nb1, (unsigned)n_msgs), dim3(kBT), 0, st, tab, n, logb, norm_p, given, levels, level_step(levels),
+             out);
+  return FLC_OK;
+}
+
+int bucket_dispatch(const BucketTable& tab, int n_msgs, int64_t n, int logb, int kind, int levels, int bits, int norm_p,
+                    int given, float* out, hipStream_t st) {
+#define FLC_BKT(K, B)                                                                                \
+  return out ? launch_bucket<K, B, true>(tab, n_msgs, n, logb, norm_p, given, levels, out, st)       \
+             : launch_bucket<K, B, false>(tab, n_msgs, n, logb, norm_p, given, levels, out, st)
+  if (kind == FLC_Q_STANDARD_DITHER) {
+    if (bits == 8) FLC_BKT(0, 8);
+    if (bits == 4) FLC_BKT(0, 4);
+    FLC_BKT(0, 2);
+  } else {
+    if (bits == 8) FLC_BKT(1, 8);
+    if (bits == 4) FLC_BKT(1, 4);
+    FLC_BKT(1, 2);
+  }
+#undef FLC_BKT
+}
+
+int check_bucket_args(const char* fn, int64_t n, int kind, int levels, int bits, int64_t bucket, int norm_p) {
+  if (n < 1 || n >= (int64_t)1 << 31) return fail(FLC_EINVAL, "%s: n must be in [1, 2^31)", fn);
+  if (bucket_log2(bucket) < 0)
+    return fail(FLC_EINVAL, "%s: bucket %lld is not a power of two in [64, 4096]", fn, (long long)bucket);
+  if (norm_p != FLC_NORM_INF && norm_p != FLC_NORM_L2) return fail(FLC_EINVAL, "%s: p must be inf(0) or 2", fn);
+  return check_quant_args(kind, levels, bits);
+}
+
+// the count slots are added to by the kernel: zero them first, one memset per run of consecutive slots
+int zero_counts(int64_t* const* counts, int n_msgs, hipStream_t st) {
+  for (int c = 0; c < n_msgs;) {
+    int e = c + 1;
+    while (e < n_msgs && counts[e] == counts[e - 1] + 1) ++e;
+    FLC_CHECK_HIP(hipMemsetAsync(counts[c], 0, (size_t)(e - c) * sizeof(int64_t), st));
+    c = e;
+  }
+  return FLC_OK;
+}
+
+}  // namespace
+}  // namespace flc
+
+extern "C" {
+
+size_t flc_bucket_wire_layout(int64_t n, int format, int bits, int64_t bucket, int64_t* offsets) {
+  if (n < 1 || n >= (1ll << 31) || bucket_log2(bucket) < 0) return 0;
+  if ((format != FLC_Q_STANDARD_DITHER && format != FLC_Q_NATURAL_DITHER) || (bits != 2 && bits != 4 && bits != 8))
+    return 0;
+  const size_t nb = (size_t)cdiv(n, bucket);
+  const size_t codes = align_up(nb * sizeof(float), 16);
+  if (offsets) {
+    offsets[0] = 0;
+    offsets[1] = (int64_t)codes;
+  }
+  return align_up(codes + ((size_t)n * bits + 7) / 8, 256);
+}
+
+int flc_bucket_encode(const float* x, int64_t n, int kind, int levels, int bits, int64_t bucket, int norm_p,
+                      int norms_given, uint64_t seed, uint64_t counter, float* norms, uint8_t* codes, int64_t* nnz,
+                      float* out, void* stream) {
+  const char* fn = "flc_bucket_encode";
+  if (!x || !norms || !codes) return fail(FLC_EINVAL, "%s: null x, norms or codes", fn);
+  if (int rc = check_bucket_args(fn, n, kind, levels, bits, bucket, norm_p)) return rc;
+  if (!aligned16(x) || !aligned16(codes) || (out && !aligned16(out)))
+    return fail(FLC_EINVAL, "%s: x, codes and out must be 16-B aligned", fn);
+  hipStream_t st = as_stream(stream);
+  if (nnz) FLC_CHECK_HIP(hipMemsetAsync(nnz, 0, sizeof(int64_t), st));
+  BucketTable tab{};
+  tab.m[0] = BucketMsg{x, codes, norms, reinterpret_cast<unsigned long long*>(nnz), seed, counter};
+  return bucket_dispatch(tab, 1, n, bucket_log2(bucket), kind, levels, bits, norm_p, norms_given != 0, out, st);
+}
+
+int flc_bucket_encode_round(const float* const* xs, int n_msgs, int64_t n, int kind, int levels, int bits,
+                            int64_t bucket, int norm_p, int norms_given, const uint64_t* seeds,
+                            const uint64_t* counters, float* const* norms, uint8_t* const* codes,
+                            int64_t* const* counts, void* stream) {
+  const char* fn = "flc_bucket_encode_round";
+  if (!xs || !seeds || !counters || !codes || !norms) return fail(FLC_EINVAL, "%s: null table", fn);
+  if (n_msgs < 1) return fail(FLC_EINVAL, "%s: n_msgs %d < 1", fn, n_msgs);
+  if (int rc = check_bucket_args(fn, n, kind, levels, bits, bucket, norm_p)) return rc;
+  for (int c = 0; c < n_msgs; ++c) {
+    if (!xs[c] || !codes[c] || !norms[c] || (counts && !counts[c]))
+      return fail(FLC_EINVAL, "%s: null entry for message %d", fn, c);
+    if (!aligned16(xs[c]) || !aligned16(codes[c]))
+      return fail(FLC_EINVAL, "%s: xs[%d] and codes[%d] must be 16-B aligned", fn, c, c);
+  }
+  hipStream_t st = as_stream(stream);
+  if (counts)
+    if (int rc = zero_counts(counts, n_msgs, st)) return rc;
+  const int logb = bucket_log2(bucket);
+  for (int c0 = 0; c0 < n_msgs; c0 += kRoundMsgs) {
+    const int m = std::min(n_msgs - c0, kRoundMsgs);
+    BucketTable tab{};
+    for (int i = 0; i < m; ++i)
+      tab.m[i] = BucketMsg{xs[c0 + i], codes[c0 + i], norms[c0 + i],
+                           counts ? reinterpret_cast<unsigned long long*>(counts[c0 + i]) : nullptr, seeds[c0 + i],
+                           counters[c0 + i]};
+    if (int rc = bucket_dispatch(tab, m, n, logb, kind, levels, bits, norm_p, norms_given != 0, nullptr, st)) return rc;
+  }
+  return FLC_OK;
+}
+
+int flc_bucket_decode(const uint8_t* codes, int64_t n, int kind, int levels, int bits, int64_t bucket,
+                      const float* norms, float weight, int accumulate, float* out, void* stream) {
+  const char* fn = "flc_bucket_decode";
+  if (!codes || !norms || !out) return fail(FLC_EINVAL, "%s: null codes, norms or out", fn);
+  if (int rc = check_bucket_args(fn, n, kind, levels, bits, bucket, FLC_NORM_INF)) return rc;
+  if (!aligned16(out) || !aligned16(codes)) return fail(FLC_EINVAL, "%s: out and codes must be 16-B aligned", fn);
+  hipStream_t st = as_stream(stream);
+  const int logb = bucket_log2(bucket);
+  const double step = level_step(levels);
+  const unsigned grid = (unsigned)std::min<int64_t>(cdiv(cdiv(n, kGroup), kThreads), 256 * 32);
+#define FLC_BDEC(K, B)                                                                                              \
+  do {                                                                                                              \
+    if (accumulate)                                                                                                 \
+      FLC_LAUNCH("bucket_decode", (bucket_decode_kernel<K, B, true>), dim3(grid), dim3(kThreads), 0, st, codes, n,  \
+                 logb, levels, step, norms, weight, out);                                                           \
+    else                                                                                                            \
+      FLC_LAUNCH("bucket_decode", (bucket_decode_kernel<K, B, false>), dim3(grid), dim3(kThreads), 0, st, codes, n, \
+                 logb, levels, step, norms, weight, out);                                                           \
+    return FLC_OK;                                                                                                  \
+  } while (0)
+  if (kind == FLC_Q_STANDARD_DITHER) {
+    if (bits == 8) FLC_BDEC(0, 8);
+    if (bits == 4) FLC_BDEC(0, 4);
+    FLC_BDEC(0, 2);
+  } else {
+    if (bits == 8) FLC_BDEC(1, 8);
+    if (bits == 4) FLC_BDEC(1, 4);
+    FLC_BDEC(1, 2);
+  }
+#undef FLC_BDEC
 }
 
 }  // extern "C"

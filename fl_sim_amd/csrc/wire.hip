@@ -633,7 +633,15 @@ constexpr long long kDenseNorm = 0, kDenseCodes = 16;
 struct DenseCodec {
   int format, levels, bits;
   int64_t n;
+  int logb = 0;  // bucket records (flc_bucket_wire_layout): log2 of the bucket size; 0: one norm for the record
 };
+
+// Bucket records: [0, 4 nb) the nb = ceil(n / B) fp32 norms, then the same code stream from the next 16-B boundary.
+// The fold reads the norm of (record, e >> log2 B) per quad run of a lane: for B >= 256 the 64 lanes of a run (256
+// consecutive elements) read one address, below that a lane's own bucket's.
+long long bucket_codes_offset(int64_t n, int logb) {
+  return (long long)align_up((size_t)cdiv(n, (int64_t)1 << logb) * sizeof(float), 16);
+}
 
 size_t dense_wire_size(int64_t n, int format, int bits) {
   const size_t code_bytes = format == kFmtNatural ? 2 * (size_t)n : ((size_t)n * (size_t)bits + 7) / 8;
@@ -670,9 +678,11 @@ __device__ __forceinline__ uint32_t quad_code(const typename Quad<BITS>::type& q
 // loads per record and lane), then the ordered chain runs over them — a round of up to kBatch clients is one batch.
 // fp32(level value) comes from an LDS table of all 2^(BITS-1) level fields (dequant's (float)level_value, as
 // quant_fused_kernel's s_lvt), so a code decodes exactly as flc_quant_decode decodes it, whatever its level field.
-template <int KIND, int BITS, class IO>
+// BKT: bucket records — the norm of element e is norms[e >> logb], the codes start at codes_off.
+template <int KIND, int BITS, class IO, bool BKT = false>
 __global__ __launch_bounds__(kWave) void dense_fold_records_kernel(FoldArgs a, int nw_all, int s, double step,
-                                                                   int64_t n, int64_t tile0, IO io) {
+                                                                   int64_t n, int64_t tile0, IO io, int logb = 0,
+                                                                   long long codes_off = kDenseCodes) {
   typedef typename Quad<BITS>::type Q;
   constexpr int kLv = KIND == kFmtNatural ? 1 : (1 << (BITS - 1));
   constexpr int kBatch = BITS == 16 ? 8 : 16;
@@ -692,19 +702,27 @@ __global__ __launch_bounds__(kWave) void dense_fold_records_kernel(FoldArgs a, i
   io.load(t0, lane, acc);
   for (int c0 = 0; c0 < nw; c0 += kBatch) {
     Q cw[kBatch][4];
-    float nr[kBatch];
+    float nr[kBatch][BKT ? 4 : 1];
 #pragma unroll
     for (int i = 0; i < kBatch; ++i) {
-      nr[i] = 0.0f;
+#pragma unroll
+      for (int u = 0; u < (BKT ? 4 : 1); ++u) nr[i][u] = 0.0f;
 #pragma unroll
       for (int u = 0; u < 4; ++u) cw[i][u] = Q{};
       if (c0 + i < nw) {
         const uint8_t* __restrict__ rc = a.rec[rec0 + c0 + i];
-        if constexpr (KIND != kFmtNatural) nr[i] = *reinterpret_cast<const float*>(rc + kDenseNorm);
+        if constexpr (KIND != kFmtNatural && !BKT) nr[i][0] = *reinterpret_cast<const float*>(rc + kDenseNorm);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int64_t e = t0 + 4 * (int64_t)(lane + u * kWave);
-          if (e < n) cw[i][u] = load_quad<BITS>(rc + kDenseCodes, e);
+          if constexpr (BKT) {
+            if (e < n) {
+              nr[i][u] = reinterpret_cast<const float*>(rc)[e >> logb];
+              cw[i][u] = load_quad<BITS>(rc + codes_off, e);
+            }
+          } else {
+            if (e < n) cw[i][u] = load_quad<BITS>(rc + kDenseCodes, e);
+          }
         }
       }
     }
@@ -712,10 +730,10 @@ __global__ __launch_bounds__(kWave) void dense_fold_records_kernel(FoldArgs a, i
     for (int i = 0; i < kBatch; ++i) {
       if (c0 + i >= nw) continue;  // (uniform)
       const float wc = a.w[rec0 + c0 + i];
-      const float nrm = nr[i];
-      const bool regular = norm_regular(nrm);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
+        const float nrm = nr[i][BKT ? u : 0];
+        const bool regular = norm_regular(nrm);
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -745,9 +763,27 @@ int launch_dense_fold(const char* name, const DenseCodec& cd, dim3 grid, hipStre
 #define FLC_DF(K, B)                                                                                              \
   do {                                                                                                            \
     FLC_LAUNCH(name, (dense_fold_records_kernel<K, B, IO>), grid, dim3(kWave), 0, st, a, nw, cd.levels, step, cd.n, \
-               tile0, io);                                                                                        \
+               tile0, io, 0, kDenseCodes);                                                                        \
     return FLC_OK;                                                                                                \
   } while (0)
+  if (cd.logb) {  // bucket records (the dithering quantizers only)
+    const long long coff = bucket_codes_offset(cd.n, cd.logb);
+#define FLC_BF(K, B)                                                                                                \
+  do {                                                                                                              \
+    FLC_LAUNCH(name, (dense_fold_records_kernel<K, B, IO, true>), grid, dim3(kWave), 0, st, a, nw, cd.levels, step, \
+               cd.n, tile0, io, cd.logb, coff);                                                                     \
+    return FLC_OK;                                                                                                  \
+  } while (0)
+    if (cd.format == FLC_Q_STANDARD_DITHER) {
+      if (cd.bits == 8) FLC_BF(0, 8);
+      if (cd.bits == 4) FLC_BF(0, 4);
+      FLC_BF(0, 2);
+    }
+    if (cd.bits == 8) FLC_BF(1, 8);
+    if (cd.bits == 4) FLC_BF(1, 4);
+    FLC_BF(1, 2);
+#undef FLC_BF
+  }
   if (cd.format == kFmtNatural) FLC_DF(2, 16);
   if (cd.format == FLC_Q_STANDARD_DITHER) {
     if (cd.bits == 8) FLC_DF(0, 8);
@@ -1283,6 +1319,15 @@ struct RoundCodec {
     c.is_dense = true, c.dense = DenseCodec{format, levels, bits, n};
     return c;
   }
+  // bucket records (flc_bucket_wire_layout); bucket_bad: the size is not a power of two in [64, 4096] (check fails)
+  int64_t bucket_bad = 0;
+  static RoundCodec bucket_records(int64_t n, int format, int levels, int bits, int64_t bucket) {
+    RoundCodec c = dense_records(n, format, levels, bits);
+    const int l = bucket_log2(bucket);
+    if (l < 0) c.bucket_bad = bucket ? bucket : -1;
+    c.dense.logb = l < 0 ? 6 : l;
+    return c;
+  }
   static RoundCodec mixed(int64_t n, const MixedRound* mx) {
     RoundCodec c{n};
     c.mx = mx;
@@ -1292,12 +1337,19 @@ struct RoundCodec {
   // the codec's own argument rule (a mixed round's is check_mixed_round, run by its entry point before anything else)
   int check(const char* fn) const {
     if (mx) return FLC_OK;
+    if (is_dense && dense.logb) {
+      if (bucket_bad)
+        return fail(FLC_EINVAL, "%s: bucket %lld is not a power of two in [64, 4096]", fn, (long long)bucket_bad);
+      if (dense.format == kFmtNatural) return fail(FLC_EINVAL, "%s: unknown format %d", fn, dense.format);
+    }
     if (is_dense) return check_dense_format(fn, dense.format, dense.levels, dense.bits);
     return check_entry_codec(fn, kind, n, k, levels);
   }
   // bytes of one record of a uniform round (after check)
   size_t record_size() const {
     size_t need = 0;
+    if (is_dense && dense.logb)
+      return align_up((size_t)bucket_codes_offset(n, dense.logb) + ((size_t)n * (size_t)dense.bits + 7) / 8, 256);
     if (is_dense) return dense_wire_size(n, dense.format, dense.bits);
     record_layout(kind, n, k, &need);
     return need;
@@ -1521,6 +1573,15 @@ int flc_fedopt_fold_dense_records(const void* const* records, const float* weigh
                           v, sizes, n_tensors, beta0, opt, lr, beta2, tau, stream);
 }
 
+int flc_fedopt_fold_bucket_records(const void* const* records, const float* weights, int n_records, int64_t n,
+                                   int format, int levels, int bits, int64_t bucket, float* const* delta,
+                                   float* const* theta, float* const* v, const int64_t* sizes, int n_tensors,
+                                   float beta0, int opt, double lr, double beta2, double tau, void* stream) {
+  return fedopt_fold_impl("flc_fedopt_fold_bucket_records", "fedopt_fold_bucket_records",
+                          RoundCodec::bucket_records(n, format, levels, bits, bucket), records, weights, n_records,
+                          delta, theta, v, sizes, n_tensors, beta0, opt, lr, beta2, tau, stream);
+}
+
 // The variance-reduced servers' folds (flc_avg_and_gradient_records, _sparse_records, _dense_records, _mixed_records),
 // as fedopt_fold_impl serves the FedOpt folds: one argument check and one chain of launches, the kernel by the round's
 // codec
@@ -1637,6 +1698,15 @@ int flc_avg_and_gradient_dense_records(float* const* params, float* const* grads
                                        int n_tensors, float inertia, void* stream) {
   return avg_and_gradient_impl("flc_avg_and_gradient_dense_records", "avg_and_gradient_dense_records",
                                RoundCodec::dense_records(n, format, levels, bits), params, grads, param_srcs,
+                               grad_records, w_params, w_grads, n_src, sizes, n_tensors, inertia, stream);
+}
+
+int flc_avg_and_gradient_bucket_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                        const void* const* grad_records, const float* w_params, const float* w_grads,
+                                        int n_src, int64_t n, int format, int levels, int bits, int64_t bucket,
+                                        const int64_t* sizes, int n_tensors, float inertia, void* stream) {
+  return avg_and_gradient_impl("flc_avg_and_gradient_bucket_records", "avg_and_gradient_bucket_records",
+                               RoundCodec::bucket_records(n, format, levels, bits, bucket), params, grads, param_srcs,
                                grad_records, w_params, w_grads, n_src, sizes, n_tensors, inertia, stream);
 }
 
@@ -1773,6 +1843,15 @@ int flc_fold_dense_record_groups(const void* const* records, const float* weight
                           dsts, n_groups, sizes, n_tensors, stream);
 }
 
+int flc_fold_bucket_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
+                                  int n_records, int64_t n, int format, int levels, int bits, int64_t bucket,
+                                  float* const* dsts, int n_groups, const int64_t* sizes, int n_tensors,
+                                  void* stream) {
+  return fold_groups_impl("flc_fold_bucket_record_groups", "fold_bucket_record_groups",
+                          RoundCodec::bucket_records(n, format, levels, bits, bucket), records, weights, group_of,
+                          n_records, dsts, n_groups, sizes, n_tensors, stream);
+}
+
 // The mixed entry points: the descriptor tables' own check first (check_mixed_round), then the uniform folds' impl
 int flc_fedopt_fold_mixed_records(const void* const* records, const float* weights, int n_records, int64_t n,
                                   const int32_t* kinds, const int64_t* ks, const int32_t* formats,
@@ -1829,6 +1908,14 @@ int flc_fold_dense_wires(const void* wires, int64_t stride, const int32_t* slots
                          int64_t n, int format, int levels, int bits, int accumulate, float* out, void* stream) {
   return fold_wires_impl("flc_fold_dense_wires", "fold_dense_wires", RoundCodec::dense_records(n, format, levels, bits),
                          wires, stride, slots, weights, n_wires, accumulate, out, stream);
+}
+
+int flc_fold_bucket_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
+                          int64_t n, int format, int levels, int bits, int64_t bucket, int accumulate, float* out,
+                          void* stream) {
+  return fold_wires_impl("flc_fold_bucket_wires", "fold_bucket_wires",
+                         RoundCodec::bucket_records(n, format, levels, bits, bucket), wires, stride, slots, weights,
+                         n_wires, accumulate, out, stream);
 }
 
 }  // extern "C"

@@ -155,6 +155,77 @@ int flc_quant_decode(const uint8_t* codes, int64_t rows, int64_t d, int kind, in
                      const float* norms, const float* row_weights, int accumulate, float* out,
                      void* stream);
 
+/* ------------------------------------------------------------------ bucketed dithering
+ * The dithering quantizers applied per bucket of `bucket` = B consecutive elements, each bucket with its own norm: the
+ * result on a vector of n elements is compressVector (compressors.py:327-365 standard, 367-404 natural dithering)
+ * applied to the slices x[0:B], x[B:2B], ..., x[(nb-1)B : n] in order, nb = ceil(n / B), the last slice possibly
+ * short.  B is a power of two in [64, 4096]; float32 only; kind, levels and bits as flc_quant_encode; norm_p is
+ * FLC_NORM_INF or FLC_NORM_L2.
+ *
+ * Record layout (flc_bucket_wire_layout): returns the record size (a multiple of 256 B; 0 for bad arguments: a format
+ * other than FLC_Q_STANDARD_DITHER / FLC_Q_NATURAL_DITHER — FLC_WIRE_NATURAL has no norm —, bits not 2, 4 or 8, a
+ * bucket outside the set above, n < 1 or n >= 2^31) and, if offsets != NULL, the byte offsets of offsets[0] the nb
+ * fp32 norms and offsets[1] the packed codes (16-B aligned, ceil(n * bits / 8) bytes, element i at bit offset
+ * i * bits: the quantizer codec's code stream; B * bits / 8 >= 16, so every bucket's codes start 16-B aligned).
+ * A pure host function. */
+size_t flc_bucket_wire_layout(int64_t n, int format, int bits, int64_t bucket, int64_t* offsets);
+/* encode one message in philox mode in ONE launch that reads x once (compressors.py:332 / 372 the norm, 339-365 /
+ * 376-404 the level choice, per slice): every bucket's norm is computed from values that stay in registers until the
+ * level decision.  p = inf: the exact max of the |x| bits, NaN-propagating (flc_quant_norm's); p = 2: fp32(sqrt(S)),
+ * S the fp64 sum of the bucket's squares in an order fixed by B and the position in the bucket (elements past n count
+ * as +0), never by the grid.  Element e uses Philox word e & 3 of counter group e >> 2, e the index in the whole
+ * message, through the tail bucket.  For n a multiple of B and p = inf the norms and codes are those of flc_quant_norm
+ * + flc_quant_encode on the [n / B, B] batch with the same (seed, counter).  norms_given != 0: the norms are read
+ * from `norms` instead (host-computed reference norms).  norms: nb floats; codes: ceil(n * bits / 8) bytes, 16-B
+ * aligned (a record's fields, or any buffers).  nnz (device int64, optional): the message's count of x != 0, zeroed in
+ * the stream by the call.  out (optional, n floats, 16-B aligned): the decoder's value of every code, from registers —
+ * compressVector's result.  A bucket whose norm is 0, +-inf or NaN encodes code 0 for x == 0 and code 1 otherwise,
+ * inside that bucket only.  Algorithmic bytes per element: 4 + bits / 8 + 4 / B (+ 4 with out).  No workspace, no
+ * status word, no grid-wide wait: capturable.  FLC_EINVAL (nothing launched): a null x, norms or codes, n < 1 or
+ * n >= 2^31, a bad bucket, levels not fitting bits, norm_p other than 0 or 2, x, codes or out not 16-B aligned. */
+int flc_bucket_encode(const float* x, int64_t n, int kind, int levels, int bits, int64_t bucket, int norm_p,
+                      int norms_given, uint64_t seed, uint64_t counter, float* norms, uint8_t* codes, int64_t* nnz,
+                      float* out, void* stream);
+/* flc_quant_encode_round's contract for bucket records: message c is xs[c] (n elements) with its own Philox
+ * (seeds[c], counters[c]), norms norms[c] (nb floats), codes codes[c] and, with counts != NULL, count *counts[c] (device
+ * int64, zeroed in the stream by the call: one memset per run of consecutive slots).  Bit-identical to
+ * flc_bucket_encode per message.  One ordinary launch per 64 messages over (block, message) with the message table in
+ * the kernel arguments; more messages chain launches.  All tables are HOST arrays of n_msgs entries.  FLC_EINVAL
+ * (nothing launched): flc_bucket_encode's cases per message, a null table or entry (counts itself may be NULL),
+ * n_msgs < 1. */
+int flc_bucket_encode_round(const float* const* xs, int n_msgs, int64_t n, int kind, int levels, int bits,
+                            int64_t bucket, int norm_p, int norms_given, const uint64_t* seeds,
+                            const uint64_t* counters, float* const* norms, uint8_t* const* codes,
+                            int64_t* const* counts, void* stream);
+/* decode (compressors.py:357 / 394 per slice): v = fp32(fp32(level_value) * sign) * norms[e / B];
+ * out = accumulate ? fmaf(weight, v, out) : weight * v  (weight 1: v itself).  FLC_EINVAL as flc_bucket_encode. */
+int flc_bucket_decode(const uint8_t* codes, int64_t n, int kind, int levels, int bits, int64_t bucket,
+                      const float* norms, float weight, int accumulate, float* out, void* stream);
+
+/* The folds over bucket records, the four forms every record codec has: flc_fold_dense_wires,
+ * flc_fedopt_fold_dense_records, flc_avg_and_gradient_dense_records and flc_fold_dense_record_groups (below) with the
+ * records laid out by flc_bucket_wire_layout(n, format, bits, bucket) and the norm of element e read from
+ * (record, e / bucket) — the server's weighted aggregation (nodes.py:1165-1180 / _fedopt.py:202-208) fused with the
+ * per-slice decode of compressors.py:357 / 394.  Each is bit-identical to decoding every record with flc_bucket_decode
+ * and running the dense entry point its counterpart names (flc_quant_decode(accumulate = 1) chains, flc_model_fold,
+ * flc_avg_and_gradients, flc_weighted_sum per group).  Arguments, chaining per 64 records and FLC_EINVAL cases as the
+ * dense forms, plus a bucket that is not a power of two in [64, 4096] and format FLC_WIRE_NATURAL (no norm). */
+int flc_fold_bucket_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
+                          int64_t n, int format, int levels, int bits, int64_t bucket, int accumulate, float* out,
+                          void* stream);
+int flc_fedopt_fold_bucket_records(const void* const* records, const float* weights, int n_records, int64_t n,
+                                   int format, int levels, int bits, int64_t bucket, float* const* delta,
+                                   float* const* theta, float* const* v, const int64_t* sizes, int n_tensors,
+                                   float beta0, int opt, double lr, double beta2, double tau, void* stream);
+int flc_avg_and_gradient_bucket_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                        const void* const* grad_records, const float* w_params, const float* w_grads,
+                                        int n_src, int64_t n, int format, int levels, int bits, int64_t bucket,
+                                        const int64_t* sizes, int n_tensors, float inertia, void* stream);
+int flc_fold_bucket_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
+                                  int n_records, int64_t n, int format, int levels, int bits, int64_t bucket,
+                                  float* const* dsts, int n_groups, const int64_t* sizes, int n_tensors,
+                                  void* stream);
+
 /* ------------------------------------------------------------------ natural compressor
  * (compressors.py:302-325).  Wire: one uint16 per element, 0 = zero, else sign << 15 | (e + 150)
  * for the chosen power of two 2^e, e in [-149, 127]. */
