@@ -172,6 +172,36 @@ SIGNATURES = {
         [c_void_p, c_int64, c_int64, c_int, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p, c_size_t, c_void_p],
     ),
+    # the selection-order forms (FLC_ORDER_*: 0 signed, 1 by magnitude): `int order` after k
+    "flc_topk_encode_tiled_ord": (
+        c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    ),
+    "flc_topk_encode_batch_ord": (
+        c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    ),
+    "flc_stacked_encode_tiled_ord": (
+        c_int,
+        [c_void_p, c_int64, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "flc_stacked_encode_delta_ord": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "flc_stacked_encode_round_ord": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "flc_stacked_encode_delta_round_ord": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "flc_topk_dense_f64_ord": (
+        c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    ),
     "flc_stacked_decode_tiled": (
         c_int,
         [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float, c_int, c_void_p, c_void_p, c_void_p],

@@ -647,30 +647,59 @@ def _after_encode(device: torch.device, kinds: Sequence[str] = _TOPK_KINDS) -> N
             raise _lib.FlcError(f"{what} lost co-residency or failed ({bits}); its output may be wrong")
 
 
+ORDER_SIGNED, ORDER_MAGNITUDE = 0, 1  # FLC_ORDER_* (include/flcodec.h)
+
+
+def _order(order) -> int:
+    """A select's order as FLC_ORDER_*: ``ORDER_SIGNED`` / ``"signed"`` (the reference's rule, compressors.py:293-296:
+    the k largest signed values) or ``ORDER_MAGNITUDE`` / ``"magnitude"`` (the k largest |x|, each kept value x's
+    own)."""
+    if isinstance(order, str):
+        if order not in ("signed", "magnitude"):
+            raise ValueError(f"order must be 'signed' or 'magnitude' (got {order!r})")
+        return ORDER_MAGNITUDE if order == "magnitude" else ORDER_SIGNED
+    o = int(order)
+    if o not in (ORDER_SIGNED, ORDER_MAGNITUDE):
+        raise ValueError(f"order must be ORDER_SIGNED or ORDER_MAGNITUDE (got {order!r})")
+    return o
+
+
+def _call_ord(name: str, order: int, k_pos: int, *args) -> None:
+    """``name`` in the signed order; otherwise its ``_ord`` form, which takes ``order`` after k (argument ``k_pos``)."""
+    if order == ORDER_SIGNED:
+        call(name, *args)
+    else:
+        call(name + "_ord", *args[:k_pos + 1], order, *args[k_pos + 1:])
+
+
 def _tiles(n: int, device: torch.device) -> torch.Tensor:
     """CSR tile pointers over FLC_TILE-output tiles (include/flcodec.h)."""
     return torch.empty((n + TILE - 1) // TILE + 1, dtype=torch.int32, device=device)
 
 
-def topk_encode(x: torch.Tensor, k: int, with_tiles: bool = False):
+def topk_encode(x: torch.Tensor, k: int, with_tiles: bool = False, order=ORDER_SIGNED):
     """Kept set of the reference Top-K (k largest signed values): (idx int32 ascending, val fp32), plus the
-    tile pointers of idx when ``with_tiles`` (emitted by the encoder, saving the decoder an index pass)."""
+    tile pointers of idx when ``with_tiles`` (emitted by the encoder, saving the decoder an index pass).
+    ``order=ORDER_MAGNITUDE``: the k largest |x| instead (:func:`_order`); ``val`` stays ``x[idx]``, signs included."""
+    order = _order(order)
     x = _dev_f32(x).reshape(-1)
     n = x.numel()
     idx = torch.empty(k, dtype=torch.int32, device=x.device)
     val = torch.empty(k, dtype=torch.float32, device=x.device)
     tiles = _tiles(n, x.device) if with_tiles else None
     ws = workspace(x.device, _ws_size(x.device, "flc_topk_workspace_size", n, k), "topk")
-    call("flc_topk_encode_tiled", _p(x), n, k, _p(idx), _p(val), _p(tiles), _p(ws), ws.numel(), _stream(x.device))
+    _call_ord("flc_topk_encode_tiled", order, 2, _p(x), n, k, _p(idx), _p(val), _p(tiles), _p(ws), ws.numel(),
+              _stream(x.device))
     _after_encode(x.device)
     return (idx, val, tiles) if with_tiles else (idx, val)
 
 
-def topk_encode_batch(xs: Sequence[torch.Tensor], k: int, with_tiles: bool = False):
+def topk_encode_batch(xs: Sequence[torch.Tensor], k: int, with_tiles: bool = False, order=ORDER_SIGNED):
     """The top-k of many clients' flat deltas (one size) in one launch (flc_topk_encode_batch): entry c equals
-    ``topk_encode(xs[c], k, with_tiles)``."""
+    ``topk_encode(xs[c], k, with_tiles, order)``."""
     import ctypes
 
+    order = _order(order)
     xs = [_dev_f32(x).reshape(-1) for x in xs]
     C = len(xs)
     if C == 0:
@@ -685,10 +714,11 @@ def topk_encode_batch(xs: Sequence[torch.Tensor], k: int, with_tiles: bool = Fal
     P = ctypes.c_void_p * C
     vp = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
     ws = workspace(dev, _ws_size(dev, "flc_topk_encode_batch_workspace_size", n, k, C), "topk_batch")
-    call("flc_topk_encode_batch", vp(P(*[x.data_ptr() for x in xs])), C, n, k,
-         vp(P(*[idx.data_ptr() + 4 * k * c for c in range(C)])), vp(P(*[val.data_ptr() + 4 * k * c for c in range(C)])),
-         vp(P(*[tiles.data_ptr() + 4 * ntl * c for c in range(C)])) if with_tiles else None, _p(ws), ws.numel(),
-         _stream(dev))
+    _call_ord("flc_topk_encode_batch", order, 3, vp(P(*[x.data_ptr() for x in xs])), C, n, k,
+              vp(P(*[idx.data_ptr() + 4 * k * c for c in range(C)])),
+              vp(P(*[val.data_ptr() + 4 * k * c for c in range(C)])),
+              vp(P(*[tiles.data_ptr() + 4 * ntl * c for c in range(C)])) if with_tiles else None, _p(ws), ws.numel(),
+              _stream(dev))
     _after_encode(dev)
     rows = zip(idx.unbind(0), val.unbind(0), tiles.unbind(0) if with_tiles else [None] * C)
     return [(i_, v_, t_) if with_tiles else (i_, v_) for i_, v_, t_ in rows]
@@ -801,10 +831,12 @@ def wire_packet(record: torch.Tensor, n: int, k: int, levels: int = 127) -> Stac
 
 def stacked_encode(x: torch.Tensor, k: int, levels: int = 127, seed: int = 0, counter: int = 0,
                    with_tiles: bool = True, wire: Optional[torch.Tensor] = None,
-                   out: Optional[StackedPacket] = None) -> StackedPacket:
+                   out: Optional[StackedPacket] = None, order=ORDER_SIGNED) -> StackedPacket:
     """Stacked top-k -> 8-bit dithering encode.  ``wire``: a packed wire record (see :func:`wire_packet`) to write
     the packet into; the returned packet's tensors are then views of it.  ``out``: a packet of the same (n, k) whose
-    tensors are overwritten (no allocation per call); it is returned."""
+    tensors are overwritten (no allocation per call); it is returned.  ``order``: the top-k stage's selection order
+    (:func:`_order`); the packet, its decode and every fold are the same either way."""
+    order = _order(order)
     x = _dev_f32(x).reshape(-1)
     n = x.numel()
     if out is not None:
@@ -822,8 +854,8 @@ def stacked_encode(x: torch.Tensor, k: int, levels: int = 127, seed: int = 0, co
         norm = torch.empty(1, dtype=torch.float32, device=x.device)
         tiles = _tiles(n, x.device) if with_tiles else None
     ws = workspace(x.device, _ws_size(x.device, "flc_topk_workspace_size", n, k), "topk")
-    call("flc_stacked_encode_tiled", _p(x), n, k, levels, seed, counter, None, _p(idx), _p(codes), _p(norm),
-         _p(tiles), _p(ws), ws.numel(), _stream(x.device))
+    _call_ord("flc_stacked_encode_tiled", order, 2, _p(x), n, k, levels, seed, counter, None, _p(idx), _p(codes),
+              _p(norm), _p(tiles), _p(ws), ws.numel(), _stream(x.device))
     _after_encode(x.device)
     return StackedPacket(idx, codes, norm, n, levels, tiles)
 
@@ -854,16 +886,18 @@ def _round_args(C: int, dev, counter: int, counters, counts):
 
 def stacked_encode_batch(xs: Sequence[torch.Tensor], k: int, levels: int = 127, seeds: Sequence[int] = (),
                          counter: int = 0, with_tiles: bool = True, wires=None, counters: Optional[Sequence[int]] = None,
-                         counts=None) -> Optional[Sequence[StackedPacket]]:
+                         counts=None, order=ORDER_SIGNED) -> Optional[Sequence[StackedPacket]]:
     """The stacked encode of many clients' flat deltas (all of one size) in one launch (flc_stacked_encode_batch):
     packet c equals ``stacked_encode(xs[c], k, levels, seeds[c], counter)`` bit for bit.  ``wires``: the packed wire
     records to write into — a ``[clients, >= stride]`` uint8 tensor (then nothing is returned: the records are the
     output) or a list of one record per client (the packets returned are views of them).  ``counters``: one Philox
     counter per client in place of ``counter``; ``counts``: a device int64 tensor ``[clients]`` (or a list of
     one-element ones) that receives each packet's number of kept entries with a nonzero (or NaN) value — either keyword
-    takes the call through flc_stacked_encode_round, whose encode makes the counts itself."""
+    takes the call through flc_stacked_encode_round, whose encode makes the counts itself, and so does
+    ``order=ORDER_MAGNITUDE`` (one order for the whole call, :func:`_order`)."""
     import ctypes
 
+    order = _order(order)
     C = len(xs)
     if C == 0:
         return []
@@ -910,28 +944,30 @@ def stacked_encode_batch(xs: Sequence[torch.Tensor], k: int, levels: int = 127, 
                    "tiles": P(*[tiles.data_ptr() + 4 * ntl * c for c in range(C)]) if with_tiles else None}
     ws = workspace(dev, _ws_size(dev, "flc_stacked_encode_batch_workspace_size", n, k, C), "topk_batch")
     vp = lambda a: None if a is None else ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
-    if counters is None and counts is None:
+    if counters is None and counts is None and order == ORDER_SIGNED:
         call("flc_stacked_encode_batch", vp(P(*xp)), C, n, k, levels,
              vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), counter, vp(ptr["idx"]), vp(ptr["codes"]),
              vp(ptr["norm"]), vp(ptr["tiles"]), _p(ws), ws.numel(), _stream(dev))
     else:
         ctr, cp = _round_args(C, dev, counter, counters, counts)
-        call("flc_stacked_encode_round", vp(P(*xp)), C, n, k, levels,
-             vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), vp(ctr), vp(ptr["idx"]), vp(ptr["codes"]),
-             vp(ptr["norm"]), vp(ptr["tiles"]), vp(cp), _p(ws), ws.numel(), _stream(dev))
+        _call_ord("flc_stacked_encode_round", order, 3, vp(P(*xp)), C, n, k, levels,
+                  vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), vp(ctr), vp(ptr["idx"]), vp(ptr["codes"]),
+                  vp(ptr["norm"]), vp(ptr["tiles"]), vp(cp), _p(ws), ws.numel(), _stream(dev))
     _after_encode(dev)
     return pks
 
 
 def stacked_encode_delta_batch(local_params: Sequence[Sequence[torch.Tensor]], global_params: Sequence[torch.Tensor],
                                k: int, levels: int = 127, seeds: Sequence[int] = (), counter: int = 0,
-                               counters: Optional[Sequence[int]] = None, counts=None) -> "PacketBatch":
+                               counters: Optional[Sequence[int]] = None, counts=None,
+                               order=ORDER_SIGNED) -> "PacketBatch":
     """The delta-fused stacked encode of a round's clients in one launch (flc_stacked_encode_delta_batch): client c's
     delta ``cat([l - g for l, g in zip(local_params[c], global_params)])`` (the global model shared by every client),
     packet c equal to ``stacked_encode_delta(local_params[c], global_params, k, levels, seeds[c], counter)``.
-    ``counters`` / ``counts``: as in :func:`stacked_encode_batch` (flc_stacked_encode_delta_round)."""
+    ``counters`` / ``counts`` / ``order``: as in :func:`stacked_encode_batch` (flc_stacked_encode_delta_round)."""
     import ctypes
 
+    order = _order(order)
     C = len(local_params)
     if C == 0:
         return []
@@ -959,31 +995,33 @@ def stacked_encode_delta_batch(local_params: Sequence[Sequence[torch.Tensor]], g
     P = ctypes.c_void_p
     vp = lambda a: ctypes.cast(a, P)  # noqa: E731
     ws = workspace(dev, _ws_size(dev, "flc_stacked_encode_delta_batch_workspace_size", n, k, C, m), "topk_batch")
-    if counters is None and counts is None:
+    if counters is None and counts is None and order == ORDER_SIGNED:
         name, ctr, cnt = "flc_stacked_encode_delta_batch", (counter,), ()
     else:
         ca, cp = _round_args(C, dev, counter, counters, counts)
         name, ctr, cnt = "flc_stacked_encode_delta_round", (vp(ca),), (None if cp is None else vp(cp),)
-    call(name, vp((P * (C * m))(*[t.data_ptr() for lp in ls for t in lp])),
-         vp((P * m)(*[t.data_ptr() for t in gs])), vp((ctypes.c_int64 * m)(*[t.numel() for t in gs])), m, C, k,
-         levels, vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), *ctr,
-         vp((P * C)(*[idx.data_ptr() + 4 * k * c for c in range(C)])),
-         vp((P * C)(*[codes.data_ptr() + kc * c for c in range(C)])),
-         vp((P * C)(*[norm.data_ptr() + 4 * c for c in range(C)])),
-         vp((P * C)(*[tiles.data_ptr() + 4 * ntl * c for c in range(C)])), *cnt, _p(ws), ws.numel(), _stream(dev))
+    _call_ord(name, order, 5, vp((P * (C * m))(*[t.data_ptr() for lp in ls for t in lp])),
+              vp((P * m)(*[t.data_ptr() for t in gs])), vp((ctypes.c_int64 * m)(*[t.numel() for t in gs])), m, C, k,
+              levels, vp((ctypes.c_uint64 * C)(*[int(s_) for s_ in seeds])), *ctr,
+              vp((P * C)(*[idx.data_ptr() + 4 * k * c for c in range(C)])),
+              vp((P * C)(*[codes.data_ptr() + kc * c for c in range(C)])),
+              vp((P * C)(*[norm.data_ptr() + 4 * c for c in range(C)])),
+              vp((P * C)(*[tiles.data_ptr() + 4 * ntl * c for c in range(C)])), *cnt, _p(ws), ws.numel(), _stream(dev))
     _after_encode(dev)
     return PacketBatch(idx, codes, norm, tiles, n, levels)
 
 
 def stacked_encode_delta(local_params: Sequence[torch.Tensor], global_params: Sequence[torch.Tensor], k: int,
                          levels: int = 127, seed: int = 0, counter: int = 0,
-                         wire: Optional[torch.Tensor] = None) -> StackedPacket:
+                         wire: Optional[torch.Tensor] = None, order=ORDER_SIGNED) -> StackedPacket:
     """The stacked encode of the client delta ``cat([l - g for l, g in zip(local, global)])`` with the delta formed in
     the encoder's read pass (flc_stacked_encode_delta): the flat delta is never written.  Same packet as
     ``stacked_encode(delta_flatten(local, global), ...)``.  ``wire``: a packed wire record to write into (the packet's
-    tensors are then views of it, see :func:`wire_packet`)."""
+    tensors are then views of it, see :func:`wire_packet`).  ``order``: as in :func:`stacked_encode` (by magnitude:
+    |local - global|)."""
     import ctypes
 
+    order = _order(order)
     ls = [t if (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 4 == 0) else t.contiguous().float()
           for t in local_params]
     gs = [t if (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 4 == 0) else t.contiguous().float()
@@ -1010,9 +1048,9 @@ def stacked_encode_delta(local_params: Sequence[torch.Tensor], global_params: Se
         norm = torch.empty(1, dtype=torch.float32, device=dev)
         tiles = _tiles(n, dev)
     ws = workspace(dev, _ws_size(dev, "flc_stacked_encode_delta_workspace_size", n, k, m), "topk")
-    call("flc_stacked_encode_delta", ctypes.cast(lp, ctypes.c_void_p), ctypes.cast(gp, ctypes.c_void_p),
-         ctypes.cast(sz, ctypes.c_void_p), m, k, levels, seed, counter, _p(idx), _p(codes), _p(norm), _p(tiles), _p(ws),
-         ws.numel(), _stream(dev))
+    _call_ord("flc_stacked_encode_delta", order, 4, ctypes.cast(lp, ctypes.c_void_p), ctypes.cast(gp, ctypes.c_void_p),
+              ctypes.cast(sz, ctypes.c_void_p), m, k, levels, seed, counter, _p(idx), _p(codes), _p(norm), _p(tiles),
+              _p(ws), ws.numel(), _stream(dev))
     _after_encode(dev)
     return StackedPacket(idx, codes, norm, n, levels, tiles)
 
@@ -1073,24 +1111,28 @@ def sparse_record_decode(record: torch.Tensor, n: int, k: int, out: Optional[tor
     return sparse_decode(idx, val, n, 1.0, out=out, weight=weight, accumulate=accumulate, tiles=tiles)
 
 
-def topk_encode_record(x: torch.Tensor, k: int, record: torch.Tensor) -> torch.Tensor:
-    """The top-k of the flat vector ``x`` written into the sparse record ``record`` (flc_topk_encode_tiled with the
-    three pointers inside it)."""
+def topk_encode_record(x: torch.Tensor, k: int, record: torch.Tensor, order=ORDER_SIGNED) -> torch.Tensor:
+    """The top-k of the flat vector ``x`` (``order``: as in :func:`topk_encode`) written into the sparse record
+    ``record`` (flc_topk_encode_tiled with the three pointers inside it)."""
+    order = _order(order)
     x = _dev_f32(x).reshape(-1)
     n = x.numel()
     idx, val, tiles = sparse_wire_views(record, n, k)
     ws = workspace(x.device, _ws_size(x.device, "flc_topk_workspace_size", n, k), "topk")
-    call("flc_topk_encode_tiled", _p(x), n, k, _p(idx), _p(val), _p(tiles), _p(ws), ws.numel(), _stream(x.device))
+    _call_ord("flc_topk_encode_tiled", order, 2, _p(x), n, k, _p(idx), _p(val), _p(tiles), _p(ws), ws.numel(),
+              _stream(x.device))
     _after_encode(x.device)
     return record
 
 
-def topk_encode_records(xs: Sequence[torch.Tensor], k: int, records: torch.Tensor) -> torch.Tensor:
+def topk_encode_records(xs: Sequence[torch.Tensor], k: int, records: torch.Tensor,
+                        order=ORDER_SIGNED) -> torch.Tensor:
     """A round's top-k messages in one call (flc_topk_encode_batch): row c of the ``[C, >= stride]`` uint8 block
     ``records`` (16-B rows) takes the sparse record of the flat fp32 vector ``xs[c]`` — all of one size on one device —
-    equal to ``topk_encode_record(xs[c], k, records[c])``."""
+    equal to ``topk_encode_record(xs[c], k, records[c], order)``."""
     import ctypes
 
+    order = _order(order)
     C = len(xs)
     if C == 0:
         return records
@@ -1111,9 +1153,9 @@ def topk_encode_records(xs: Sequence[torch.Tensor], k: int, records: torch.Tenso
     vp = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
     ws = workspace(dev, _ws_size(dev, "flc_topk_encode_batch_workspace_size", n, k, C), "topk_batch")
     with torch.cuda.device(dev):
-        call("flc_topk_encode_batch", vp(P(*xp)), C, n, k, vp(P(*[b + off["idx"] for b in bases])),
-             vp(P(*[b + off["val"] for b in bases])), vp(P(*[b + off["tiles"] for b in bases])), _p(ws), ws.numel(),
-             _stream(dev))
+        _call_ord("flc_topk_encode_batch", order, 3, vp(P(*xp)), C, n, k, vp(P(*[b + off["idx"] for b in bases])),
+                  vp(P(*[b + off["val"] for b in bases])), vp(P(*[b + off["tiles"] for b in bases])), _p(ws),
+                  ws.numel(), _stream(dev))
     _after_encode(dev)
     return records
 
@@ -1783,12 +1825,14 @@ def quant_decode_f64(codes: torch.Tensor, n: int, kind: int, levels: int, norm: 
     return out
 
 
-def topk_dense_f64(x: torch.Tensor, k: int) -> torch.Tensor:
-    """out = x on the k largest elements (ties: the highest indices), +0 elsewhere; 0 < k < n."""
+def topk_dense_f64(x: torch.Tensor, k: int, order=ORDER_SIGNED) -> torch.Tensor:
+    """out = x on the k largest elements (ties: the highest indices), +0 elsewhere; 0 < k < n.  ``order``: as in
+    :func:`topk_encode` (by magnitude: the k largest |x|)."""
+    order = _order(order)
     x = _dev_f64(x)
     out = torch.empty_like(x)
     ws = _ws64(x, k)
-    call("flc_topk_dense_f64", _p(x), x.numel(), int(k), _p(out), _p(ws), ws.numel(), _stream(x.device))
+    _call_ord("flc_topk_dense_f64", order, 2, _p(x), x.numel(), int(k), _p(out), _p(ws), ws.numel(), _stream(x.device))
     _after_encode(x.device, ("f64",))
     return out
 

@@ -260,6 +260,19 @@ def stacked_pipeline(compressors: Sequence[Compressor]) -> Optional[Tuple[int, i
     return int(tk.K), int(sd.s)
 
 
+def pipeline_order(compressors: Sequence[Compressor]) -> int:
+    """The selection order (``codec.ORDER_*``) a compressor list's top-k stage runs in: ``codec.ORDER_MAGNITUDE`` when
+    its first compressor is a top-k made with ``magnitude=True`` — alone, or heading the stacked pipeline of
+    :func:`stacked_pipeline` — else ``codec.ORDER_SIGNED`` (the reference's rule, compressors.py:293-296).  The order
+    changes which entries a record holds, never the record: layouts, folds and residuals are the same."""
+    if not compressors:
+        return codec.ORDER_SIGNED
+    tk = compressors[0]
+    if isinstance(tk, Compressor) and tk.compressorType == CompressorType.TOPK_COMPRESSOR and tk.magnitude:
+        return codec.ORDER_MAGNITUDE
+    return codec.ORDER_SIGNED
+
+
 def _ptrs(ts: Sequence[torch.Tensor]):
     return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
@@ -592,7 +605,7 @@ def _sparse_record(x: torch.Tensor, shapes, n: int, comp: Compressor, K: int, de
     stride, _ = codec.sparse_wire_layout(n, K)
     rec = torch.empty(stride, dtype=torch.uint8, device=dev)
     if comp.compressorType == CompressorType.TOPK_COMPRESSOR:
-        codec.topk_encode_record(x, K, rec)  # compressors.py:293-296
+        codec.topk_encode_record(x, K, rec, order=comp.order)  # compressors.py:293-296 (or by magnitude)
         comp._finish(n, comp.K)
         return CompressedDelta(shapes, dev, n, record=rec, k=K, sparse=True)
     idx, val, tiles = codec.sparse_wire_views(rec, n, K)
@@ -832,7 +845,8 @@ class _Item(NamedTuple):
 
 
 class _Batch:
-    """The waiting messages of one (device, n, k, levels): a round's stacked records, encoded together.  The stream
+    """The waiting messages of one (device, n, k, levels, order): a round's stacked records, encoded together (a signed
+    and a magnitude message never share a launch: a batched encode runs in one selection order).  The stream
     handling around the encode is shared with :class:`_DenseBatch`, which replaces :meth:`_encode_rows`."""
 
     stats = _STATS
@@ -875,7 +889,7 @@ class _Batch:
 
     def _encode_rows(self, items, dev):
         """The items' records, encoded on ``dev``'s current stream: the rows of one ``[C, stride]`` block."""
-        _, n, k, levels = self.key
+        _, n, k, levels, order = self.key
         stride, _ = codec.stacked_wire_layout(n, k)
         C = len(items)
         recs = torch.empty(C, stride, dtype=torch.uint8, device=dev)
@@ -885,9 +899,10 @@ class _Batch:
         if fast is not None:  # one C call: the encode's launch chain fills the count slots too
             ws = codec.workspace(dev, codec._ws_size(dev, "flc_stacked_encode_batch_workspace_size", n, k, C),
                                  "topk_batch")
-            fast(flats, seeds, ctrs, k, levels, recs, cnts, ws)
+            fast(flats, seeds, ctrs, k, levels, recs, cnts, ws, order)
         else:
-            codec.stacked_encode_batch(flats, k, levels, seeds=seeds, counters=ctrs, counts=cnts, wires=recs)
+            codec.stacked_encode_batch(flats, k, levels, seeds=seeds, counters=ctrs, counts=cnts, wires=recs,
+                                       order=order)
         codec._after_encode(dev)
         rows = recs.unbind(0)
         fed = [(r, it.mem) for it, r in zip(items, rows) if it.mem is not None]
@@ -1042,15 +1057,16 @@ class _NaturalBatch(_Batch):
 # flc_topk_encode_tiled.  The same switch (FLC_DEFER_ENCODE), size bound and pending bounds as the stacked batches.
 # Rand-k keeps the immediate path.
 class _SparseBatch(_Batch):
-    """The waiting top-k messages of one (device, "sparse", n, K); an item has no Philox state and no count slot."""
+    """The waiting top-k messages of one (device, "sparse", n, K, order); an item has no Philox state and no count
+    slot."""
 
     stats = _SPARSE_STATS
 
     def _encode_rows(self, items, dev):
-        _, _, n, k = self.key
+        _, _, n, k, order = self.key
         stride, _ = codec.sparse_wire_layout(n, k)
         recs = torch.empty(len(items), stride, dtype=torch.uint8, device=dev)
-        codec.topk_encode_records([it.flat for it in items], k, recs)
+        codec.topk_encode_records([it.flat for it in items], k, recs, order=order)
         rows = recs.unbind(0)
         fed = [(r, it.mem) for it, r in zip(items, rows) if it.mem is not None]
         if fed:  # error feedback: e = a − c at the records' kept entries, one launch for the round, after the encode
@@ -1116,7 +1132,7 @@ def _defer(flat: torch.Tensor, shapes, n: int, K: int, s: int, tk: Compressor, s
     # compressors' pending lists have room, so the _finish calls below read nothing back and run no batch: they come
     # before the item is appended only so that the append and the bounds sit in one place (_enqueue)
     cnt = sd._count_slot(dev, st)
-    b = _waiting(_Batch, (dev.index, n, K, s))
+    b = _waiting(_Batch, (dev.index, n, K, s, tk.order))
     d = CompressedDelta(shapes, dev, n, k=K, levels=s, batch=b)
     tk._finish(n, tk.K)
     sd._finish_pending(n, cnt, _norm_stage_send(sd, None), _code_fraction(sd.s))
@@ -1178,7 +1194,7 @@ def _defer_sparse(flat: torch.Tensor, shapes, n: int, K: int, tk: Compressor, de
     takes the residual once the batch has encoded) joins the round's batched top-k encode; the send statistics advance
     here as ``compressVector`` advances them (compressors.py:293-296)."""
     st = torch.cuda.current_stream(dev)
-    b = _waiting(_SparseBatch, (dev.index, "sparse", n, K))
+    b = _waiting(_SparseBatch, (dev.index, "sparse", n, K, tk.order))
     d = CompressedDelta(shapes, dev, n, k=K, batch=b, sparse=True)
     tk._finish(n, tk.K)
     return _enqueue(b, _Item(d, flat, 0, 0, None, None, st, st.cuda_stream, mem))
@@ -1195,7 +1211,7 @@ def _stacked_fast(local, cached, shapes, n: int, K: int, s: int, tk: Compressor,
     cnt = sd._count_slot(dev)
     ws = codec.workspace(dev, codec._ws_size(dev, "flc_stacked_encode_delta_workspace_size", n, K, len(local)), "topk")
     try:
-        fast(local, cached, K, s, seed_ctr[0], seed_ctr[1], rec, cnt, ws)
+        fast(local, cached, K, s, seed_ctr[0], seed_ctr[1], rec, cnt, ws, tk.order)
     except TypeError:
         return None  # (nothing launched)
     codec._after_encode(dev)
@@ -1221,12 +1237,12 @@ def _stacked(ls, gs, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compres
     if sd.rng_mode == "philox":
         # the delta formed inside the encoder's read; the dithering stage's nonzero count stays on the device
         if gs is None:
-            codec.stacked_encode(ls, K, s, seed, ctr, wire=rec)
+            codec.stacked_encode(ls, K, s, seed, ctr, wire=rec, order=tk.order)
             cnt = sd._count_slot(dev)
             _lib.call("flc_count_nonzero_at_batch", _ptrs([ls]), _ptrs([pk.idx]), 1, n, K, _ptrs([cnt]),
                       codec._stream(dev))
         else:
-            codec.stacked_encode_delta(ls, gs, K, s, seed, ctr, wire=rec)
+            codec.stacked_encode_delta(ls, gs, K, s, seed, ctr, wire=rec, order=tk.order)
             cnt = sd._count_slot(dev)
             _lib.call("flc_delta_count_nonzero_at", _ptrs(ls), _ptrs(gs),
                       (ctypes.c_int64 * len(ls))(*[t.numel() for t in ls]), len(ls), pk.idx.data_ptr(), K,
@@ -1241,8 +1257,8 @@ def _stacked(ls, gs, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compres
     val = torch.empty(K, dtype=torch.float32, device=dev)
     ws = codec.workspace(dev, codec._ws_size(dev, "flc_topk_workspace_size", n, K), "topk")
     st = codec._stream(dev)
-    _lib.call("flc_topk_encode_tiled", x.data_ptr(), n, K, pk.idx.data_ptr(), val.data_ptr(), pk.tiles.data_ptr(),
-              ws.data_ptr(), ws.numel(), st)
+    codec._call_ord("flc_topk_encode_tiled", tk.order, 2, x.data_ptr(), n, K, pk.idx.data_ptr(), val.data_ptr(),
+                    pk.tiles.data_ptr(), ws.data_ptr(), ws.numel(), st)
     codec._after_encode(dev)
     tk._finish(n, tk.K)
     row = val.reshape(1, K)

@@ -93,6 +93,7 @@ class Compressor:
     """MI355X-native drop-in for the reference ``Compressor`` (compressors.py:35-419)."""
 
     bucket = 0  # (objects pickled before the attribute existed)
+    magnitude = False  # (likewise; every factory but makeTopKCompressor(..., magnitude=True) leaves it False)
 
     def __init__(self, compressorName: str = "", rng: str = "compat", seed: int = 0, extended_levels: bool = False,
                  norm: str = "auto", bucket: int = 0):
@@ -161,7 +162,7 @@ class Compressor:
         if t == CompressorType.RANDK_COMPRESSOR:
             return f"Random-K (K={self.K}) Compressor"
         if t == CompressorType.TOPK_COMPRESSOR:
-            return f"Top-K (K={self.K}) Compressor"
+            return f"Top-K by magnitude (K={self.K}) Compressor" if self.magnitude else f"Top-K (K={self.K}) Compressor"
         if t == CompressorType.NATURAL_COMPRESSOR_FP64:
             return f"Natural for fp64 [{omega}={self.getW():.1f}]"
         if t == CompressorType.NATURAL_COMPRESSOR_FP32:
@@ -188,7 +189,7 @@ class Compressor:
         if t == CompressorType.RANDK_COMPRESSOR:
             return f"Rand [K={self.K},D={self.D}]"
         if t == CompressorType.TOPK_COMPRESSOR:
-            return f"Top [K={self.K},D={self.D}]"
+            return f"Top|x| [K={self.K},D={self.D}]" if self.magnitude else f"Top [K={self.K},D={self.D}]"
         if t == CompressorType.NATURAL_COMPRESSOR_FP64:
             return f"Natural for fp64 [{omega}={self.getW():.1f}]"
         if t == CompressorType.NATURAL_COMPRESSOR_FP32:
@@ -305,6 +306,7 @@ class Compressor:
     def _set(self, name: str, ctype: CompressorType, w: float) -> None:
         self.__compressorName = name
         self.__compressorType = ctype
+        self.magnitude = False
         self.__w = w
 
     def makeIdenticalCompressor(self):
@@ -322,6 +324,7 @@ class Compressor:
         # (all levels > 10), leaving the object half switched, as the reference does
         self.__compressorName = name
         self.__compressorType = ctype
+        self.magnitude = False
         if self.extended_levels and 1 <= int(levels) <= 127:
             self.levelsValues = standard_levels(int(levels))  # i * (1/s): the arange table where both exist
         else:
@@ -350,6 +353,7 @@ class Compressor:
         # compressors.py:191-221 (any level count constructs; the device codec takes up to 127)
         self.__compressorName = name
         self.__compressorType = ctype
+        self.magnitude = False
         self.levelsValues = natural_levels(int(levels))
         self.s = len(self.levelsValues) - 1
         assert self.s == levels
@@ -370,10 +374,15 @@ class Compressor:
         self.K = K
         self.resetStats()
 
-    def makeTopKCompressor(self, K, D):
+    def makeTopKCompressor(self, K, D, magnitude=False):
+        """``magnitude=False``: the reference's rule, the K largest signed values (compressors.py:293-296).
+        ``magnitude=True`` (an extension): the K largest |x|, each kept with its own sign — the top-k of the gradient
+        sparsification literature, and the one error feedback needs (a negative component is never among the largest
+        signed values)."""
         self._set("TopKCompressor", CompressorType.TOPK_COMPRESSOR, 0.0)
         self.D = D
         self.K = K
+        self.magnitude = bool(magnitude)
         self.resetStats()
 
     def makeNaturalCompressorFP64(self):
@@ -392,6 +401,11 @@ class Compressor:
 
     def getW(self):
         return self.w
+
+    @property
+    def order(self) -> int:
+        """The top-k select's order (codec.ORDER_*): by magnitude when made with ``magnitude=True``, else signed."""
+        return codec.ORDER_MAGNITUDE if self.magnitude else codec.ORDER_SIGNED
 
     # ------------------------------------------------------------------ codec (compressors.py:267-410)
     def compressVector(self, x):
@@ -496,7 +510,7 @@ class Compressor:
                 # np.argsort(out)[:-K] is empty for K == 0 and K >= d: nothing is zeroed
                 out = codec.copy(x)
             else:
-                idx, val, tiles = codec.topk_encode(x, K, with_tiles=True)
+                idx, val, tiles = codec.topk_encode(x, K, with_tiles=True, order=self.order)
                 out = codec.sparse_decode(idx, val, d, tiles=tiles)
             self._finish(d, self.K)
             return out
@@ -641,7 +655,7 @@ class Compressor:
             return out
         if t == CompressorType.TOPK_COMPRESSOR:
             K = int(self.K)
-            out = codec.copy_f64(x) if K <= 0 or K >= d else codec.topk_dense_f64(x, K)
+            out = codec.copy_f64(x) if K <= 0 or K >= d else codec.topk_dense_f64(x, K, order=self.order)
             self._finish(d, self.K)
             return out
         if t == CompressorType.ADAPTIVE_RANDOM_COMPRESSOR:
@@ -710,7 +724,8 @@ class Compressor:
         if t == CompressorType.TOPK_COMPRESSOR:
             X2 = X.reshape(X.shape[0], -1)
             out = torch.empty_like(X2)
-            for c, (idx, val, tiles) in enumerate(codec.topk_encode_batch(list(X2.unbind(0)), int(self.K), True)):
+            for c, (idx, val, tiles) in enumerate(codec.topk_encode_batch(list(X2.unbind(0)), int(self.K), True,
+                                                                            order=self.order)):
                 codec.sparse_decode(idx, val, X2.shape[1], out=out[c], tiles=tiles)
             return out.reshape(X.shape)
         if t not in _STD and t not in _NATD:
@@ -728,7 +743,7 @@ class Compressor:
             seed, ctr = self.philox.next()
             return codec.quant_encode(x2, kind, self.s, codec.quant_norm(x2, self.p), seed, ctr, None, want_nnz=False)
         if t == CompressorType.TOPK_COMPRESSOR:
-            return codec.topk_encode(x, int(self.K), with_tiles=True)
+            return codec.topk_encode(x, int(self.K), with_tiles=True, order=self.order)
         if t in _NATURAL:
             seed, ctr = self.philox.next()
             return codec.natural_encode(x, seed, ctr, None, want_nnz=False)[0]

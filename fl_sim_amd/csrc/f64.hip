@@ -443,6 +443,13 @@ __device__ __forceinline__ unsigned long long order_key64(double v) {
   return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
 }
 
+// the key in a select's order (FLC_ORDER_*): magnitude = the same order on |v|; the staged bits keep v's sign
+template <bool MAG>
+__device__ __forceinline__ unsigned long long sel_key64(double v) {
+  if constexpr (MAG) return order_key64(fabs(v));
+  else return order_key64(v);
+}
+
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 constexpr int kDigits = 8;          // 8-bit digits of a 64-bit key, most significant first
 constexpr int kSample64 = 16384;    // sample keys
@@ -585,6 +592,7 @@ __device__ __forceinline__ int range_shift64(unsigned long long maxoff, int bits
 
 // The sample's S keys, loaded by kSampleBlocks blocks (scattered loads from one CU wait on its address translation a
 // page at a time); block 0 also resets the state the select kernel accumulates into
+template <bool MAG>
 __global__ __launch_bounds__(kT) void sel64_prep_kernel(const double* __restrict__ x, int64_t n, int S,
                                                         Sel64* __restrict__ st) {
   const int tid = threadIdx.x;
@@ -603,7 +611,7 @@ __global__ __launch_bounds__(kT) void sel64_prep_kernel(const double* __restrict
   }
   for (int j = blockIdx.x * kT + tid; j < S; j += gridDim.x * kT) {
     const int64_t pos = (int64_t)(((double)j + 0.5) * (double)n / (double)S);
-    unsigned key = (unsigned)(order_key64(x[pos < n ? pos : n - 1]) >> 32);
+    unsigned key = (unsigned)(sel_key64<MAG>(x[pos < n ? pos : n - 1]) >> 32);
     st->sample[j] = key;
     if (S == kSample64 && gridDim.x * kT == kSample64) {  // (one key per thread: every lane of the wave holds one)
       // the compact sample: the wave's 8 largest keys, descending (topk.hip's compact sample for float32)
@@ -879,6 +887,7 @@ __device__ __forceinline__ void grid_sync64(Sel64* st, unsigned long long target
 //   4. the bin of the K-th largest (every block the same), its keys appended to one list, block 0 waits for every
 //      block's appends and selects T among them;
 // else (the band off or failed) the exact radix select over x.
+template <bool MAG>
 __global__ __launch_bounds__(kGT) void sel64_select_kernel(const double* __restrict__ x, int64_t n, long long k, int S,
                                                            long long r_lo, long long r_hi, int segcap,
                                                            Sel64* __restrict__ st, unsigned long long* __restrict__ seg,
@@ -970,7 +979,7 @@ __global__ __launch_bounds__(kGT) void sel64_select_kernel(const double* __restr
         for (int j = 0; j < 2; ++j) {
           const int loc = 2 * (r * kGT + tid) + j;
           const double v = loc == rem - 1 ? xlast : j ? cv[r].y : cv[r].x;
-          const unsigned long long key = order_key64(v);
+          const unsigned long long key = sel_key64<MAG>(v);
           const bool in = loc < rem && key >= t_lo;
           const unsigned long long m = __ballot(in);
           if (m == 0ull) continue;
@@ -1053,7 +1062,7 @@ __global__ __launch_bounds__(kGT) void sel64_select_kernel(const double* __restr
         const unsigned short* si = segi + (size_t)ch * segcap;
         for (int i0 = 0; i0 < c; i0 += kWave) {  // (wave-uniform bounds)
           const int i = i0 + lane;
-          const unsigned long long key = i < c ? order_key64(__longlong_as_double((long long)sc[i])) : 0ull;
+          const unsigned long long key = i < c ? sel_key64<MAG>(__longlong_as_double((long long)sc[i])) : 0ull;
           // (and below t_hi: the band's top bin may reach past the ceiling — its width need not be a multiple of the
           // bin width — and the keys above the ceiling were counted apart, in `above`, not in the bin)
           const bool in = i < c && key >= lo_b && key - lo_b < wb && key < t_hi;
@@ -1134,8 +1143,8 @@ __global__ __launch_bounds__(kGT) void sel64_select_kernel(const double* __restr
       } else if (i < n) {
         v0 = x[i];
       }
-      const int d0 = i < n ? digit(i, order_key64(v0)) : -1;
-      const int d1 = i + 1 < n ? digit(i + 1, order_key64(v1)) : -1;
+      const int d0 = i < n ? digit(i, sel_key64<MAG>(v0)) : -1;
+      const int d1 = i + 1 < n ? digit(i + 1, sel_key64<MAG>(v1)) : -1;
       hist_add64(s_h, (unsigned)d0, d0 >= 0);
       hist_add64(s_h, (unsigned)d1, d1 >= 0);
     }
@@ -1200,6 +1209,7 @@ constexpr int kPiece = FLC_EMIT_PIECE;
 #endif
 constexpr int kEmitSegMax = FLC_EMIT_SEG_MAX;
 constexpr int kPieces = kChunk / kPiece;
+template <bool MAG>
 __global__ __launch_bounds__(kWave) void sel64_emit_kernel(const double* __restrict__ x, int64_t n, int segcap,
                                                            const Sel64* __restrict__ st,
                                                            const unsigned long long* __restrict__ seg,
@@ -1235,7 +1245,7 @@ __global__ __launch_bounds__(kWave) void sel64_emit_kernel(const double* __restr
 #pragma unroll
     for (int u = 0; u < kPiece / 2 / kWave; ++u) t2[lane + u * kWave] = u64x2{0ull, 0ull};
     auto put = [&](int loc, unsigned long long b) {
-      const unsigned long long key = order_key64(__longlong_as_double((long long)b));
+      const unsigned long long key = sel_key64<MAG>(__longlong_as_double((long long)b));
       if ((loc / kPiece) == sub && (key > T || (key == T && c * kChunk + loc >= ithr))) s_tile[loc % kPiece] = b;
     };
     if (lane < cc) put(loc0, b0);
@@ -1266,7 +1276,7 @@ __global__ __launch_bounds__(kWave) void sel64_emit_kernel(const double* __restr
   for (int u = 0; u < kPiece / 2 / kWave; ++u) {
     const int64_t e = e0 + 2 * (lane + u * kWave);
     auto keep = [&](double d, int64_t i) {
-      const unsigned long long key = order_key64(d);
+      const unsigned long long key = sel_key64<MAG>(d);
       return (key > T || (key == T && i >= ithr)) ? d : 0.0;
     };
     if (e + 2 <= n) {
@@ -1494,7 +1504,11 @@ int flc_quant_decode_f64(const uint8_t* codes, int64_t n, int kind, int levels, 
   return FLC_OK;
 }
 
-int flc_topk_dense_f64(const double* x, int64_t n, int64_t k, double* out, void* ws, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+template <bool MAG>
+int topk_dense_f64(const double* x, int64_t n, int64_t k, double* out, void* ws, size_t ws_bytes, void* stream) {
   if (!x || !out || n <= 0) return fail(FLC_EINVAL, "flc_topk_dense_f64: bad arguments");
   if (k <= 0 || k >= n) return fail(FLC_EINVAL, "flc_topk_dense_f64: need 0 < k < n (got k=%lld, n=%lld)",
                                     (long long)k, (long long)n);
@@ -1507,23 +1521,37 @@ int flc_topk_dense_f64(const double* x, int64_t n, int64_t k, double* out, void*
   int dev = 0;
   const int cus = std::min(stream_cus(st, &dev), kMaxG64);
   if (cdiv(nch, cus) > kMaxCPB) f.on = false;  // (more chunks per block than its LDS counters: the exact passes)
-  FLC_LAUNCH("sel64_prep", sel64_prep_kernel, dim3(f.on ? (unsigned)kSampleBlocks : 1u), dim3(kT), 0, st, x, n,
+  FLC_LAUNCH("sel64_prep", sel64_prep_kernel<MAG>, dim3(f.on ? (unsigned)kSampleBlocks : 1u), dim3(kT), 0, st, x, n,
              f.on ? f.S : 0, w.sel);
   {  // (grid-synchronised: one block per CU, all resident)
     Coresident co(st, dev);
     if (co.status()) return co.status();
-    FLC_LAUNCH_CO(co, "sel64_select", sel64_select_kernel, dim3((unsigned)cus), dim3(kGT), 0, st, x, n, (long long)k,
+    FLC_LAUNCH_CO(co, "sel64_select", sel64_select_kernel<MAG>, dim3((unsigned)cus), dim3(kGT), 0, st, x, n, (long long)k,
                f.on ? f.S : 0, f.r_lo, f.r_hi, f.on ? f.segcap : 0, w.sel, w.seg, w.segi, w.counts, f.on ? nch : 0,
                force_timeout64() ? 0u : (1u << 22));
     const int rc = co.finish();
     if (rc) return rc;
   }
   // (segments longer than kEmitSegMax: x is read again instead, every piece's wave would scan its chunk's segment)
-  FLC_LAUNCH("sel64_emit", sel64_emit_kernel, dim3((unsigned)cdiv(n, kPiece)), dim3(kWave), 0, st, x, n,
+  FLC_LAUNCH("sel64_emit", sel64_emit_kernel<MAG>, dim3((unsigned)cdiv(n, kPiece)), dim3(kWave), 0, st, x, n,
              f.on && f.segcap <= kEmitSegMax ? f.segcap : 0,
              (const Sel64*)w.sel, (const unsigned long long*)w.seg, (const unsigned short*)w.segi,
              (const int*)w.counts, out, w.sticky);
   return FLC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int flc_topk_dense_f64_ord(const double* x, int64_t n, int64_t k, int order, double* out, void* ws, size_t ws_bytes,
+                           void* stream) {
+  if (order == FLC_ORDER_SIGNED) return topk_dense_f64<false>(x, n, k, out, ws, ws_bytes, stream);
+  if (order == FLC_ORDER_MAGNITUDE) return topk_dense_f64<true>(x, n, k, out, ws, ws_bytes, stream);
+  return fail(FLC_EINVAL, "flc_topk_dense_f64: order must be FLC_ORDER_SIGNED or FLC_ORDER_MAGNITUDE (got %d)", order);
+}
+
+int flc_topk_dense_f64(const double* x, int64_t n, int64_t k, double* out, void* ws, size_t ws_bytes, void* stream) {
+  return flc_topk_dense_f64_ord(x, n, k, FLC_ORDER_SIGNED, out, ws, ws_bytes, stream);
 }
 
 // the select state of the workspace's last flc_topk_dense_f64(n, k), copied to the host, and that call's band

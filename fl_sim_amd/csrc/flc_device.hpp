@@ -276,6 +276,14 @@ __device__ __forceinline__ uint32_t order_key(uint32_t b) {
   if (b == 0x80000000u) b = 0u;                             // -0 -> +0
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
+// The key of an element's raw bits in a select's order (FLC_ORDER_*): signed = the order above; magnitude = the same
+// order on |x| (Aji & Heafield's / Stich et al.'s top-k), so a NaN of either sign is largest, +v and -v tie, -0 == +0.
+// The sign stays in the raw bits a select stages and writes out; only the key drops it.
+template <bool MAG>
+__device__ __forceinline__ uint32_t sel_key(uint32_t raw) {
+  if constexpr (MAG) return order_key(raw & 0x7fffffffu);
+  else return order_key(raw);
+}
 // value of a key (canonical NaN / +0 for the collapsed classes)
 __device__ __forceinline__ float key_value(uint32_t k) {
   if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);

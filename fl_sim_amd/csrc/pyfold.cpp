@@ -464,13 +464,13 @@ PyObject* avg_and_gradients(PyObject*, PyObject* args) {
 // 16-B aligned; the delta is formed in the encoder's read), then, with `count` (an int64 HIP tensor), the dithering
 // stage's send count (flc_delta_count_nonzero_at over the kept entries).  `ws`: the encoder's workspace (uint8).  The
 // same checks as model_fold: TypeError for a tensor the encoder does not take (the caller converts and retries),
-// ValueError for sizes.
+// ValueError for sizes.  An optional last argument is the top-k stage's selection order (FLC_ORDER_*, default signed).
 PyObject* stacked_delta_record(PyObject*, PyObject* args) {
   PyObject *loc, *glo, *record, *count, *wso;
   long long k;
-  int levels;
+  int levels, order = FLC_ORDER_SIGNED;
   unsigned long long seed, counter;
-  if (!PyArg_ParseTuple(args, "OOLiKKOOO", &loc, &glo, &k, &levels, &seed, &counter, &record, &count, &wso))
+  if (!PyArg_ParseTuple(args, "OOLiKKOOO|i", &loc, &glo, &k, &levels, &seed, &counter, &record, &count, &wso, &order))
     return nullptr;
   Refs refs;
   int dev = -1;
@@ -499,9 +499,10 @@ PyObject* stacked_delta_record(PyObject*, PyObject* args) {
   int32_t* idx = reinterpret_cast<int32_t*>(rp + off[1]);
   const char* what = "flc_stacked_encode_delta";  // (two calls: the one that failed is named)
   const int rc = run_on(dev, [&](void* st) {
-    int r = flc_stacked_encode_delta(lp.data(), gp.data(), sz.data(), m, k, levels, seed, counter, idx, rp + off[2],
-                                     reinterpret_cast<float*>(rp + off[0]), reinterpret_cast<uint32_t*>(rp + off[3]),
-                                     ws->data_ptr(), (size_t)ws->numel(), st);
+    int r = flc_stacked_encode_delta_ord(lp.data(), gp.data(), sz.data(), m, k, order, levels, seed, counter, idx,
+                                         rp + off[2], reinterpret_cast<float*>(rp + off[0]),
+                                         reinterpret_cast<uint32_t*>(rp + off[3]), ws->data_ptr(), (size_t)ws->numel(),
+                                         st);
     if (r == FLC_OK && cp) {
       what = "flc_delta_count_nonzero_at";
       r = flc_delta_count_nonzero_at(lp.data(), gp.data(), sz.data(), m, idx, k, cp, st);
@@ -568,12 +569,14 @@ PyObject* ef_accumulate(PyObject*, PyObject* args) {
 // stacked_records_round(flats, seeds, counters, k, levels, records, counts, ws): the deferred messages of a round in
 // one C call and one encode launch chain — flc_stacked_encode_round of the flat deltas, one Philox (seed, counter) per
 // message, into the rows of the [C, >= stride] record block (row c equals client c's one-message record); its select
-// writes the send counts counts[c] itself (no count launches).
+// writes the send counts counts[c] itself (no count launches).  An optional last argument is the round's selection
+// order (FLC_ORDER_*, default signed).
 PyObject* stacked_records_round(PyObject*, PyObject* args) {
   PyObject *flats, *seeds, *recs, *counts, *wso, *ctrs;
   long long k;
-  int levels;
-  if (!PyArg_ParseTuple(args, "OOOLiOOO", &flats, &seeds, &ctrs, &k, &levels, &recs, &counts, &wso)) return nullptr;
+  int levels, order = FLC_ORDER_SIGNED;
+  if (!PyArg_ParseTuple(args, "OOOLiOOO|i", &flats, &seeds, &ctrs, &k, &levels, &recs, &counts, &wso, &order))
+    return nullptr;
   Refs refs;
   PyObject* seqs[3] = {flats, seeds, counts};
   PyObject* f[3];
@@ -630,8 +633,9 @@ PyObject* stacked_records_round(PyObject*, PyObject* args) {
     tp[c] = reinterpret_cast<uint32_t*>(r + off[3]);
   }
   if (!on_device(dev, "flc_stacked_encode_round", [&](void* st) {
-        return flc_stacked_encode_round(xp.data(), (int)C, n, k, levels, sd.data(), ct64.data(), ip.data(), kp.data(),
-                                        np.data(), tp.data(), cp.data(), ws->data_ptr(), (size_t)ws->numel(), st);
+        return flc_stacked_encode_round_ord(xp.data(), (int)C, n, k, order, levels, sd.data(), ct64.data(), ip.data(),
+                                            kp.data(), np.data(), tp.data(), cp.data(), ws->data_ptr(),
+                                            (size_t)ws->numel(), st);
       }))
     return nullptr;
   Py_RETURN_NONE;
@@ -1096,10 +1100,10 @@ PyMethodDef kMethods[] = {
      "ef_accumulate(local, global_or_None, e): e += cat(local - global) in place (flc_ef_accumulate) on the current "
      "stream of the memory's device"},
     {"stacked_records_round", stacked_records_round, METH_VARARGS,
-     "stacked_records_round(flats, seeds, counters, k, levels, records, counts, ws): flc_stacked_encode_round into the "
+     "stacked_records_round(flats, seeds, counters, k, levels, records, counts, ws[, order]): flc_stacked_encode_round into the "
      "rows of a record block, one Philox counter per message, the send counts written by the encode itself"},
     {"stacked_delta_record", stacked_delta_record, METH_VARARGS,
-     "stacked_delta_record(local, global, k, levels, seed, counter, record, count, ws): flc_stacked_encode_delta into a "
+     "stacked_delta_record(local, global, k, levels, seed, counter, record, count, ws[, order]): flc_stacked_encode_delta into a "
      "packed wire record (+ flc_delta_count_nonzero_at into count) on the current stream of the tensors' device"},
     {"alias", alias, METH_VARARGS,
      "alias(host_tensor, device_index): a HIP-device tensor over a pinned host tensor's memory (zero-copy)"},

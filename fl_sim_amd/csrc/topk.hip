@@ -4,7 +4,9 @@
 // Selection contract (compressors.py:294-295, `out[np.argsort(out)[:-K]] = 0`): keep the k largest
 // *signed* values; -0 == +0; NaN is largest; among elements equal to the k-th largest value the
 // highest indices are kept (stable ascending argsort order; the reference's own argsort is unstable,
-// so any tie choice satisfies it — see DESIGN.md).
+// so any tie choice satisfies it — see DESIGN.md).  The `_ord` entry points take the selection order: FLC_ORDER_MAGNITUDE
+// runs the same select on |x| (sel_key / cand_value below, a compile-time trait of the source) and keeps each value's
+// own sign; everything said of keys here then reads "keys of |x|" (DESIGN.md §3.1d).
 //
 // Two launches (the default, "fused" path); block b of the encode owns the element range [b M, (b + 1) M):
 //   sample   32 K strided keys of x (order-preserving uint32 keys).
@@ -44,6 +46,7 @@
 #include <algorithm>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "flc_device.hpp"
@@ -552,6 +555,7 @@ __device__ __forceinline__ void sample_general(const unsigned* sample, int S, lo
 // registers and bytes in flight per wave as FlatSrc's SF = 4.
 struct FlatSrc {
   static constexpr int SF = 4;
+  static constexpr bool kMag = false;
   const float* x;
   struct Step {
     float4 v[SF];
@@ -589,6 +593,7 @@ typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));  // 4-B al
 
 struct DeltaSrc {
   static constexpr int SF = 2;
+  static constexpr bool kMag = false;
   SegTab t;
   struct Step {
     float4 l[SF], g[SF];
@@ -671,25 +676,41 @@ struct DeltaSrc {
   }
 };
 
+// The same source selected by magnitude (FLC_ORDER_MAGNITUDE): the elements, the staged raw bits and everything written
+// out are the source's own, signs included; only the key of an element (sel_key) and the filter's predicate
+// (cand_value) see |x|.  The signed instances are the code they were: every use of the trait is an `if constexpr`.
+template <class Base>
+struct MagSrc : Base {
+  static constexpr bool kMag = true;
+};
+
 template <bool FULL>
 __device__ __forceinline__ bool in_span(int o, int lim) { return FULL || o < lim; }
 
-template <bool FULL>
-__device__ __forceinline__ void cand4(const float4& v, float tf, int o, int lim, bool& f0, bool& f1, bool& f2,
-                                      bool& f3) {
-  f0 = is_cand(v.x, tf) && in_span<FULL>(o + 0, lim);
-  f1 = is_cand(v.y, tf) && in_span<FULL>(o + 1, lim);
-  f2 = is_cand(v.z, tf) && in_span<FULL>(o + 2, lim);
-  f3 = is_cand(v.w, tf) && in_span<FULL>(o + 3, lim);
+// the value the floor is compared with: |v| in magnitude order (a VALU source modifier of the compare; for the delta
+// source after the subtraction, which Step::val has done)
+template <bool MAG>
+__device__ __forceinline__ float cand_value(float v) {
+  if constexpr (MAG) return fabsf(v);
+  else return v;
 }
 
-template <bool FULL, class Step, int SF>
+template <bool FULL, bool MAG>
+__device__ __forceinline__ void cand4(const float4& v, float tf, int o, int lim, bool& f0, bool& f1, bool& f2,
+                                      bool& f3) {
+  f0 = is_cand(cand_value<MAG>(v.x), tf) && in_span<FULL>(o + 0, lim);
+  f1 = is_cand(cand_value<MAG>(v.y), tf) && in_span<FULL>(o + 1, lim);
+  f2 = is_cand(cand_value<MAG>(v.z), tf) && in_span<FULL>(o + 2, lim);
+  f3 = is_cand(cand_value<MAG>(v.w), tf) && in_span<FULL>(o + 3, lim);
+}
+
+template <bool FULL, class Step, int SF, bool MAG>
 __device__ __forceinline__ unsigned step_count(const Step& v, float tf, int lim, int lane) {
   unsigned cnt = 0;
 #pragma unroll
   for (int q = 0; q < SF; ++q) {
     bool f0, f1, f2, f3;
-    cand4<FULL>(v.val(q), tf, 256 * q + 4 * lane, lim, f0, f1, f2, f3);
+    cand4<FULL, MAG>(v.val(q), tf, 256 * q + 4 * lane, lim, f0, f1, f2, f3);
     cnt += __popcll(__ballot(f0)) + __popcll(__ballot(f1)) + __popcll(__ballot(f2)) + __popcll(__ballot(f3));
   }
   return cnt;
@@ -711,8 +732,9 @@ struct FilterCtx {
 };
 
 // one LDS candidate into the band histogram / above count / max key
+template <bool MAG>
 __device__ __forceinline__ void band_bin(FilterCtx& c, unsigned p) {
-  const unsigned key = order_key(c.s_key[p]);
+  const unsigned key = sel_key<MAG>(c.s_key[p]);
   const unsigned long long rel = (unsigned long long)(key - c.t_lo);
   if (rel >= c.width0) ++c.above;
   else atomicAdd(&c.s_hist[(unsigned)(rel >> c.sh0)], 1u);
@@ -723,7 +745,7 @@ __device__ __forceinline__ void band_bin(FilterCtx& c, unsigned p) {
 // candidates are formed after the pass in one dense sweep over LDS (every lane busy), only candidates
 // beyond the LDS capacity are binned here (and kept in the HBM overflow while it has room)
 // (OVF = false: the caller has checked that the whole step lands below kCap — the hot path, LDS stores only)
-template <bool OVF>
+template <bool OVF, bool MAG>
 __device__ __forceinline__ void emit(FilterCtx& c, unsigned q, unsigned e, float v) {
   const unsigned raw = __float_as_uint(v);
   const unsigned p = q;
@@ -735,7 +757,7 @@ __device__ __forceinline__ void emit(FilterCtx& c, unsigned q, unsigned e, float
       c.g_key[p - kCap] = raw;
       c.g_idx[p - kCap] = e;
     }
-    const unsigned key = order_key(raw);
+    const unsigned key = sel_key<MAG>(raw);
     const unsigned long long rel = (unsigned long long)(key - c.t_lo);
     if (rel >= c.width0) ++c.above;
     else atomicAdd(&c.s_hist[(unsigned)(rel >> c.sh0)], 1u);
@@ -744,14 +766,14 @@ __device__ __forceinline__ void emit(FilterCtx& c, unsigned q, unsigned e, float
 }
 
 // ordered append from position `pos` (within a q: lane-major, then the 4 components)
-template <bool FULL, class Step, int SF, bool OVF>
+template <bool FULL, class Step, int SF, bool OVF, bool MAG>
 __device__ __forceinline__ void step_write(const Step& st, float tf, int lim, int lane, unsigned wbu,
                                            unsigned pos, FilterCtx& c) {
 #pragma unroll
   for (int q = 0; q < SF; ++q) {
     bool f0, f1, f2, f3;
     const float4 vq = st.val(q);
-    cand4<FULL>(vq, tf, 256 * q + 4 * lane, lim, f0, f1, f2, f3);
+    cand4<FULL, MAG>(vq, tf, 256 * q + 4 * lane, lim, f0, f1, f2, f3);
     const unsigned long long m0 = __ballot(f0), m1 = __ballot(f1), m2 = __ballot(f2), m3 = __ballot(f3);
     if ((m0 | m1 | m2 | m3) != 0ull) {
       unsigned p = pos;
@@ -761,10 +783,10 @@ __device__ __forceinline__ void step_write(const Step& st, float tf, int lim, in
       p = __builtin_amdgcn_mbcnt_hi((unsigned)(m3 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m3, p));
       if (f0 | f1 | f2 | f3) {
         const unsigned e = wbu + (unsigned)(256 * q + 4 * lane);
-        if (f0) { emit<OVF>(c, p, e + 0u, vq.x); ++p; }
-        if (f1) { emit<OVF>(c, p, e + 1u, vq.y); ++p; }
-        if (f2) { emit<OVF>(c, p, e + 2u, vq.z); ++p; }
-        if (f3) emit<OVF>(c, p, e + 3u, vq.w);
+        if (f0) { emit<OVF, MAG>(c, p, e + 0u, vq.x); ++p; }
+        if (f1) { emit<OVF, MAG>(c, p, e + 1u, vq.y); ++p; }
+        if (f2) { emit<OVF, MAG>(c, p, e + 2u, vq.z); ++p; }
+        if (f3) emit<OVF, MAG>(c, p, e + 3u, vq.w);
       }
       pos += __popcll(m0) + __popcll(m1) + __popcll(m2) + __popcll(m3);
     }
@@ -772,20 +794,20 @@ __device__ __forceinline__ void step_write(const Step& st, float tf, int lim, in
 }
 
 // one block step: count, exchange the 16 wave counts through LDS, append in index order
-template <bool FULL, class Step, int SF>
+template <bool FULL, class Step, int SF, bool MAG>
 __device__ __forceinline__ void step_process(const Step& v, int64_t wb, int64_t end, float tf,
                                              unsigned (&s_wc)[2][kENW], int par, unsigned& base, FilterCtx& c) {
   constexpr int span = SF * 256;
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x >> 6;
   const int lim = FULL ? span : (int)(end > wb ? (end - wb < span ? end - wb : span) : 0);
-  const unsigned cnt = step_count<FULL, Step, SF>(v, tf, lim, lane);
+  const unsigned cnt = step_count<FULL, Step, SF, MAG>(v, tf, lim, lane);
   if (lane == 0) s_wc[par][wid] = cnt;
   lds_barrier();
 #if !FLC_BAND_AFTER_PASS
   {  // the band histogram of the earlier steps' LDS candidates (their writes are visible after this barrier),
      // binned while this step's loads are in flight: the post-pass sweep is left with the last step's
     const unsigned s1 = base < (unsigned)kCap ? base : (unsigned)kCap;
-    for (unsigned p = c.swept + threadIdx.x; p < s1; p += kET) band_bin(c, p);
+    for (unsigned p = c.swept + threadIdx.x; p < s1; p += kET) band_bin<MAG>(c, p);
     c.swept = s1;
   }
 #endif
@@ -802,9 +824,9 @@ __device__ __forceinline__ void step_process(const Step& v, int64_t wb, int64_t 
   asm volatile("" : "+v"(tf2));
   if (cnt != 0u) {
     if (base + tot <= (unsigned)kCap)  // (block-uniform) the step lands in LDS: no overflow code on the hot path
-      step_write<FULL, Step, SF, false>(v, tf2, lim, lane, (unsigned)wb, base + pre, c);
+      step_write<FULL, Step, SF, false, MAG>(v, tf2, lim, lane, (unsigned)wb, base + pre, c);
     else
-      step_write<FULL, Step, SF, true>(v, tf2, lim, lane, (unsigned)wb, base + pre, c);
+      step_write<FULL, Step, SF, true, MAG>(v, tf2, lim, lane, (unsigned)wb, base + pre, c);
   }
   base += tot;
 }
@@ -1065,7 +1087,7 @@ template <class Src>
 __device__ __forceinline__ unsigned sample_one(const Src& x, int64_t n, int S, const EncWs& w, int j) {
   if (j >= S) return 0u;
   const int64_t pos = (S == n) ? (int64_t)j : (int64_t)(((double)j + 0.5) * (double)n / (double)S);
-  const unsigned key = order_key(__float_as_uint(x.get(pos < n ? pos : n - 1)));
+  const unsigned key = sel_key<Src::kMag>(__float_as_uint(x.get(pos < n ? pos : n - 1)));
   w.sample()[j] = key;
   return key;
 }
@@ -1142,6 +1164,10 @@ __device__ __forceinline__ DeltaSrc batch_src(const DeltaSrc& proto, const Batch
   DeltaSrc d = proto;
   d.t.lp = static_cast<const float* const*>(e.x);
   return d;
+}
+template <class Base>
+__device__ __forceinline__ MagSrc<Base> batch_src(const MagSrc<Base>& proto, const BatchEntry& e) {
+  return MagSrc<Base>{batch_src(static_cast<const Base&>(proto), e)};
 }
 
 // batched: `per` blocks sample each client into its own header (and zero the client's header for its select: the
@@ -1290,32 +1316,32 @@ __device__ __forceinline__ FilterOut filter_phase(const Src& x, int64_t n, const
     int s = 0;
     if (take_all && nfull > 0) x.template load<true>(cur, wb0, b1, lane, va);
     if (!take_all && nfull >= 3) {  // peeled first iteration: steps 0 and 1 are in flight already
-      step_process<true, Step, SF>(va, wb0, b1, tf, s_wc, 0, base, fc);
+      step_process<true, Step, SF, Src::kMag>(va, wb0, b1, tf, s_wc, 0, base, fc);
       x.template load<true>(cur, wb0 + 2 * kBS, b1, lane, va);
-      step_process<true, Step, SF>(vb, wb0 + kBS, b1, tf, s_wc, 1, base, fc);
+      step_process<true, Step, SF, Src::kMag>(vb, wb0 + kBS, b1, tf, s_wc, 1, base, fc);
       s = 2;
     }
     for (; s + 3 <= nfull; s += 2) {
       const int64_t wa = wb0 + (int64_t)s * kBS, wbn = wa + kBS;
       x.template load<true>(cur, wbn, b1, lane, vb);
-      step_process<true, Step, SF>(va, wa, b1, tf, s_wc, 0, base, fc);
+      step_process<true, Step, SF, Src::kMag>(va, wa, b1, tf, s_wc, 0, base, fc);
       x.template load<true>(cur, wbn + kBS, b1, lane, va);
-      step_process<true, Step, SF>(vb, wbn, b1, tf, s_wc, 1, base, fc);
+      step_process<true, Step, SF, Src::kMag>(vb, wbn, b1, tf, s_wc, 1, base, fc);
     }
     if (s + 2 == nfull) {
       const int64_t wa = wb0 + (int64_t)s * kBS, wbn = wa + kBS;
       x.template load<true>(cur, wbn, b1, lane, vb);
-      step_process<true, Step, SF>(va, wa, b1, tf, s_wc, 0, base, fc);
-      step_process<true, Step, SF>(vb, wbn, b1, tf, s_wc, 1, base, fc);
+      step_process<true, Step, SF, Src::kMag>(va, wa, b1, tf, s_wc, 0, base, fc);
+      step_process<true, Step, SF, Src::kMag>(vb, wbn, b1, tf, s_wc, 1, base, fc);
       s += 2;
     } else if (s + 1 == nfull) {
-      step_process<true, Step, SF>(va, wb0 + (int64_t)s * kBS, b1, tf, s_wc, 0, base, fc);
+      step_process<true, Step, SF, Src::kMag>(va, wb0 + (int64_t)s * kBS, b1, tf, s_wc, 0, base, fc);
       ++s;
     }
     if (s < nsteps) {  // the partial last step of the last block
       const int64_t wa = wb0 + (int64_t)s * kBS;
       x.template load<false>(cur, wa, b1, lane, va);
-      step_process<false, Step, SF>(va, wa, b1, tf, s_wc, s & 1, base, fc);
+      step_process<false, Step, SF, Src::kMag>(va, wa, b1, tf, s_wc, s & 1, base, fc);
     }
   }
   const unsigned C_b = base;
@@ -1324,7 +1350,7 @@ __device__ __forceinline__ FilterOut filter_phase(const Src& x, int64_t n, const
   BLKT(1);
   {  // band histogram / above / max of the stored candidates
     const unsigned nst = C_b < (unsigned)kCap ? C_b : (unsigned)kCap;
-    for (unsigned p = fc.swept + tid; p < nst; p += kET) band_bin(fc, p);
+    for (unsigned p = fc.swept + tid; p < nst; p += kET) band_bin<Src::kMag>(fc, p);
     __syncthreads();
   }
 
@@ -1582,7 +1608,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
       const unsigned p = p0 + tid;
       unsigned raw = 0, id = 0;
       if (p < ncand) cand_get(src, p, raw, id);
-      const unsigned key = order_key(raw);
+      const unsigned key = sel_key<Src::kMag>(raw);
       mk = (p < ncand && key > mk) ? key : mk;
       hist_add(s_hist, key >> sh, p < ncand);
     }
@@ -1627,7 +1653,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
     // each of my in-bin keys give the compaction its per-wave strict / tie counts once T is known
     unsigned gtw = 0;
     auto scan_one = [&](const unsigned p, const unsigned raw) {
-      const unsigned key = order_key(raw);
+      const unsigned key = sel_key<Src::kMag>(raw);
       const unsigned long long rel = (unsigned long long)key - lo0;
       const bool valid = p < cq1 && key >= lo0 && key >= t_lo;  // (x-mode: below the floor never counts)
       gtw += (unsigned)__popcll(__ballot(valid && rel >= wd0));
@@ -1822,7 +1848,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
       const unsigned p = p0 + tid;
       unsigned raw = 0, id = 0;
       if (p < ncand) cand_get(src, p, raw, id);
-      const unsigned key = order_key(raw);
+      const unsigned key = sel_key<Src::kMag>(raw);
       const unsigned long long rel = (unsigned long long)key - lo;
       const bool in = p < ncand && key >= lo;
       above += (in && rel >= wd) ? 1u : 0u;
@@ -1850,7 +1876,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
         const unsigned p = p0 + tid;
         unsigned raw = 0, id = 0;
         if (p < ncand) cand_get(src, p, raw, id);
-        const unsigned key = order_key(raw);
+        const unsigned key = sel_key<Src::kMag>(raw);
         cnt += (p < ncand && key > T) ? (1ull << 32) : 0ull;
         cnt += (p < ncand && key == T) ? 1ull : 0ull;
       }
@@ -1934,7 +1960,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
       const unsigned p = p0 + lane;
       unsigned raw = 0, id = 0;
       if (p < q1) cand_get(src, p, raw, id);
-      const unsigned key = order_key(raw);
+      const unsigned key = sel_key<Src::kMag>(raw);
       ws += __popcll(__ballot(p < q1 && key > T));
       wt += __popcll(__ballot(p < q1 && key == T));
     }
@@ -2055,7 +2081,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
         const unsigned n_raw = src.s_key[pn], n_id = src.s_idx[pn];
         const unsigned p = p0 + lane;
         const bool in = p < wq1;
-        const unsigned key = order_key(c_raw);
+        const unsigned key = sel_key<Src::kMag>(c_raw);
         const bool is_s = in && key > T, is_t = in && key == T;
         const unsigned long long ms = __ballot(is_s), mt = __ballot(is_t);
         const long long tb = t_before + __builtin_amdgcn_mbcnt_hi((unsigned)(mt >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mt, 0u));
@@ -2100,7 +2126,7 @@ __global__ __launch_bounds__(kET) void topk_select_kernel(Src x, int64_t n, long
     auto round = [&](const unsigned p0, const unsigned rw, const unsigned raw, const unsigned id) {
       const unsigned p = p0 + lane;
       const bool in = p < q1;
-      const unsigned key = order_key(raw);
+      const unsigned key = sel_key<Src::kMag>(raw);
       const bool is_s = in && key > T, is_t = in && key == T;
       const unsigned long long ms = __ballot(is_s), mt = __ballot(is_t);
       const long long sb = s_before + __builtin_amdgcn_mbcnt_hi((unsigned)(ms >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ms, 0u));
@@ -2476,6 +2502,18 @@ int check_topk(const float* x, int64_t n, int64_t k, const char* who) {
   return FLC_OK;
 }
 
+int check_order(int order, const char* who) {
+  if (order != FLC_ORDER_SIGNED && order != FLC_ORDER_MAGNITUDE)
+    return fail(FLC_EINVAL, "%s: order must be FLC_ORDER_SIGNED or FLC_ORDER_MAGNITUDE (got %d)", who, order);
+  return FLC_OK;
+}
+
+// f(source in the call's selection order): the magnitude instances take the same source wrapped in MagSrc
+template <class Src, class F>
+int with_order(const Src& src, int order, F&& f) {
+  return order == FLC_ORDER_MAGNITUDE ? f(MagSrc<Src>{src}) : f(src);
+}
+
 }  // namespace
 }  // namespace flc
 
@@ -2491,12 +2529,20 @@ size_t flc_topk_workspace_size(int64_t n, int64_t k) {
 
 // (idx, val and tiles inside a flc_sparse_wire_layout(n, k) record: the call writes the top-k compressor's sparse
 // record, compressors.py:293-296 — wire.hip folds a round of them)
+int flc_topk_encode_tiled_ord(const float* x, int64_t n, int64_t k, int order, int32_t* idx, float* val,
+                              uint32_t* tiles, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_topk(x, n, k, "flc_topk_encode")) return rc;
+  if (int rc = check_order(order, "flc_topk_encode")) return rc;
+  if (!idx || !val) return fail(FLC_EINVAL, "flc_topk_encode: null output");
+  return with_order(FlatSrc{x}, order, [&](const auto& src) {
+    return launch_topk<false>(src, n, k, ws, ws_bytes, as_stream(stream), idx, val, nullptr, nullptr, 0, 0, 0, tiles,
+                              "flc_topk_encode");
+  });
+}
+
 int flc_topk_encode_tiled(const float* x, int64_t n, int64_t k, int32_t* idx, float* val, uint32_t* tiles, void* ws,
                           size_t ws_bytes, void* stream) {
-  if (int rc = check_topk(x, n, k, "flc_topk_encode")) return rc;
-  if (!idx || !val) return fail(FLC_EINVAL, "flc_topk_encode: null output");
-  return launch_topk<false>(FlatSrc{x}, n, k, ws, ws_bytes, as_stream(stream), idx, val, nullptr, nullptr, 0, 0, 0, tiles,
-                            "flc_topk_encode");
+  return flc_topk_encode_tiled_ord(x, n, k, FLC_ORDER_SIGNED, idx, val, tiles, ws, ws_bytes, stream);
 }
 
 int flc_topk_encode(const float* x, int64_t n, int64_t k, int32_t* idx, float* val, void* ws, size_t ws_bytes,
@@ -2504,17 +2550,27 @@ int flc_topk_encode(const float* x, int64_t n, int64_t k, int32_t* idx, float* v
   return flc_topk_encode_tiled(x, n, k, idx, val, nullptr, ws, ws_bytes, stream);
 }
 
-int flc_stacked_encode_tiled(const float* x, int64_t n, int64_t k, int levels, uint64_t seed, uint64_t counter,
-                             const double* compat_u, int32_t* idx, uint8_t* codes, float* norm, uint32_t* tiles,
-                             void* ws, size_t ws_bytes, void* stream) {
+int flc_stacked_encode_tiled_ord(const float* x, int64_t n, int64_t k, int order, int levels, uint64_t seed,
+                                 uint64_t counter, const double* compat_u, int32_t* idx, uint8_t* codes, float* norm,
+                                 uint32_t* tiles, void* ws, size_t ws_bytes, void* stream) {
   if (int rc = check_topk(x, n, k, "flc_stacked_encode")) return rc;
+  if (int rc = check_order(order, "flc_stacked_encode")) return rc;
   if (!idx || !codes || !norm) return fail(FLC_EINVAL, "flc_stacked_encode: null output");
   if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "flc_stacked_encode: levels must be in [1, 127]");
   if (compat_u)
     return fail(FLC_EUNSUPPORTED,
                 "flc_stacked_encode: compat RNG is composed by the caller (flc_topk_encode + flc_quant_encode)");
-  return launch_topk<true>(FlatSrc{x}, n, k, ws, ws_bytes, as_stream(stream), idx, nullptr, codes, norm, levels, seed,
-                           counter, tiles, "flc_stacked_encode");
+  return with_order(FlatSrc{x}, order, [&](const auto& src) {
+    return launch_topk<true>(src, n, k, ws, ws_bytes, as_stream(stream), idx, nullptr, codes, norm, levels, seed,
+                             counter, tiles, "flc_stacked_encode");
+  });
+}
+
+int flc_stacked_encode_tiled(const float* x, int64_t n, int64_t k, int levels, uint64_t seed, uint64_t counter,
+                             const double* compat_u, int32_t* idx, uint8_t* codes, float* norm, uint32_t* tiles,
+                             void* ws, size_t ws_bytes, void* stream) {
+  return flc_stacked_encode_tiled_ord(x, n, k, FLC_ORDER_SIGNED, levels, seed, counter, compat_u, idx, codes, norm,
+                                      tiles, ws, ws_bytes, stream);
 }
 
 int flc_stacked_encode(const float* x, int64_t n, int64_t k, int levels, uint64_t seed, uint64_t counter,
@@ -2531,10 +2587,12 @@ size_t flc_stacked_encode_delta_workspace_size(int64_t n, int64_t k, int n_tenso
   return align_up(flc_topk_workspace_size(n, k), 256) + delta_table_bytes(n_tensors < 0 ? 0 : n_tensors);
 }
 
-int flc_stacked_encode_delta(const float* const* local, const float* const* global, const int64_t* sizes,
-                             int n_tensors, int64_t k, int levels, uint64_t seed, uint64_t counter, int32_t* idx,
-                             uint8_t* codes, float* norm, uint32_t* tiles, void* ws, size_t ws_bytes, void* stream) {
+int flc_stacked_encode_delta_ord(const float* const* local, const float* const* global, const int64_t* sizes,
+                                 int n_tensors, int64_t k, int order, int levels, uint64_t seed, uint64_t counter,
+                                 int32_t* idx, uint8_t* codes, float* norm, uint32_t* tiles, void* ws, size_t ws_bytes,
+                                 void* stream) {
   if (n_tensors <= 0 || !local || !global || !sizes) return fail(FLC_EINVAL, "flc_stacked_encode_delta: bad arguments");
+  if (int rc = check_order(order, "flc_stacked_encode_delta")) return rc;
   if (!idx || !codes || !norm) return fail(FLC_EINVAL, "flc_stacked_encode_delta: null output");
   if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "flc_stacked_encode_delta: levels must be in [1, 127]");
   std::vector<long long> off((size_t)n_tensors + 1, 0);
@@ -2568,8 +2626,17 @@ int flc_stacked_encode_delta(const float* const* local, const float* const* glob
   src.t.lp = reinterpret_cast<const float* const*>(tab + off.size() * 8);
   src.t.gp = reinterpret_cast<const float* const*>(tab + off.size() * 8 + (size_t)n_tensors * 8);
   src.t.nseg = n_tensors;
-  return launch_topk<true>(src, n, k, ws, enc, st, idx, nullptr, codes, norm, levels, seed, counter, tiles,
-                           "flc_stacked_encode_delta");
+  return with_order(src, order, [&](const auto& sx) {
+    return launch_topk<true>(sx, n, k, ws, enc, st, idx, nullptr, codes, norm, levels, seed, counter, tiles,
+                             "flc_stacked_encode_delta");
+  });
+}
+
+int flc_stacked_encode_delta(const float* const* local, const float* const* global, const int64_t* sizes,
+                             int n_tensors, int64_t k, int levels, uint64_t seed, uint64_t counter, int32_t* idx,
+                             uint8_t* codes, float* norm, uint32_t* tiles, void* ws, size_t ws_bytes, void* stream) {
+  return flc_stacked_encode_delta_ord(local, global, sizes, n_tensors, k, FLC_ORDER_SIGNED, levels, seed, counter, idx,
+                                      codes, norm, tiles, ws, ws_bytes, stream);
 }
 
 size_t flc_stacked_encode_batch_workspace_size(int64_t n, int64_t k, int n_clients) {
@@ -2581,11 +2648,12 @@ size_t flc_stacked_encode_batch_workspace_size(int64_t n, int64_t k, int n_clien
 namespace {
 // the flat batched stacked encode: client c's Philox counter is counters[c] (null: `counter` for every client), its
 // send count goes to counts[c] (counts null: none)
-int stacked_encode_flat_batch(const char* who, const float* const* xs, int n_clients, int64_t n, int64_t k, int levels,
-                              const uint64_t* seeds, const uint64_t* counters, uint64_t counter, int32_t* const* idx,
+int stacked_encode_flat_batch(const char* who, const float* const* xs, int n_clients, int64_t n, int64_t k, int order,
+                              int levels, const uint64_t* seeds, const uint64_t* counters, uint64_t counter, int32_t* const* idx,
                               uint8_t* const* codes, float* const* norm, uint32_t* const* tiles,
                               int64_t* const* counts, void* ws, size_t ws_bytes, void* stream) {
   if (n_clients <= 0 || !xs || !seeds || !idx || !codes || !norm) return fail(FLC_EINVAL, "%s: bad arguments", who);
+  if (int rc = check_order(order, who)) return rc;
   if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "%s: levels must be in [1, 127]", who);
   std::vector<BatchEntry> ents((size_t)n_clients);
   for (int c = 0; c < n_clients; ++c) {
@@ -2596,7 +2664,9 @@ int stacked_encode_flat_batch(const char* who, const float* const* xs, int n_cli
                          counters ? counters[c] : counter,
                          counts ? reinterpret_cast<unsigned long long*>(counts[c]) : nullptr};
   }
-  return launch_topk_batch(FlatSrc{nullptr}, ents, {}, n, k, levels, ws, ws_bytes, as_stream(stream), who);
+  return with_order(FlatSrc{nullptr}, order, [&](const auto& proto) {
+    return launch_topk_batch(proto, ents, {}, n, k, levels, ws, ws_bytes, as_stream(stream), who);
+  });
 }
 }  // namespace
 
@@ -2605,17 +2675,26 @@ extern "C" {
 int flc_stacked_encode_batch(const float* const* xs, int n_clients, int64_t n, int64_t k, int levels,
                              const uint64_t* seeds, uint64_t counter, int32_t* const* idx, uint8_t* const* codes,
                              float* const* norm, uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream) {
-  return stacked_encode_flat_batch("flc_stacked_encode_batch", xs, n_clients, n, k, levels, seeds, nullptr, counter, idx,
+  return stacked_encode_flat_batch("flc_stacked_encode_batch", xs, n_clients, n, k, FLC_ORDER_SIGNED, levels, seeds,
+                                   nullptr, counter, idx,
                                    codes, norm, tiles, nullptr, ws, ws_bytes, stream);
+}
+
+int flc_stacked_encode_round_ord(const float* const* xs, int n_clients, int64_t n, int64_t k, int order, int levels,
+                                 const uint64_t* seeds, const uint64_t* counters, int32_t* const* idx,
+                                 uint8_t* const* codes, float* const* norm, uint32_t* const* tiles,
+                                 int64_t* const* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (!counters) return fail(FLC_EINVAL, "flc_stacked_encode_round: null counters");
+  return stacked_encode_flat_batch("flc_stacked_encode_round", xs, n_clients, n, k, order, levels, seeds, counters, 0,
+                                   idx, codes, norm, tiles, counts, ws, ws_bytes, stream);
 }
 
 int flc_stacked_encode_round(const float* const* xs, int n_clients, int64_t n, int64_t k, int levels,
                              const uint64_t* seeds, const uint64_t* counters, int32_t* const* idx,
                              uint8_t* const* codes, float* const* norm, uint32_t* const* tiles, int64_t* const* counts,
                              void* ws, size_t ws_bytes, void* stream) {
-  if (!counters) return fail(FLC_EINVAL, "flc_stacked_encode_round: null counters");
-  return stacked_encode_flat_batch("flc_stacked_encode_round", xs, n_clients, n, k, levels, seeds, counters, 0, idx,
-                                   codes, norm, tiles, counts, ws, ws_bytes, stream);
+  return flc_stacked_encode_round_ord(xs, n_clients, n, k, FLC_ORDER_SIGNED, levels, seeds, counters, idx, codes, norm,
+                                      tiles, counts, ws, ws_bytes, stream);
 }
 
 size_t flc_topk_encode_batch_workspace_size(int64_t n, int64_t k, int n_clients) {
@@ -2624,17 +2703,27 @@ size_t flc_topk_encode_batch_workspace_size(int64_t n, int64_t k, int n_clients)
 
 // (idx[c], val[c] and tiles[c] inside client c's flc_sparse_wire_layout(n, k) record: a round's sparse records,
 // compressors.py:293-296 per client, in one call)
-int flc_topk_encode_batch(const float* const* xs, int n_clients, int64_t n, int64_t k, int32_t* const* idx,
-                          float* const* val, uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream) {
+int flc_topk_encode_batch_ord(const float* const* xs, int n_clients, int64_t n, int64_t k, int order,
+                              int32_t* const* idx, float* const* val, uint32_t* const* tiles, void* ws, size_t ws_bytes,
+                              void* stream) {
   const char* who = "flc_topk_encode_batch";
   if (n_clients <= 0 || !xs || !idx || !val) return fail(FLC_EINVAL, "%s: bad arguments", who);
+  if (int rc = check_order(order, who)) return rc;
   std::vector<BatchEntry> ents((size_t)n_clients);
   for (int c = 0; c < n_clients; ++c) {
     if (int rc = check_topk(xs[c], n, k, who)) return rc;
     if (!idx[c] || !val[c]) return fail(FLC_EINVAL, "%s: null output of client %d", who, c);
     ents[c] = BatchEntry{xs[c], 0, idx[c], nullptr, nullptr, tiles ? tiles[c] : nullptr, val[c], 0, nullptr};
   }
-  return launch_topk_batch<FlatSrc, false>(FlatSrc{nullptr}, ents, {}, n, k, 0, ws, ws_bytes, as_stream(stream), who);
+  return with_order(FlatSrc{nullptr}, order, [&](const auto& proto) {
+    using Src = std::decay_t<decltype(proto)>;
+    return launch_topk_batch<Src, false>(proto, ents, {}, n, k, 0, ws, ws_bytes, as_stream(stream), who);
+  });
+}
+
+int flc_topk_encode_batch(const float* const* xs, int n_clients, int64_t n, int64_t k, int32_t* const* idx,
+                          float* const* val, uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream) {
+  return flc_topk_encode_batch_ord(xs, n_clients, n, k, FLC_ORDER_SIGNED, idx, val, tiles, ws, ws_bytes, stream);
 }
 
 // the delta batch's tables: off[n_tensors + 1] (int64), the global pointers, then each client's local pointers
@@ -2654,12 +2743,13 @@ size_t flc_stacked_encode_delta_batch_workspace_size(int64_t n, int64_t k, int n
 namespace {
 // the delta batched stacked encode; counters / counter / counts as stacked_encode_flat_batch
 int stacked_encode_delta_batch(const char* who, const float* const* local, const float* const* global,
-                               const int64_t* sizes, int n_tensors, int n_clients, int64_t k, int levels,
+                               const int64_t* sizes, int n_tensors, int n_clients, int64_t k, int order, int levels,
                                const uint64_t* seeds, const uint64_t* counters, uint64_t counter, int32_t* const* idx,
                                uint8_t* const* codes, float* const* norm, uint32_t* const* tiles,
                                int64_t* const* counts, void* ws, size_t ws_bytes, void* stream) {
   if (n_tensors <= 0 || n_clients <= 0 || !local || !global || !sizes || !seeds || !idx || !codes || !norm)
     return fail(FLC_EINVAL, "%s: bad arguments", who);
+  if (int rc = check_order(order, who)) return rc;
   if (levels < 1 || levels > 127) return fail(FLC_EINVAL, "%s: levels must be in [1, 127]", who);
   std::vector<long long> off((size_t)n_tensors + 1, 0);
   for (int t = 0; t < n_tensors; ++t) {
@@ -2699,7 +2789,9 @@ int stacked_encode_delta_batch(const char* who, const float* const* local, const
     ents[c] = BatchEntry{dx + o_lp + (size_t)c * n_tensors * 8, seeds[c], idx[c], codes[c], norm[c],
                          tiles ? tiles[c] : nullptr, nullptr, counters ? counters[c] : counter,
                          counts ? reinterpret_cast<unsigned long long*>(counts[c]) : nullptr};
-  return launch_topk_batch(proto, ents, extra, n, k, levels, ws, ws_bytes, as_stream(stream), who);
+  return with_order(proto, order, [&](const auto& px) {
+    return launch_topk_batch(px, ents, extra, n, k, levels, ws, ws_bytes, as_stream(stream), who);
+  });
 }
 }  // namespace
 
@@ -2710,7 +2802,18 @@ int flc_stacked_encode_delta_batch(const float* const* local, const float* const
                                    uint64_t counter, int32_t* const* idx, uint8_t* const* codes, float* const* norm,
                                    uint32_t* const* tiles, void* ws, size_t ws_bytes, void* stream) {
   return stacked_encode_delta_batch("flc_stacked_encode_delta_batch", local, global, sizes, n_tensors, n_clients, k,
-                                    levels, seeds, nullptr, counter, idx, codes, norm, tiles, nullptr, ws, ws_bytes,
+                                    FLC_ORDER_SIGNED, levels, seeds, nullptr, counter, idx, codes, norm, tiles, nullptr,
+                                    ws, ws_bytes, stream);
+}
+
+int flc_stacked_encode_delta_round_ord(const float* const* local, const float* const* global, const int64_t* sizes,
+                                       int n_tensors, int n_clients, int64_t k, int order, int levels,
+                                       const uint64_t* seeds, const uint64_t* counters, int32_t* const* idx,
+                                       uint8_t* const* codes, float* const* norm, uint32_t* const* tiles,
+                                       int64_t* const* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (!counters) return fail(FLC_EINVAL, "flc_stacked_encode_delta_round: null counters");
+  return stacked_encode_delta_batch("flc_stacked_encode_delta_round", local, global, sizes, n_tensors, n_clients, k,
+                                    order, levels, seeds, counters, 0, idx, codes, norm, tiles, counts, ws, ws_bytes,
                                     stream);
 }
 
@@ -2719,9 +2822,8 @@ int flc_stacked_encode_delta_round(const float* const* local, const float* const
                                    const uint64_t* counters, int32_t* const* idx, uint8_t* const* codes,
                                    float* const* norm, uint32_t* const* tiles, int64_t* const* counts, void* ws,
                                    size_t ws_bytes, void* stream) {
-  if (!counters) return fail(FLC_EINVAL, "flc_stacked_encode_delta_round: null counters");
-  return stacked_encode_delta_batch("flc_stacked_encode_delta_round", local, global, sizes, n_tensors, n_clients, k,
-                                    levels, seeds, counters, 0, idx, codes, norm, tiles, counts, ws, ws_bytes, stream);
+  return flc_stacked_encode_delta_round_ord(local, global, sizes, n_tensors, n_clients, k, FLC_ORDER_SIGNED, levels,
+                                            seeds, counters, idx, codes, norm, tiles, counts, ws, ws_bytes, stream);
 }
 
 // the pinned table ring's bookkeeping on its own (no device): ops are triples (kind, slot, stream id); kind 0 stages

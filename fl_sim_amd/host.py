@@ -56,7 +56,9 @@ class HostCodecPipeline:
             raise ValueError(f"{name}: host tensor must be pinned (torch.empty(..., pin_memory=True))")
 
     def run(self, host_xs: Sequence[torch.Tensor], host_outs: Sequence[torch.Tensor], k: int, levels: int = 127,
-            seeds: Optional[Sequence[int]] = None, counters: Optional[Sequence[int]] = None) -> List[int]:
+            seeds: Optional[Sequence[int]] = None, counters: Optional[Sequence[int]] = None,
+            order=codec.ORDER_SIGNED) -> List[int]:
+        """``order``: the top-k stage's selection order (codec.ORDER_*)."""
         if len(host_xs) != len(host_outs):
             raise ValueError("one output per client delta")
         m = len(host_xs)
@@ -82,7 +84,7 @@ class HostCodecPipeline:
                 self.s_comp.wait_event(loaded)
                 if self.out_free[b] is not None:
                     self.s_comp.wait_event(self.out_free[b])
-                pkt = codec.stacked_encode(self.x[b], k, levels, seed=seeds[i], counter=counters[i])
+                pkt = codec.stacked_encode(self.x[b], k, levels, seed=seeds[i], counter=counters[i], order=order)
                 codec.stacked_decode(pkt, out=self.out[b])
                 done = torch.cuda.Event()
                 done.record(self.s_comp)
@@ -161,9 +163,10 @@ class HostWirePipeline:
             s.wait_stream(cur)
 
     def encode(self, host_xs: Sequence[torch.Tensor], wires: Sequence[HostWire], seeds: Optional[Sequence[int]] = None,
-               counters: Optional[Sequence[int]] = None) -> None:
+               counters: Optional[Sequence[int]] = None, order=codec.ORDER_SIGNED) -> None:
         """Client side: ``host_xs[i]`` (pinned fp32) -> ``wires[i]`` (pinned).  Asynchronous; ``synchronize()``
-        before reading the wires on the host."""
+        before reading the wires on the host.  ``order``: the top-k stage's selection order (codec.ORDER_*); the wire
+        and the server side do not depend on it."""
         m = len(host_xs)
         if len(wires) != m:
             raise ValueError("one wire per client delta")
@@ -187,7 +190,7 @@ class HostWirePipeline:
                 if self.wire_free[b] is not None:
                     self.s_comp.wait_event(self.wire_free[b])  # record b drained to the host
                 codec.stacked_encode(self.x[b], self.k, self.levels, seed=seeds[i], counter=counters[i],
-                                     wire=self.rec[b])
+                                     wire=self.rec[b], order=order)
                 done = torch.cuda.Event()
                 done.record(self.s_comp)
                 self.in_free[b] = done

@@ -681,6 +681,51 @@ int flc_stacked_encode_delta_round(const float* const* local, const float* const
                                    float* const* norm, uint32_t* const* tiles, int64_t* const* counts, void* ws,
                                    size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ top-k by magnitude (selection order)
+ * compressors.py:293-296 keeps the K largest *signed* values (`out[np.argsort(out)[:-K]] = 0`); that is
+ * FLC_ORDER_SIGNED, the order of every entry point above.  FLC_ORDER_MAGNITUDE keeps the K largest |x| instead (the
+ * top-k of Aji & Heafield, Deep Gradient Compression and Stich et al.): the kept index set is exactly the signed
+ * select's on |x| — a NaN of either sign is the largest magnitude, -0 == +0, +v and -v tie, and among the entries tied
+ * with the K-th largest magnitude the highest indices are kept — and each kept value is x's own, sign included, bit
+ * for bit.  The stacked pipeline's second stage is unchanged and runs on the kept values: norm = max|kept| = max|x|,
+ * the Philox word by element id, the code's sign bit the kept value's own sign.  flc_topk_select_stats reports the
+ * signed select's diagnostics on |x|; flc_topk_select_plan and every workspace size do not depend on the order.
+ *
+ * Each `_ord` entry is the entry of the same name with `order` after k; the entries above are its order = 0 case.
+ * Any other order returns FLC_EINVAL and launches nothing. */
+enum { FLC_ORDER_SIGNED = 0, FLC_ORDER_MAGNITUDE = 1 };
+/* compressors.py:293-296 by |x| (order 1): the sparse record of flc_topk_encode_tiled; tiles may be NULL */
+int flc_topk_encode_tiled_ord(const float* x, int64_t n, int64_t k, int order, int32_t* idx, float* val,
+                              uint32_t* tiles, void* ws, size_t ws_bytes, void* stream);
+/* compressors.py:293-296 by |x| per client: flc_topk_encode_batch */
+int flc_topk_encode_batch_ord(const float* const* xs, int n_clients, int64_t n, int64_t k, int order,
+                              int32_t* const* idx, float* const* val, uint32_t* const* tiles, void* ws, size_t ws_bytes,
+                              void* stream);
+/* compressors.py:293-296 by |x|, then 327-365 on the kept values: flc_stacked_encode_tiled; tiles may be NULL */
+int flc_stacked_encode_tiled_ord(const float* x, int64_t n, int64_t k, int order, int levels, uint64_t seed,
+                                 uint64_t counter, const double* compat_u, int32_t* idx, uint8_t* codes, float* norm,
+                                 uint32_t* tiles, void* ws, size_t ws_bytes, void* stream);
+/* the same on the client delta local - global formed in the read pass (|local - global|: the magnitude is taken after
+ * the subtraction): flc_stacked_encode_delta */
+int flc_stacked_encode_delta_ord(const float* const* local, const float* const* global, const int64_t* sizes,
+                                 int n_tensors, int64_t k, int order, int levels, uint64_t seed, uint64_t counter,
+                                 int32_t* idx, uint8_t* codes, float* norm, uint32_t* tiles, void* ws, size_t ws_bytes,
+                                 void* stream);
+/* a round's clients in one launch, compressors.py:293-296 by |x| per client: flc_stacked_encode_round and
+ * flc_stacked_encode_delta_round (one order for the whole call) */
+int flc_stacked_encode_round_ord(const float* const* xs, int n_clients, int64_t n, int64_t k, int order, int levels,
+                                 const uint64_t* seeds, const uint64_t* counters, int32_t* const* idx,
+                                 uint8_t* const* codes, float* const* norm, uint32_t* const* tiles,
+                                 int64_t* const* counts, void* ws, size_t ws_bytes, void* stream);
+int flc_stacked_encode_delta_round_ord(const float* const* local, const float* const* global, const int64_t* sizes,
+                                       int n_tensors, int n_clients, int64_t k, int order, int levels,
+                                       const uint64_t* seeds, const uint64_t* counters, int32_t* const* idx,
+                                       uint8_t* const* codes, float* const* norm, uint32_t* const* tiles,
+                                       int64_t* const* counts, void* ws, size_t ws_bytes, void* stream);
+/* compressors.py:293-296 by |x| in float64: flc_topk_dense_f64 (declared with the float64 forms below) */
+int flc_topk_dense_f64_ord(const double* x, int64_t n, int64_t k, int order, double* out, void* ws, size_t ws_bytes,
+                           void* stream);
+
 /* ------------------------------------------------------------------ other compressors
  * identical (compressors.py:273-275): out = +x;  lazy (276-283): out = x / p (fp32 division);
  * rand-k (284-292): out = 0, out[idx[j]] = scale * x[idx[j]] (idx in any order, unique). */
