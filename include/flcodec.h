@@ -173,10 +173,15 @@ size_t flc_bucket_wire_layout(int64_t n, int format, int bits, int64_t bucket, i
  * 376-404 the level choice, per slice): every bucket's norm is computed from values that stay in registers until the
  * level decision.  p = inf: the exact max of the |x| bits, NaN-propagating (flc_quant_norm's); p = 2: fp32(sqrt(S)),
  * S the fp64 sum of the bucket's squares in an order fixed by B and the position in the bucket (elements past n count
- * as +0), never by the grid.  Element e uses Philox word e & 3 of counter group e >> 2, e the index in the whole
- * message, through the tail bucket.  For n a multiple of B and p = inf the norms and codes are those of flc_quant_norm
- * + flc_quant_encode on the [n / B, B] batch with the same (seed, counter).  norms_given != 0: the norms are read
- * from `norms` instead (host-computed reference norms).  norms: nb floats; codes: ceil(n * bits / 8) bytes, 16-B
+ * as +0), never by the grid: per run of 8 consecutive elements a chain ss = ss + fp64(v)^2 in index order from 0.0,
+ * a balanced pairwise tree over min(B / 8, 64) adjacent runs, then for B >= 1024 r = 0.0, r += (sum of 512 elements)
+ * over the bucket's B / 512 such sums in index order.  A subnormal fp32(sqrt(S)) is kept (not flushed: the bucket
+ * encodes under it); where fp32(sqrt(S)) overflows (sqrt(S) > FLT_MAX with every element finite) the norm is +inf and
+ * the bucket takes the rule for a norm of +inf below.  Element e uses Philox word e & 3 of counter group e >> 2, e the
+ * index in the whole message, through the tail bucket.  For n a multiple of B and p = inf the norms and codes are
+ * those of flc_quant_norm + flc_quant_encode on the [n / B, B] batch with the same (seed, counter).  norms_given != 0:
+ * the norms are read from `norms` instead (host-computed reference norms).  norms: nb floats; codes:
+ * ceil(n * bits / 8) bytes, 16-B
  * aligned (a record's fields, or any buffers).  nnz (device int64, optional): the message's count of x != 0, zeroed in
  * the stream by the call.  out (optional, n floats, 16-B aligned): the decoder's value of every code, from registers —
  * compressVector's result.  A bucket whose norm is 0, +-inf or NaN encodes code 0 for x == 0 and code 1 otherwise,
@@ -197,8 +202,12 @@ int flc_bucket_encode_round(const float* const* xs, int n_msgs, int64_t n, int k
                             int64_t bucket, int norm_p, int norms_given, const uint64_t* seeds,
                             const uint64_t* counters, float* const* norms, uint8_t* const* codes,
                             int64_t* const* counts, void* stream);
-/* decode (compressors.py:357 / 394 per slice): v = fp32(fp32(level_value) * sign) * norms[e / B];
- * out = accumulate ? fmaf(weight, v, out) : weight * v  (weight 1: v itself).  FLC_EINVAL as flc_bucket_encode. */
+/* decode (compressors.py:357 / 394 per slice): v = fp32(fp32(level_value) * sign) * norms[e / B] where that norm is
+ * regular, nrm > 0 && nrm <= FLT_MAX (a subnormal one included); under any other norm — +-0, negative, +-inf, NaN —
+ * code 0 gives +0 and every other code NaN, inside that bucket only (flc_quant_decode's rule per bucket; the encoder
+ * never writes a negative norm, a hand-made record may hold one).  The sign bit with level 0 decodes to -0 * norm.
+ * out = accumulate ? fmaf(weight, v, out) : weight * v  (weight 1: v itself); nothing is written past n, and the
+ * record's padding is never interpreted.  FLC_EINVAL as flc_bucket_encode. */
 int flc_bucket_decode(const uint8_t* codes, int64_t n, int kind, int levels, int bits, int64_t bucket,
                       const float* norms, float weight, int accumulate, float* out, void* stream);
 
@@ -206,7 +215,9 @@ int flc_bucket_decode(const uint8_t* codes, int64_t n, int kind, int levels, int
  * flc_fedopt_fold_dense_records, flc_avg_and_gradient_dense_records and flc_fold_dense_record_groups (below) with the
  * records laid out by flc_bucket_wire_layout(n, format, bits, bucket) and the norm of element e read from
  * (record, e / bucket) — the server's weighted aggregation (nodes.py:1165-1180 / _fedopt.py:202-208) fused with the
- * per-slice decode of compressors.py:357 / 394.  Each is bit-identical to decoding every record with flc_bucket_decode
+ * per-slice decode of compressors.py:357 / 394, flc_bucket_decode's rule for a norm that is not regular applied per
+ * bucket (a negative, -0 or -inf norm beside a regular one changes that bucket only).  Each is bit-identical to
+ * decoding every record with flc_bucket_decode
  * and running the dense entry point its counterpart names (flc_quant_decode(accumulate = 1) chains, flc_model_fold,
  * flc_avg_and_gradients, flc_weighted_sum per group).  Arguments, chaining per 64 records and FLC_EINVAL cases as the
  * dense forms, plus a bucket that is not a power of two in [64, 4096] and format FLC_WIRE_NATURAL (no norm). */
