@@ -17,9 +17,9 @@ there is no CPU fallback.
 import os
 
 from . import _lib
-from .compressors import Compressor, CompressorType
+from .compressors import Compressor, CompressorType, SignCompressor
 
-__all__ = ["Compressor", "CompressorType", "native_library", "load_torch_ops", "__version__"]
+__all__ = ["Compressor", "CompressorType", "SignCompressor", "native_library", "load_torch_ops", "__version__"]
 __version__ = "0.1.0"
 
 

@@ -99,6 +99,25 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_int,
          c_void_p],
     ),
+    "flc_sign_wire_layout": (c_size_t, [c_int64, c_int64, c_void_p]),
+    "flc_sign_workspace_size": (c_size_t, [c_int64, c_int64]),
+    "flc_sign_encode": (
+        c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    ),
+    "flc_sign_decode": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_float, c_int, c_void_p, c_void_p]),
+    "flc_fold_sign_wires": (
+        c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p]
+    ),
+    "flc_fedopt_fold_sign_records": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int,
+         c_double, c_double, c_double, c_void_p],
+    ),
+    "flc_avg_and_gradient_sign_records": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                  c_int64, c_int64, c_void_p, c_int, c_float, c_void_p]),
+    "flc_fold_sign_record_groups": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p]
+    ),
     "flc_count_consumers": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "flc_natural_workspace_size": (c_size_t, [c_int64]),
     "flc_natural_encode": (

@@ -525,6 +525,74 @@ def bucket_decode(record: torch.Tensor, n: int, kind: int, levels: int, bits: in
     return out
 
 
+# --------------------------------------------------------------------------------------- sign records
+_SIGN_LAYOUT: Dict[tuple, tuple] = {}
+
+
+def sign_wire_layout(n: int, bucket: int = 0):
+    """(record bytes, {"scales", "bits"} byte offsets) of a scaled-sign record (flc_sign_wire_layout): the
+    ``ceil(n / bucket)`` fp32 scales (one for ``bucket == 0``), then one bit per element."""
+    import ctypes
+
+    key = (int(n), int(bucket))
+    r = _SIGN_LAYOUT.get(key)
+    if r is None:
+        off = (ctypes.c_int64 * 2)()
+        total = _lib.size("flc_sign_wire_layout", key[0], key[1], ctypes.cast(off, ctypes.c_void_p))
+        if total == 0:
+            raise ValueError(f"bad sign record shape n={n}, bucket={bucket}")
+        r = _SIGN_LAYOUT[key] = (int(total), {"scales": int(off[0]), "bits": int(off[1])})
+    return r
+
+
+def sign_wire_views(record: torch.Tensor, n: int, bucket: int = 0):
+    """(scales, bits) views into a sign record (a contiguous uint8 HIP tensor of at least ``sign_wire_layout(...)[0]``
+    bytes, 16-B aligned): the per-bucket fp32 scales and the ``ceil(n / 8)`` bytes of the bit stream."""
+    stride, off = sign_wire_layout(n, bucket)
+    if record.dtype != torch.uint8 or record.device.type != "cuda" or not record.is_contiguous():
+        raise TypeError("a wire record is a contiguous uint8 HIP tensor")
+    rec = record.reshape(-1)
+    if rec.numel() < stride or rec.data_ptr() % 16 != 0:
+        raise ValueError(f"a sign record needs {stride} bytes, 16-B aligned")
+    nb = (n + bucket - 1) // bucket if bucket else 1
+    return (rec[off["scales"]:off["scales"] + 4 * nb].view(torch.float32), rec[off["bits"]:off["bits"] + (n + 7) // 8])
+
+
+def sign_encode(x: torch.Tensor, bucket: int = 0, record: Optional[torch.Tensor] = None, decode: bool = False,
+                residual: Optional[torch.Tensor] = None):
+    """One message as a scaled-sign record (flc_sign_encode): per bucket ``scale = fp32(sum|x| / m)`` and one sign bit
+    per element, in one launch that reads ``x`` once (two for ``bucket == 0``).  ``decode``: also the decoded vector
+    ``±scale``; ``residual`` (n floats, may be ``x`` itself): receives ``x - decoded`` in the same pass.  Returns
+    ``(record, decoded or None)``; ``record`` is allocated when not given."""
+    x = _dev_f32(x).reshape(-1)
+    n, dev = x.numel(), x.device
+    stride, _ = sign_wire_layout(n, bucket)
+    if record is None:
+        record = torch.empty(stride, dtype=torch.uint8, device=dev)
+    sv, bv = sign_wire_views(record, n, bucket)
+    if residual is not None and (residual.dtype != torch.float32 or residual.device != dev or residual.numel() != n
+                                 or not residual.is_contiguous()):
+        raise ValueError("residual must be a contiguous float32 tensor of x's size on x's device")
+    out = torch.empty(n, dtype=torch.float32, device=dev) if decode else None
+    need = _lib.size("flc_sign_workspace_size", n, bucket)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    call("flc_sign_encode", _p(x), n, bucket, _p(sv), _p(bv), _p(out), _p(residual), _p(ws), need, _stream(dev))
+    return record, out
+
+
+def sign_decode(record: torch.Tensor, n: int, bucket: int = 0, out: Optional[torch.Tensor] = None,
+                weight: float = 1.0, accumulate: bool = False) -> torch.Tensor:
+    """The decoded flat vector of a sign record (flc_sign_decode): ``v = bit ? -scale : scale``;
+    ``out = fmaf(weight, v, out)`` when accumulating, ``weight * v`` otherwise."""
+    sv, bv = sign_wire_views(record, n, bucket)
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs an out tensor")
+        out = torch.empty(n, dtype=torch.float32, device=record.device)
+    call("flc_sign_decode", _p(bv), n, bucket, _p(sv), float(weight), int(accumulate), _p(out), _stream(out.device))
+    return out
+
+
 def fold_dense_wires(wires: torch.Tensor, slots: Sequence[int], weights: Sequence[float], n: int, fmt: int,
                      levels: int, bits: int, out: Optional[torch.Tensor] = None,
                      accumulate: bool = False) -> torch.Tensor:

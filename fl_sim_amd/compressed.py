@@ -116,7 +116,7 @@ import torch
 from . import _lib, codec
 from ._lib import FLC_NORM_INF, FLC_NORM_L2, FLC_Q_NATURAL_DITHER, FLC_Q_STANDARD_DITHER, FLC_WIRE_NATURAL
 from . import rng as _rng
-from .compressors import Compressor, CompressorType
+from .compressors import Compressor, CompressorType, SignCompressor
 from .feedback import ErrorFeedbackClientMixin, ErrorMemory
 
 
@@ -154,13 +154,15 @@ class CompressedDelta(_abc.Sequence):
     dense record of a dithering quantizer (its norm and packed ``bits``-bit codes) or of the natural compressor (one
     uint16 per element), ``format`` being flc_dense_wire_layout's; ``kind == "bucket"`` (``wire=True`` with a bucket
     size): the bucket record of a bucketed dithering quantizer (one norm per ``bucket`` elements, then the packed codes;
-    flc_bucket_wire_layout); ``kind == "dense"``: the decoded flat delta.
+    flc_bucket_wire_layout); ``kind == "sign"`` (``wire=True`` with a :class:`SignCompressor`): the scaled-sign record
+    (one scale per bucket, then one bit per element; flc_sign_wire_layout); ``kind == "dense"``: the decoded flat delta.
     Indexing gives tensor ``j`` of the model's shapes (the decoded values, one flat decode on first access), so code
     written for a list of delta tensors reads it unchanged."""
 
     def __init__(self, shapes: Sequence[torch.Size], device: torch.device, n: int, *, record=None, k: int = 0,
                  levels: int = 0, flat: Optional[torch.Tensor] = None, batch: Optional["_Batch"] = None,
-                 format: Optional[int] = None, bits: int = 0, sparse: bool = False, bucket: int = 0):
+                 format: Optional[int] = None, bits: int = 0, sparse: bool = False, bucket: int = 0,
+                 sign: bool = False):
         self.shapes = [torch.Size(s) for s in shapes]
         self.device = device
         self.n = int(n)
@@ -168,7 +170,9 @@ class CompressedDelta(_abc.Sequence):
         self._batch = batch  # (a deferred encode: the record is made by the batch's launch on first access)
         self.format, self.bits = format, int(bits)
         self.bucket = int(bucket)  # a bucket record's bucket size (flc_bucket_wire_layout), else 0
-        if format is not None and self.bucket:
+        if sign:  # (a scaled-sign record, flc_sign_wire_layout(n, bucket): bucket 0 is the whole vector)
+            self.kind = "sign"
+        elif format is not None and self.bucket:
             self.kind = "bucket"
         elif format is not None:
             self.kind = "natural" if format == FLC_WIRE_NATURAL else "quant"
@@ -198,7 +202,7 @@ class CompressedDelta(_abc.Sequence):
             self._batch.run()
         d = self.__dict__.copy()
         d["_batch"] = None
-        if self.kind in ("quant", "natural", "bucket"):
+        if self.kind in ("quant", "natural", "bucket", "sign"):
             d["_flat"] = d["_views"] = None
         return d
 
@@ -215,7 +219,9 @@ class CompressedDelta(_abc.Sequence):
         """The decoded flat delta (flc_stacked_decode_tiled, flc_sparse_decode_tiled, flc_quant_decode or
         flc_natural_decode of the record, once)."""
         if self._flat is None:
-            if self.kind == "bucket":
+            if self.kind == "sign":
+                self._flat = codec.sign_decode(self.record, self.n, self.bucket)
+            elif self.kind == "bucket":
                 self._flat = codec.bucket_decode(self.record, self.n, self.format, self.levels, self.bits, self.bucket)
             elif self.kind in ("quant", "natural"):
                 self._flat = codec.dense_record_decode(self.record, self.n, self.format, self.levels, self.bits)
@@ -629,6 +635,23 @@ def _flatten(ts: Sequence[torch.Tensor], dev: torch.device) -> torch.Tensor:
     return torch.cat([t.reshape(-1) for t in _fp32_on(ts, dev)])
 
 
+def _sign_wire(compressors: Sequence[Compressor], wire: bool) -> Optional[SignCompressor]:
+    """The one :class:`SignCompressor` whose record a ``wire`` message carries, else None."""
+    if wire and len(compressors) == 1 and isinstance(compressors[0], SignCompressor):
+        return compressors[0]
+    return None
+
+
+def _sign_record(x: torch.Tensor, shapes, n: int, comp: SignCompressor, dev, feedback: bool = False) -> CompressedDelta:
+    """The scaled-sign record of the flat fp32 vector ``x`` in one flc_sign_encode; ``feedback``: ``x`` is the error
+    memory holding ``a``, and the same pass leaves ``e' = a − decode(record)`` in it."""
+    if n != comp.D:
+        raise ValueError(f"Sign compressor built for D={comp.D} applied to a message of {n} elements")
+    rec, _ = codec.sign_encode(x, comp.bucket, residual=x if feedback else None)
+    comp._finish(n, comp.send_components())
+    return CompressedDelta(shapes, dev, n, record=rec, bucket=comp.bucket, sign=True)
+
+
 def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
               compressors: Sequence[Compressor], wire: bool = False, sparse: bool = False,
               bucket: int = 0) -> CompressedDelta:
@@ -670,6 +693,9 @@ def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]
         if pipe is not None and 0 < pipe[0] < n:
             return _stacked(ls, gs, shapes, n, pipe[0], pipe[1], compressors[0], compressors[1], dev, seed_ctr)
         out = codec.delta_flatten(ls, gs)
+    sg = _sign_wire(compressors, wire)
+    if sg is not None and out.dtype == torch.float32:  # the 1-bit record as the message, nothing decoded
+        return _sign_record(out, shapes, n, sg, dev)
     dc = dense_wire_codec(compressors) if wire else None
     B = _bucket_of(compressors, bucket)
     if B and dc is not None and out.dtype == torch.float32:  # a bucket record: one norm per B elements, then the codes
@@ -744,6 +770,9 @@ def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torc
         d = _stacked(e, None, shapes, n, pipe[0], pipe[1], tk, sd, dev, seed_ctr)
         codec.ef_residual_round([d._record], [e], n, pipe[0], pipe[1])
         return d
+    sg = _sign_wire(compressors, wire)
+    if sg is not None:  # the memory is the encoder's input and its residual output: no decode, no residual launch
+        return _sign_record(e, shapes, n, sg, dev, feedback=True)
     dc = dense_wire_codec(compressors) if wire else None
     B = _bucket_of(compressors, bucket)
     if B:  # bucketed: encoded at once from the memory's values, then the plain dense residual of the decoded record
@@ -1275,7 +1304,7 @@ def _stacked(ls, gs, shapes, n: int, K: int, s: int, tk: Compressor, sd: Compres
     return CompressedDelta(shapes, dev, n, record=rec, k=K, levels=s)
 
 
-_RECORD_KINDS = ("stacked", "quant", "natural", "sparse", "bucket")
+_RECORD_KINDS = ("stacked", "quant", "natural", "sparse", "bucket", "sign")
 
 
 def _round_deltas(messages: Sequence, key: str, kinds: Tuple[str, ...]) -> Optional[List[CompressedDelta]]:
@@ -1341,15 +1370,19 @@ _STACKED = _entries("", codec._pyrecs, codec._pygrecs, codec._pygroups)
 _SPARSE = _entries("sparse_", codec._pysrecs, codec._pygsrecs, None)
 _DENSE = _entries("dense_", codec._pydrecs, codec._pygdrecs, None)
 _BUCKET = _entries("bucket_", lambda: None, lambda: None, None)  # (the C entries; no one-call _flcfold form)
-_MIXED = _entries("mixed_", codec._pymrecs, None, None)  # (a mixed_round: every record by its own descriptor)
+_SIGN = _entries("sign_", lambda: None, lambda: None, None)  # (likewise)
+_MIXED = _entries("mixed_",codec._pymrecs, None, None)  # (a mixed_round: every record by its own descriptor)
 
 
 def _record_entries(d0: CompressedDelta) -> Tuple[tuple, _Entries]:
     """(shape, entries) of a uniform round of ``d0``'s records — the one place that knows a kind's entry points.
     ``shape`` is what every entry of the kind takes after the record count: (n, k, levels) of stacked records, (n, k)
-    of sparse ones, (n, format, levels, bits) of dense ones, (n, format, levels, bits, bucket) of bucket ones."""
+    of sparse ones, (n, format, levels, bits) of dense ones, (n, format, levels, bits, bucket) of bucket ones,
+    (n, bucket) of sign ones."""
     if d0.kind == "sparse":
         return (d0.n, d0.k), _SPARSE
+    if d0.kind == "sign":
+        return (d0.n, d0.bucket), _SIGN
     if d0.kind == "bucket":
         return (d0.n, d0.format, d0.levels, d0.bits, d0.bucket), _BUCKET
     if d0.kind in ("quant", "natural"):
@@ -1401,7 +1434,7 @@ def mixed_round(messages: Sequence, key: str = "delta_parameters") -> Optional[L
             return None
         ds.append(d)
     d0 = ds[0]
-    if any(d.n != d0.n for d in ds) or all(d.kind in ("dense", "bucket") for d in ds):
+    if any(d.n != d0.n for d in ds) or all(d.kind in ("dense", "bucket", "sign") for d in ds):
         return None
     if all(d.codec_key == d0.codec_key for d in ds):
         return None
@@ -1419,7 +1452,7 @@ def _mixed_tables(deltas: Sequence[CompressedDelta], dev: torch.device, records=
     for i, d in enumerate(deltas):
         if d.kind == "dense":
             t, desc = d._flat, (_REC_FLAT, 0, 0, 0, 0)
-        elif d.kind == "bucket":  # (not in the mixed fold's descriptor tables: read as its decoded vector)
+        elif d.kind in ("bucket", "sign"):  # (not in the mixed fold's descriptor tables: read as its decoded vector)
             t, desc = d.flat(), (_REC_FLAT, 0, 0, 0, 0)
         else:
             t = d.record

@@ -47,7 +47,7 @@ from . import codec
 from . import rng as _rng
 from ._lib import FLC_Q_NATURAL_DITHER, FLC_Q_STANDARD_DITHER
 
-__all__ = ["CompressorType", "Compressor"]
+__all__ = ["CompressorType", "Compressor", "SignCompressor", "SIGN_COMPRESSOR"]
 
 
 @unique
@@ -760,3 +760,44 @@ class Compressor:
         if t in _NATURAL:
             return codec.natural_decode(packet, int(d if d is not None else packet.numel()))
         raise NotImplementedError(f"decode: {t}")
+
+
+SIGN_COMPRESSOR = "SIGN_COMPRESSOR"  # SignCompressor.compressorType: outside CompressorType, which stays the reference's
+
+
+class SignCompressor(Compressor):
+    """Scaled sign, ``C(x) = (||x||_1 / d) * sign(x)`` per bucket: EF-signSGD's compressor (Karimireddy et al., 2019),
+    one bit per element plus one fp32 scale per bucket of ``bucket`` elements (0: the whole vector).  Biased — use it
+    with error feedback.  An extension over the reference: its type is the sentinel ``SIGN_COMPRESSOR``, not a
+    ``CompressorType`` member.  Deterministic: no RNG draw."""
+
+    def __init__(self, D: int, bucket: int = 0):
+        super().__init__("SignCompressor", bucket=bucket)
+        if int(D) < 1:
+            raise ValueError(f"D must be >= 1 (got {D})")
+        self.D = int(D)
+
+    compressorType = property(lambda self: SIGN_COMPRESSOR)
+    is_biased = property(lambda self: True)
+    w = property(lambda self: 0.0)
+    name = property(lambda self: f"Scaled sign [D={self.D},B={self.bucket}]")
+    fullName = name
+
+    def send_components(self) -> float:
+        """fp32 components per message, counted as the reference counts: one per scale, 1/32 per sign bit."""
+        nb = (self.D + self.bucket - 1) // self.bucket if self.bucket else 1
+        return nb + self.D / 32.0
+
+    def compressVector(self, x):
+        """One flc_sign_encode with ``out`` (device and numpy inputs alike): the decoded vector ``±scale``."""
+        shape, dtype = tuple(x.shape), x.dtype  # (refusals first: nothing is copied or launched for them)
+        if len(shape) != 1 or shape[0] != self.D:
+            raise ValueError(f"Sign compressor built for D={self.D} applied to a vector of shape {shape}")
+        if str(dtype).endswith("float64"):  # (torch.float64 or numpy's)
+            raise ValueError("the sign compressor takes float32 vectors")
+        return super().compressVector(x)
+
+    def _compress_device(self, x: torch.Tensor, host_norm=None) -> torch.Tensor:
+        _, out = codec.sign_encode(x, self.bucket, decode=True)
+        self._finish(self.D, self.send_components())
+        return out

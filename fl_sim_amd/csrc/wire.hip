@@ -628,6 +628,9 @@ __global__ __launch_bounds__(kWave) void stacked_fold_wires_kernel(FoldArgs a, W
 // a = fmaf(w_c, v_c, a) with v_c the decoders' value of the code (dequant<KIND, BITS> in quant.hip, natural_value).
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kFmtNatural = 2;  // FLC_WIRE_NATURAL (0 / 1: FLC_Q_STANDARD_DITHER / FLC_Q_NATURAL_DITHER)
+// Sign records (flc_sign_wire_layout): internal only — RoundCodec::sign_records sets it, and no public `format`
+// argument reaches a launch with it (check_dense_format refuses 3)
+constexpr int kFmtSign = 3;
 constexpr long long kDenseNorm = 0, kDenseCodes = 16;
 
 struct DenseCodec {
@@ -665,6 +668,7 @@ __device__ __forceinline__ typename Quad<BITS>::type load_quad(const uint8_t* __
   if constexpr (BITS == 16) return *reinterpret_cast<const uint2*>(p);
   else if constexpr (BITS == 8) return *reinterpret_cast<const uint32_t*>(p);
   else if constexpr (BITS == 4) return (uint32_t)*reinterpret_cast<const uint16_t*>(p);
+  else if constexpr (BITS == 1) return (uint32_t)*p >> (e & 4);  // (the byte's nibble of the four elements)
   else return (uint32_t)*p;
 }
 template <int BITS>
@@ -679,16 +683,18 @@ __device__ __forceinline__ uint32_t quad_code(const typename Quad<BITS>::type& q
 // fp32(level value) comes from an LDS table of all 2^(BITS-1) level fields (dequant's (float)level_value, as
 // quant_fused_kernel's s_lvt), so a code decodes exactly as flc_quant_decode decodes it, whatever its level field.
 // BKT: bucket records — the norm of element e is norms[e >> logb], the codes start at codes_off.
+// KIND 3 (kFmtSign, BITS 1): sign records — v = bit ? -scale : scale, the scale read as the norms are (a whole-vector
+// record's scales[0] lies where a dense record's norm does, its bits where the codes do); no level table.
 template <int KIND, int BITS, class IO, bool BKT = false>
 __global__ __launch_bounds__(kWave) void dense_fold_records_kernel(FoldArgs a, int nw_all, int s, double step,
                                                                    int64_t n, int64_t tile0, IO io, int logb = 0,
                                                                    long long codes_off = kDenseCodes) {
   typedef typename Quad<BITS>::type Q;
-  constexpr int kLv = KIND == kFmtNatural ? 1 : (1 << (BITS - 1));
+  constexpr int kLv = KIND >= kFmtNatural ? 1 : (1 << (BITS - 1));
   constexpr int kBatch = BITS == 16 ? 8 : 16;
   __shared__ float s_lvt[kLv];
   const int lane = threadIdx.x;
-  if constexpr (KIND != kFmtNatural) {
+  if constexpr (KIND < kFmtNatural) {
     for (int i = lane; i < kLv; i += kWave) s_lvt[i] = (float)level_value<KIND>(i, s, step);
     __syncthreads();
   }
@@ -740,6 +746,8 @@ __global__ __launch_bounds__(kWave) void dense_fold_records_kernel(FoldArgs a, i
           const uint32_t code = quad_code<BITS>(cw[i][u], j);
           if constexpr (KIND == kFmtNatural) {
             v[j] = natural_value(code);
+          } else if constexpr (KIND == kFmtSign) {
+            v[j] = code ? -nrm : nrm;
           } else if (!regular) {
             v[j] = code == 0u ? 0.0f : __uint_as_float(0x7fc00000u);
           } else {
@@ -766,6 +774,14 @@ int launch_dense_fold(const char* name, const DenseCodec& cd, dim3 grid, hipStre
                tile0, io, 0, kDenseCodes);                                                                        \
     return FLC_OK;                                                                                                \
   } while (0)
+  if (cd.format == kFmtSign) {  // sign records: the 1-bit instance (logb 0: the whole vector under scales[0])
+    if (cd.logb) {
+      FLC_LAUNCH(name, (dense_fold_records_kernel<kFmtSign, 1, IO, true>), grid, dim3(kWave), 0, st, a, nw, 1, 1.0,
+                 cd.n, tile0, io, cd.logb, bucket_codes_offset(cd.n, cd.logb));
+      return FLC_OK;
+    }
+    FLC_DF(kFmtSign, 1);
+  }
   if (cd.logb) {  // bucket records (the dithering quantizers only)
     const long long coff = bucket_codes_offset(cd.n, cd.logb);
 #define FLC_BF(K, B)                                                                                                \
@@ -1328,6 +1344,16 @@ struct RoundCodec {
     c.dense.logb = l < 0 ? 6 : l;
     return c;
   }
+  // sign records (flc_sign_wire_layout); bucket 0: one scale for the record
+  bool is_sign = false;
+  static RoundCodec sign_records(int64_t n, int64_t bucket) {
+    RoundCodec c = dense_records(n, kFmtSign, 1, 1);
+    c.is_sign = true;
+    const int l = bucket ? bucket_log2(bucket) : 0;
+    if (l < 0) c.bucket_bad = bucket;
+    c.dense.logb = l < 0 ? 6 : l;
+    return c;
+  }
   static RoundCodec mixed(int64_t n, const MixedRound* mx) {
     RoundCodec c{n};
     c.mx = mx;
@@ -1337,6 +1363,11 @@ struct RoundCodec {
   // the codec's own argument rule (a mixed round's is check_mixed_round, run by its entry point before anything else)
   int check(const char* fn) const {
     if (mx) return FLC_OK;
+    if (is_sign) {
+      if (bucket_bad)
+        return fail(FLC_EINVAL, "%s: bucket %lld is not 0 or a power of two in [64, 4096]", fn, (long long)bucket_bad);
+      return FLC_OK;
+    }
     if (is_dense && dense.logb) {
       if (bucket_bad)
         return fail(FLC_EINVAL, "%s: bucket %lld is not a power of two in [64, 4096]", fn, (long long)bucket_bad);
@@ -1348,6 +1379,8 @@ struct RoundCodec {
   // bytes of one record of a uniform round (after check)
   size_t record_size() const {
     size_t need = 0;
+    if (is_sign)
+      return align_up((size_t)(dense.logb ? bucket_codes_offset(n, dense.logb) : kDenseCodes) + ((size_t)n + 7) / 8, 256);
     if (is_dense && dense.logb)
       return align_up((size_t)bucket_codes_offset(n, dense.logb) + ((size_t)n * (size_t)dense.bits + 7) / 8, 256);
     if (is_dense) return dense_wire_size(n, dense.format, dense.bits);
@@ -1916,6 +1949,39 @@ int flc_fold_bucket_wires(const void* wires, int64_t stride, const int32_t* slot
   return fold_wires_impl("flc_fold_bucket_wires", "fold_bucket_wires",
                          RoundCodec::bucket_records(n, format, levels, bits, bucket), wires, stride, slots, weights,
                          n_wires, accumulate, out, stream);
+}
+
+// The four forms over sign records (flc_sign_wire_layout): the 1-bit instance of the dense fold
+int flc_fold_sign_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
+                        int64_t n, int64_t bucket, int accumulate, float* out, void* stream) {
+  return fold_wires_impl("flc_fold_sign_wires", "fold_sign_wires", RoundCodec::sign_records(n, bucket), wires, stride,
+                         slots, weights, n_wires, accumulate, out, stream);
+}
+
+int flc_fedopt_fold_sign_records(const void* const* records, const float* weights, int n_records, int64_t n,
+                                 int64_t bucket, float* const* delta, float* const* theta, float* const* v,
+                                 const int64_t* sizes, int n_tensors, float beta0, int opt, double lr, double beta2,
+                                 double tau, void* stream) {
+  return fedopt_fold_impl("flc_fedopt_fold_sign_records", "fedopt_fold_sign_records",
+                          RoundCodec::sign_records(n, bucket), records, weights, n_records, delta, theta, v, sizes,
+                          n_tensors, beta0, opt, lr, beta2, tau, stream);
+}
+
+int flc_avg_and_gradient_sign_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                      const void* const* grad_records, const float* w_params, const float* w_grads,
+                                      int n_src, int64_t n, int64_t bucket, const int64_t* sizes, int n_tensors,
+                                      float inertia, void* stream) {
+  return avg_and_gradient_impl("flc_avg_and_gradient_sign_records", "avg_and_gradient_sign_records",
+                               RoundCodec::sign_records(n, bucket), params, grads, param_srcs, grad_records, w_params,
+                               w_grads, n_src, sizes, n_tensors, inertia, stream);
+}
+
+int flc_fold_sign_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
+                                int n_records, int64_t n, int64_t bucket, float* const* dsts, int n_groups,
+                                const int64_t* sizes, int n_tensors, void* stream) {
+  return fold_groups_impl("flc_fold_sign_record_groups", "fold_sign_record_groups",
+                          RoundCodec::sign_records(n, bucket), records, weights, group_of, n_records, dsts, n_groups,
+                          sizes, n_tensors, stream);
 }
 
 }  // extern "C"

@@ -237,6 +237,67 @@ int flc_fold_bucket_record_groups(const void* const* records, const float* weigh
                                   float* const* dsts, int n_groups, const int64_t* sizes, int n_tensors,
                                   void* stream);
 
+/* ------------------------------------------------------------------ scaled sign (1 bit per element)
+ * C(x) = (||x||_1 / d) * sign(x) per bucket: the compressor of EF-signSGD (Karimireddy et al., 2019) and the wire of
+ * 1-bit SGD.  Biased: meant for error feedback.  float32 only; n in [1, 2^31); bucket 0: the whole vector is one
+ * bucket (nb = 1); bucket B a power of two in [64, 4096]: consecutive slices of B elements, nb = ceil(n / B), the last
+ * slice possibly short.  For bucket b of m_b elements (the true count in the tail bucket):
+ *   scale_b = fp32(S_b / (double)m_b)  — one fp64 division, one rounding — S_b the fp64 sum of the fp32 |x_i| in an
+ *             order fixed by B (bucket 0: by n) and the positions, never by the grid: per run of 8 consecutive
+ *             elements a chain ss = ss + fp64(|x|) in index order from 0.0, a balanced pairwise tree over
+ *             min(B / 8, 64) adjacent runs, then for B >= 1024 r = 0.0, r += (sum of 512 elements) over the bucket's
+ *             B / 512 such sums in index order.  Bucket 0: that sum with B = 4096 per span of 4096 elements (elements
+ *             past n count as +0), then over the P = ceil(n / 4096) span sums: 512 chains, chain t over sums t,
+ *             t + 512, ... ascending from 0.0, the tree over 64 adjacent chains, and the 8 results in order from 0.0.
+ *   bit_i   = the IEEE sign bit of x_i (-0: 1, +0: 0), element i at bit i & 7 of byte i >> 3
+ *   value_i = bit_i ? -scale_b : scale_b   (a zero decodes to +-scale: a true 1-bit code)
+ * Non-finite inputs propagate through S_b by IEEE arithmetic; there is no special rule.
+ *
+ * Record layout (flc_sign_wire_layout): returns the record size (a multiple of 256 B; 0 for n < 1, n >= 2^31 or a
+ * bucket other than 0 or a power of two in [64, 4096]) and, if offsets != NULL, the byte offsets of offsets[0] the nb
+ * fp32 scales (0) and offsets[1] the bit stream (the next 16-B boundary, ceil(n / 8) bytes).  A pure host function. */
+size_t flc_sign_wire_layout(int64_t n, int64_t bucket, int64_t* offsets);
+/* bytes of flc_sign_encode's workspace: 0 for a bucket size (and for bad arguments), one fp64 per span of 4096
+ * elements for bucket 0 */
+size_t flc_sign_workspace_size(int64_t n, int64_t bucket);
+/* encode one message.  bucket B: ONE launch that reads x once — scales, bits and the optional outputs leave from the
+ * registers that hold x.  bucket 0: two launches in the call (the pass that writes the bits and one fp64 partial per
+ * span into ws, then the fold of the partials, in the order above in every block that needs the scale, with the
+ * elementwise pass over x if out or residual is given); no grid-wide wait.  scales: nb floats.  bits: 16-B aligned,
+ * written in whole 16-B words: ceil(n / 8) bytes rounded up to 16 must be writable (a record's field always is), the
+ * bits past n are 0.  out (optional, n floats): value_i.  residual (optional, n floats, may be x itself):
+ * fp32(x_i - value_i), the error memory's e' = a - C(a) in the encode's own pass.  ws: flc_sign_workspace_size bytes,
+ * 8-B aligned (bucket 0 only; ignored otherwise).  Algorithmic bytes per element: 4 + 1 / 8 + 4 / B.  No RNG, no
+ * status word: capturable.  FLC_EINVAL (nothing launched): a null x, scales or bits, n < 1 or n >= 2^31, a bad bucket,
+ * x, bits, out or residual not 16-B aligned, bucket 0 with a null, short or misaligned workspace. */
+int flc_sign_encode(const float* x, int64_t n, int64_t bucket, float* scales, uint8_t* bits, float* out,
+                    float* residual, void* ws, size_t ws_bytes, void* stream);
+/* decode: out = accumulate ? fmaf(weight, value, out) : weight * value  (weight 1: the value itself); nothing is
+ * written past n and the record's padding is never interpreted.  The scale is used as stored, whatever its bits (a
+ * hand-made record may hold any).  FLC_EINVAL: a null bits, scales or out, n or bucket as above, out or bits not 16-B
+ * aligned. */
+int flc_sign_decode(const uint8_t* bits, int64_t n, int64_t bucket, const float* scales, float weight, int accumulate,
+                    float* out, void* stream);
+/* The folds over sign records, the four forms every record codec has (flc_fold_dense_wires,
+ * flc_fedopt_fold_dense_records, flc_avg_and_gradient_dense_records, flc_fold_dense_record_groups) with the records
+ * laid out by flc_sign_wire_layout(n, bucket): the 1-bit instance of the dense fold, 1/32 of the decoded vector's
+ * bytes per record.  Each is bit-identical to decoding every record with flc_sign_decode into a zeroed vector and
+ * running the dense entry point its counterpart names.  Arguments, chaining per 64 records and FLC_EINVAL cases as
+ * the dense forms, with a bad bucket in place of the format's cases.  The mixed folds do not take sign records. */
+int flc_fold_sign_wires(const void* wires, int64_t stride, const int32_t* slots, const float* weights, int n_wires,
+                        int64_t n, int64_t bucket, int accumulate, float* out, void* stream);
+int flc_fedopt_fold_sign_records(const void* const* records, const float* weights, int n_records, int64_t n,
+                                 int64_t bucket, float* const* delta, float* const* theta, float* const* v,
+                                 const int64_t* sizes, int n_tensors, float beta0, int opt, double lr, double beta2,
+                                 double tau, void* stream);
+int flc_avg_and_gradient_sign_records(float* const* params, float* const* grads, const float* const* param_srcs,
+                                      const void* const* grad_records, const float* w_params, const float* w_grads,
+                                      int n_src, int64_t n, int64_t bucket, const int64_t* sizes, int n_tensors,
+                                      float inertia, void* stream);
+int flc_fold_sign_record_groups(const void* const* records, const float* weights, const int32_t* group_of,
+                                int n_records, int64_t n, int64_t bucket, float* const* dsts, int n_groups,
+                                const int64_t* sizes, int n_tensors, void* stream);
+
 /* ------------------------------------------------------------------ natural compressor
  * (compressors.py:302-325).  Wire: one uint16 per element, 0 = zero, else sign << 15 | (e + 150)
  * for the chosen power of two 2^e, e in [-149, 127]. */
