@@ -118,6 +118,19 @@ SIGNATURES = {
     "flc_fold_sign_record_groups": (
         c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p]
     ),
+    "flc_lowrank_wire_layout": (c_size_t, [c_int64, c_int64, c_int, c_void_p]),
+    "flc_lowrank_workspace_size": (c_size_t, [c_int64, c_int64, c_int]),
+    "flc_lowrank_encode": (
+        c_int,
+        [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+         c_void_p],
+    ),
+    "flc_lowrank_decode": (
+        c_int, [c_void_p, c_int64, c_int64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    ),
+    "flc_fold_lowrank_records": (
+        c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p]
+    ),
     "flc_count_consumers": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "flc_natural_workspace_size": (c_size_t, [c_int64]),
     "flc_natural_encode": (

@@ -412,6 +412,35 @@ def avg_parameters_and_gradients(model_params: Sequence[torch.Tensor], messages:
     return grads
 
 
+def _fold_lowrank(lrs, alpha: float, delta_parameters, ps, vps, opt: str, lr: float, betas, tau: float) -> bool:
+    """A device-resident FedOpt round of low-rank records of one (n, cols, rank): ``F = Σ_c α·P^_c Q'_cᵀ`` in one
+    codec.fold_lowrank_records call (the MFMA fold) into a flat scratch, then the one-launch dense fold of that single
+    vector with weight 1 and the optimiser step.  Not bit-identical to decoding every message and folding them: the
+    sum is associated differently.  False (nothing launched) when the model or the records are not on one HIP device
+    or the tensors do not hold the records' elements."""
+    d0 = lrs[0]
+    dev = _model_device(delta_parameters)
+    if dev is None or [p.numel() for p in delta_parameters] != [s.numel() for s in d0.shapes]:
+        return False
+    recs = [d.record for d in lrs]
+    if any(r.get_device() != dev for r in recs) or any(not (p.is_cuda and p.get_device() == dev) for p in ps):
+        return False
+    with torch.cuda.device(dev):
+        flat = codec.fold_lowrank_records(recs, [alpha] * len(recs), d0.n, d0.cols, d0.rank)
+        views, off = [], 0
+        for p in delta_parameters:
+            views.append(flat[off:off + p.numel()].view(p.shape))
+            off += p.numel()
+        if _fold(delta_parameters, [views], [1.0], 0, betas[0], theta=ps, v=vps, opt=opt if vps is not None else "avg",
+                 lr=lr, beta2=betas[1], tau=tau):
+            return True
+    for j, dp in enumerate(delta_parameters):  # (a model the one-launch fold does not take) per-tensor launches
+        _weighted_sum_any(dp, [views[j]], [1.0], 0, betas[0])
+        vp = None if vps is None else vps[j]
+        _contig_call(codec.fedopt_step, ps[j], dp, vp, opt if vp is not None else "avg", lr, betas[1], tau)
+    return True
+
+
 def fedopt_update(model_params: Sequence[torch.Tensor], delta_parameters: Sequence[torch.Tensor],
                   v_parameters: Optional[Sequence[torch.Tensor]], messages: Sequence[Mapping], optimizer: str,
                   lr: float, betas: Sequence[float], tau: float) -> None:
@@ -437,6 +466,9 @@ def fedopt_update(model_params: Sequence[torch.Tensor], delta_parameters: Sequen
                           [{"delta_parameters": m["delta_parameters"] if recs is not None else d}
                            for m, d in zip(messages, dm)], optimizer, lr, betas, tau)
         return
+    lrs = compressed.lowrank_round(messages)
+    if lrs is not None and _fold_lowrank(lrs, alpha, delta_parameters, _params(model_params), vps, opt, lr, betas, tau):
+        return  # Σ α·P^Q'ᵀ as one matrix product into a flat scratch, then the one-launch fold and optimizer step
     # (the parameters as they are for the one-pass fold: its kernels write θ in place, outside autograd)
     if recs is not None and compressed.fold_records(recs, [alpha] * len(recs), delta_parameters, model_params, vps,
                                                     betas[0], opt if vps is not None else "avg", lr, betas[1], tau,

@@ -593,6 +593,124 @@ def sign_decode(record: torch.Tensor, n: int, bucket: int = 0, out: Optional[tor
     return out
 
 
+# --------------------------------------------------------------------------------------- low-rank records
+LOWRANK_COLS = (256, 512, 1024)
+LOWRANK_RANKS = (1, 2, 4)
+_LOWRANK_LAYOUT: Dict[tuple, tuple] = {}
+
+
+def lowrank_cols(n: int) -> int:
+    """The default matrix width of a low-rank record of ``n`` elements: the smallest power of two ``>= sqrt(n)``,
+    clipped to [256, 1024]."""
+    c = 256
+    while c < 1024 and c * c < n:
+        c *= 2
+    return c
+
+
+def lowrank_wire_layout(n: int, cols: int, rank: int):
+    """(record bytes, {"p", "q"} byte offsets) of a low-rank record (flc_lowrank_wire_layout): ``P^`` as
+    ``[ceil(n / cols)][rank]`` fp32, then ``Q'`` as ``[cols][rank]`` fp32 from the next 16-B boundary."""
+    import ctypes
+
+    key = (int(n), int(cols), int(rank))
+    r = _LOWRANK_LAYOUT.get(key)
+    if r is None:
+        off = (ctypes.c_int64 * 2)()
+        total = _lib.size("flc_lowrank_wire_layout", key[0], key[1], key[2], ctypes.cast(off, ctypes.c_void_p))
+        if total == 0:
+            raise ValueError(f"bad low-rank record shape n={n}, cols={cols}, rank={rank}")
+        r = _LOWRANK_LAYOUT[key] = (int(total), {"p": int(off[0]), "q": int(off[1])})
+    return r
+
+
+def lowrank_wire_views(record: torch.Tensor, n: int, cols: int, rank: int):
+    """(P^ ``[m, rank]``, Q' ``[cols, rank]``) float32 views into a low-rank record (a contiguous uint8 HIP tensor of
+    at least ``lowrank_wire_layout(...)[0]`` bytes, 16-B aligned)."""
+    stride, off = lowrank_wire_layout(n, cols, rank)
+    if record.dtype != torch.uint8 or record.device.type != "cuda" or not record.is_contiguous():
+        raise TypeError("a wire record is a contiguous uint8 HIP tensor")
+    rec = record.reshape(-1)
+    if rec.numel() < stride or rec.data_ptr() % 16 != 0:
+        raise ValueError(f"a low-rank record needs {stride} bytes, 16-B aligned")
+    m = (n + cols - 1) // cols
+    return (rec[off["p"]:off["p"] + 4 * m * rank].view(torch.float32).view(m, rank),
+            rec[off["q"]:off["q"] + 4 * cols * rank].view(torch.float32).view(cols, rank))
+
+
+def lowrank_encode(x: torch.Tensor, q: torch.Tensor, record: Optional[torch.Tensor] = None,
+                   q_next: Optional[torch.Tensor] = None, decode: bool = False,
+                   residual: Optional[torch.Tensor] = None):
+    """One message as a low-rank record (flc_lowrank_encode): one PowerSGD power iteration from ``q`` (``[cols, rank]``
+    float32 on ``x``'s device), ``x`` read once for ``P``, ``MᵀP`` and the Gram matrix.  ``q_next`` (may be ``q``)
+    receives the next call's warm start; ``decode``: also the decoded vector; ``residual`` (n floats, may be ``x``
+    itself): receives ``x - decoded``.  Returns ``(record, decoded or None)``."""
+    x = _dev_f32(x).reshape(-1)
+    n, dev = x.numel(), x.device
+    if q.dim() != 2 or q.dtype != torch.float32 or q.device != dev or not q.is_contiguous():
+        raise ValueError("q must be a contiguous float32 [cols, rank] tensor on x's device")
+    cols, rank = int(q.shape[0]), int(q.shape[1])
+    stride, _ = lowrank_wire_layout(n, cols, rank)
+    if record is None:
+        record = torch.empty(stride, dtype=torch.uint8, device=dev)
+    lowrank_wire_views(record, n, cols, rank)  # (the record's checks)
+    if q_next is not None and (q_next.shape != q.shape or q_next.dtype != torch.float32 or q_next.device != dev
+                               or not q_next.is_contiguous()):
+        raise ValueError("q_next must be a contiguous float32 tensor of q's shape on x's device")
+    if residual is not None and (residual.dtype != torch.float32 or residual.device != dev or residual.numel() != n
+                                 or not residual.is_contiguous()):
+        raise ValueError("residual must be a contiguous float32 tensor of x's size on x's device")
+    out = torch.empty(n, dtype=torch.float32, device=dev) if decode else None
+    need = _lib.size("flc_lowrank_workspace_size", n, cols, rank)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    call("flc_lowrank_encode", _p(x), n, cols, rank, _p(q), _p(record), _p(q_next), _p(out), _p(residual), _p(ws),
+         need, _stream(dev))
+    return record, out
+
+
+def lowrank_decode(record: torch.Tensor, n: int, cols: int, rank: int, out: Optional[torch.Tensor] = None,
+                   weight: float = 1.0, accumulate: bool = False, x: Optional[torch.Tensor] = None,
+                   residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The decoded flat vector ``P^ Q'ᵀ`` of a low-rank record (flc_lowrank_decode);
+    ``out = fmaf(weight, v, out)`` when accumulating, ``weight * v`` otherwise.  ``residual`` (with ``x``, n floats
+    each; may be ``x`` itself) receives ``x - v`` in the same pass."""
+    lowrank_wire_views(record, n, cols, rank)
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs an out tensor")
+        out = torch.empty(n, dtype=torch.float32, device=record.device)
+    for t in (out, x, residual):
+        if t is not None and (t.dtype != torch.float32 or t.device != record.device or t.numel() != n
+                              or not t.is_contiguous()):
+            raise ValueError("out, x and residual must be contiguous float32 tensors of n elements on the record's device")
+    call("flc_lowrank_decode", _p(record), n, cols, rank, float(weight), int(accumulate), _p(out), _p(x), _p(residual),
+         _stream(out.device))
+    return out
+
+
+def fold_lowrank_records(records: Sequence[torch.Tensor], weights: Sequence[float], n: int, cols: int, rank: int,
+                         out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """``out = (accumulate ? out : 0) + Σ_c weights[c] · P^_c Q'_cᵀ`` as one matrix product of inner dimension
+    ``len(records) · rank`` on the fp32 MFMA (flc_fold_lowrank_records), records in the given order.  Not bit-identical
+    to decoding every record and adding: the sum is associated differently."""
+    import ctypes
+
+    if len(records) != len(weights) or not records:
+        raise ValueError("one weight per record, at least one record")
+    for r in records:
+        lowrank_wire_views(r, n, cols, rank)
+    dev = records[0].device
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs an out tensor")
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+    ptrs = (ctypes.c_void_p * len(records))(*[r.data_ptr() for r in records])
+    ws = (ctypes.c_float * len(records))(*[float(w) for w in weights])
+    call("flc_fold_lowrank_records", ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(ws, ctypes.c_void_p),
+         len(records), n, cols, rank, int(accumulate), _p(out), _stream(dev))
+    return out
+
+
 def fold_dense_wires(wires: torch.Tensor, slots: Sequence[int], weights: Sequence[float], n: int, fmt: int,
                      levels: int, bits: int, out: Optional[torch.Tensor] = None,
                      accumulate: bool = False) -> torch.Tensor:

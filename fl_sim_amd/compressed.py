@@ -116,7 +116,7 @@ import torch
 from . import _lib, codec
 from ._lib import FLC_NORM_INF, FLC_NORM_L2, FLC_Q_NATURAL_DITHER, FLC_Q_STANDARD_DITHER, FLC_WIRE_NATURAL
 from . import rng as _rng
-from .compressors import Compressor, CompressorType, SignCompressor
+from .compressors import Compressor, CompressorType, LowRankCompressor, SignCompressor
 from .feedback import ErrorFeedbackClientMixin, ErrorMemory
 
 
@@ -155,14 +155,18 @@ class CompressedDelta(_abc.Sequence):
     uint16 per element), ``format`` being flc_dense_wire_layout's; ``kind == "bucket"`` (``wire=True`` with a bucket
     size): the bucket record of a bucketed dithering quantizer (one norm per ``bucket`` elements, then the packed codes;
     flc_bucket_wire_layout); ``kind == "sign"`` (``wire=True`` with a :class:`SignCompressor`): the scaled-sign record
-    (one scale per bucket, then one bit per element; flc_sign_wire_layout); ``kind == "dense"``: the decoded flat delta.
+    (one scale per bucket, then one bit per element; flc_sign_wire_layout); ``kind == "lowrank"`` (``wire=True`` with
+    a :class:`LowRankCompressor`; ``lowrank=(cols, rank)``): the low-rank record (``P^`` then ``Q'``;
+    flc_lowrank_wire_layout), which only FedOpt's device fold reads as a record — every other reader takes its decoded
+    vector; ``kind == "dense"``: the decoded flat delta.
     Indexing gives tensor ``j`` of the model's shapes (the decoded values, one flat decode on first access), so code
     written for a list of delta tensors reads it unchanged."""
 
     def __init__(self, shapes: Sequence[torch.Size], device: torch.device, n: int, *, record=None, k: int = 0,
                  levels: int = 0, flat: Optional[torch.Tensor] = None, batch: Optional["_Batch"] = None,
                  format: Optional[int] = None, bits: int = 0, sparse: bool = False, bucket: int = 0,
-                 sign: bool = False):
+                 sign: bool = False, lowrank: Optional[Tuple[int, int]] = None):
+        self.cols, self.rank = (int(lowrank[0]), int(lowrank[1])) if lowrank else (0, 0)
         self.shapes = [torch.Size(s) for s in shapes]
         self.device = device
         self.n = int(n)
@@ -170,7 +174,9 @@ class CompressedDelta(_abc.Sequence):
         self._batch = batch  # (a deferred encode: the record is made by the batch's launch on first access)
         self.format, self.bits = format, int(bits)
         self.bucket = int(bucket)  # a bucket record's bucket size (flc_bucket_wire_layout), else 0
-        if sign:  # (a scaled-sign record, flc_sign_wire_layout(n, bucket): bucket 0 is the whole vector)
+        if lowrank:  # (a low-rank record, flc_lowrank_wire_layout(n, cols, rank))
+            self.kind = "lowrank"
+        elif sign:  # (a scaled-sign record, flc_sign_wire_layout(n, bucket): bucket 0 is the whole vector)
             self.kind = "sign"
         elif format is not None and self.bucket:
             self.kind = "bucket"
@@ -193,7 +199,8 @@ class CompressedDelta(_abc.Sequence):
     @property
     def codec_key(self) -> tuple:
         """What a round's records must share to be folded together."""
-        return (self.kind, self.n, self.k, self.levels, self.format, self.bits, self.bucket)
+        key = (self.kind, self.n, self.k, self.levels, self.format, self.bits, self.bucket)
+        return key + (self.cols, self.rank) if self.kind == "lowrank" else key
 
     def __getstate__(self):
         """A copied or pickled message carries its record (a deferred encode runs first); a dense record travels
@@ -202,13 +209,15 @@ class CompressedDelta(_abc.Sequence):
             self._batch.run()
         d = self.__dict__.copy()
         d["_batch"] = None
-        if self.kind in ("quant", "natural", "bucket", "sign"):
+        if self.kind in ("quant", "natural", "bucket", "sign", "lowrank"):
             d["_flat"] = d["_views"] = None
         return d
 
     def __setstate__(self, d):
         self.__dict__.update(d)
         self.__dict__.setdefault("bucket", 0)  # (a delta pickled before bucket records existed)
+        self.__dict__.setdefault("cols", 0)  # (... before low-rank records existed)
+        self.__dict__.setdefault("rank", 0)
 
     @property
     def nbytes(self) -> int:
@@ -219,7 +228,9 @@ class CompressedDelta(_abc.Sequence):
         """The decoded flat delta (flc_stacked_decode_tiled, flc_sparse_decode_tiled, flc_quant_decode or
         flc_natural_decode of the record, once)."""
         if self._flat is None:
-            if self.kind == "sign":
+            if self.kind == "lowrank":
+                self._flat = codec.lowrank_decode(self.record, self.n, self.cols, self.rank)
+            elif self.kind == "sign":
                 self._flat = codec.sign_decode(self.record, self.n, self.bucket)
             elif self.kind == "bucket":
                 self._flat = codec.bucket_decode(self.record, self.n, self.format, self.levels, self.bits, self.bucket)
@@ -652,6 +663,24 @@ def _sign_record(x: torch.Tensor, shapes, n: int, comp: SignCompressor, dev, fee
     return CompressedDelta(shapes, dev, n, record=rec, bucket=comp.bucket, sign=True)
 
 
+def _lowrank_wire(compressors: Sequence[Compressor], wire: bool) -> Optional[LowRankCompressor]:
+    """The one :class:`LowRankCompressor` whose record a ``wire`` message carries, else None."""
+    if wire and len(compressors) == 1 and isinstance(compressors[0], LowRankCompressor):
+        return compressors[0]
+    return None
+
+
+def _lowrank_record(x: torch.Tensor, shapes, n: int, comp: LowRankCompressor, dev,
+                    feedback: bool = False) -> CompressedDelta:
+    """The low-rank record of the flat fp32 vector ``x`` in one flc_lowrank_encode (``comp``'s ``Q`` advanced);
+    ``feedback``: ``x`` is the error memory holding ``a``, and the call's decode pass leaves
+    ``e' = a − decode(record)`` in it."""
+    if n != comp.D:
+        raise ValueError(f"Low-rank compressor built for D={comp.D} applied to a message of {n} elements")
+    rec, _ = comp.encode(x, residual=x if feedback else None)
+    return CompressedDelta(shapes, dev, n, record=rec, lowrank=(comp.cols, comp.rank))
+
+
 def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
               compressors: Sequence[Compressor], wire: bool = False, sparse: bool = False,
               bucket: int = 0) -> CompressedDelta:
@@ -696,6 +725,9 @@ def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]
     sg = _sign_wire(compressors, wire)
     if sg is not None and out.dtype == torch.float32:  # the 1-bit record as the message, nothing decoded
         return _sign_record(out, shapes, n, sg, dev)
+    lr = _lowrank_wire(compressors, wire)
+    if lr is not None and out.dtype == torch.float32:  # the low-rank record as the message, nothing decoded
+        return _lowrank_record(out, shapes, n, lr, dev)
     dc = dense_wire_codec(compressors) if wire else None
     B = _bucket_of(compressors, bucket)
     if B and dc is not None and out.dtype == torch.float32:  # a bucket record: one norm per B elements, then the codes
@@ -773,6 +805,9 @@ def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torc
     sg = _sign_wire(compressors, wire)
     if sg is not None:  # the memory is the encoder's input and its residual output: no decode, no residual launch
         return _sign_record(e, shapes, n, sg, dev, feedback=True)
+    lr = _lowrank_wire(compressors, wire)
+    if lr is not None:  # likewise: the memory is x and residual of the one flc_lowrank_encode
+        return _lowrank_record(e, shapes, n, lr, dev, feedback=True)
     dc = dense_wire_codec(compressors) if wire else None
     B = _bucket_of(compressors, bucket)
     if B:  # bucketed: encoded at once from the memory's values, then the plain dense residual of the decoded record
@@ -1342,6 +1377,12 @@ def sparse_round(messages: Sequence, key: str = "delta_parameters") -> Optional[
     return _round_deltas(messages, key, ("sparse",))
 
 
+def lowrank_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
+    """The messages' compressed deltas when every one is a low-rank record of one (n, cols, rank), else None.  Not one
+    of :func:`record_round`'s kinds: only FedOpt's device fold reads these as records (aggregation.fedopt_update)."""
+    return _round_deltas(messages, key, ("lowrank",))
+
+
 def record_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
     """:func:`stacked_round`, :func:`dense_record_round` or :func:`sparse_round`: a round the record folds take, else
     None."""
@@ -1434,7 +1475,7 @@ def mixed_round(messages: Sequence, key: str = "delta_parameters") -> Optional[L
             return None
         ds.append(d)
     d0 = ds[0]
-    if any(d.n != d0.n for d in ds) or all(d.kind in ("dense", "bucket", "sign") for d in ds):
+    if any(d.n != d0.n for d in ds) or all(d.kind in ("dense", "bucket", "sign", "lowrank") for d in ds):
         return None
     if all(d.codec_key == d0.codec_key for d in ds):
         return None
@@ -1452,7 +1493,7 @@ def _mixed_tables(deltas: Sequence[CompressedDelta], dev: torch.device, records=
     for i, d in enumerate(deltas):
         if d.kind == "dense":
             t, desc = d._flat, (_REC_FLAT, 0, 0, 0, 0)
-        elif d.kind in ("bucket", "sign"):  # (not in the mixed fold's descriptor tables: read as its decoded vector)
+        elif d.kind in ("bucket", "sign", "lowrank"):  # (not in the mixed fold's descriptor tables: read as its decoded vector)
             t, desc = d.flat(), (_REC_FLAT, 0, 0, 0, 0)
         else:
             t = d.record

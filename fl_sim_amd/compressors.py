@@ -47,7 +47,8 @@ from . import codec
 from . import rng as _rng
 from ._lib import FLC_Q_NATURAL_DITHER, FLC_Q_STANDARD_DITHER
 
-__all__ = ["CompressorType", "Compressor", "SignCompressor", "SIGN_COMPRESSOR"]
+__all__ = ["CompressorType", "Compressor", "SignCompressor", "SIGN_COMPRESSOR", "LowRankCompressor",
+           "LOWRANK_COMPRESSOR"]
 
 
 @unique
@@ -801,3 +802,65 @@ class SignCompressor(Compressor):
         _, out = codec.sign_encode(x, self.bucket, decode=True)
         self._finish(self.D, self.send_components())
         return out
+
+
+LOWRANK_COMPRESSOR = "LOWRANK_COMPRESSOR"  # LowRankCompressor.compressorType: outside CompressorType, as SIGN_COMPRESSOR
+
+
+class LowRankCompressor(Compressor):
+    """Low rank, one PowerSGD power iteration (Vogels et al., 2019) on the flat vector read as a
+    ``ceil(D / cols) x cols`` matrix, the view of ``torch.distributed``'s ``batched_powerSGD_hook``: the message is
+    ``P^`` (orthonormal columns) and ``Q'``, ``(ceil(D / cols) + cols) * rank`` fp32 components.  Biased — use it with
+    error feedback.  ``cols=None``: the smallest power of two ``>= sqrt(D)`` in [256, 1024].  The initial ``Q`` is
+    ``torch.randn(cols, rank)`` from a CPU generator seeded with ``seed``, moved to the device once; ``warm_start``
+    keeps every call's ``q_next`` as the next call's ``Q`` (a dropped column keeps its previous values).  An extension
+    over the reference: its type is the sentinel ``LOWRANK_COMPRESSOR``.  Deterministic: no RNG draw on the device."""
+
+    def __init__(self, D: int, rank: int = 2, cols: Optional[int] = None, seed: int = 0, warm_start: bool = True):
+        super().__init__("LowRankCompressor")
+        if int(D) < 1:
+            raise ValueError(f"D must be >= 1 (got {D})")
+        self.D = int(D)
+        self.cols = codec.lowrank_cols(self.D) if cols is None else int(cols)
+        self.rank = int(rank)
+        if self.cols not in codec.LOWRANK_COLS or self.rank not in codec.LOWRANK_RANKS:
+            raise ValueError(f"cols must be one of {codec.LOWRANK_COLS} and rank one of {codec.LOWRANK_RANKS} "
+                             f"(got cols={cols}, rank={rank})")
+        self.warm_start = bool(warm_start)
+        self._q0 = torch.randn(self.cols, self.rank, generator=torch.Generator().manual_seed(int(seed)))
+        self._q: Optional[torch.Tensor] = None  # Q on the encode's device
+
+    compressorType = property(lambda self: LOWRANK_COMPRESSOR)
+    is_biased = property(lambda self: True)
+    w = property(lambda self: 0.0)
+    name = property(lambda self: f"Low rank [D={self.D},cols={self.cols},r={self.rank}]")
+    fullName = name
+
+    def send_components(self) -> float:
+        """fp32 components per message: ``P^`` and ``Q'``."""
+        return float((-(-self.D // self.cols) + self.cols) * self.rank)
+
+    def q_on(self, dev: torch.device) -> torch.Tensor:
+        """``Q`` on ``dev`` (moved there once); with ``warm_start`` the encode overwrites it with ``q_next``."""
+        if self._q is None or self._q.device != dev:
+            self._q = self._q0.to(dev)
+        return self._q
+
+    def encode(self, x: torch.Tensor, decode: bool = False, residual: Optional[torch.Tensor] = None):
+        """(record, decoded or None) of the flat fp32 device vector ``x`` (codec.lowrank_encode), ``Q`` advanced."""
+        q = self.q_on(x.device)
+        rec, out = codec.lowrank_encode(x, q, q_next=q if self.warm_start else None, decode=decode, residual=residual)
+        self._finish(self.D, self.send_components())
+        return rec, out
+
+    def compressVector(self, x):
+        """One flc_lowrank_encode with ``out`` (device and numpy inputs alike): the decoded vector ``P^ Q'ᵀ``."""
+        shape, dtype = tuple(x.shape), x.dtype  # (refusals first: nothing is copied or launched for them)
+        if len(shape) != 1 or shape[0] != self.D:
+            raise ValueError(f"Low-rank compressor built for D={self.D} applied to a vector of shape {shape}")
+        if str(dtype).endswith("float64"):  # (torch.float64 or numpy's)
+            raise ValueError("the low-rank compressor takes float32 vectors")
+        return super().compressVector(x)
+
+    def _compress_device(self, x: torch.Tensor, host_norm=None) -> torch.Tensor:
+        return self.encode(x, decode=True)[1]

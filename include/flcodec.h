@@ -298,6 +298,53 @@ int flc_fold_sign_record_groups(const void* const* records, const float* weights
                                 int n_records, int64_t n, int64_t bucket, float* const* dsts, int n_groups,
                                 const int64_t* sizes, int n_tensors, void* stream);
 
+/* ------------------------------------------------------------------ low rank (PowerSGD)
+ * One power iteration of PowerSGD (Vogels et al., 2019) on a flattened buffer, the view of torch.distributed's
+ * batched_powerSGD_hook: the flat fp32 vector x is the row-major matrix M of m = ceil(n / cols) rows and cols columns
+ * (elements at and past n read as +0; nothing is read or written past n).  Biased: meant for error feedback.
+ * float32 only; n in [1, 2^31); cols in {256, 512, 1024}; rank r in {1, 2, 4}.  With Q (cols x r, row-major):
+ *   P = M Q (fp32);  G = P^T P (fp64);  G = L L^T by Cholesky in fp64;  W = L^-1;
+ *   P^ = P W^T and Q' = (M^T P) W^T (each entry an fp64 sum over l <= k, rounded once);  decoded = P^ Q'^T.
+ * Drop rule: at Cholesky step k, if G_kk == 0 or the pivot d_k <= 2^-40 G_kk, column k is dropped: P^[:, k] = 0,
+ * Q'[:, k] = 0 and it adds nothing to later columns (a zero vector gives an all-zero record, never a NaN).
+ * q_next = Q' with every dropped column replaced by the input Q's: the next call's warm start.
+ * Every sum's order is a function of (n, cols, rank) only (lowrank.hip's header states it): a rerun gives the same
+ * bytes on any device.
+ *
+ * Record layout (flc_lowrank_wire_layout): returns the record size (a multiple of 256 B; 0 for bad arguments) and,
+ * if offsets != NULL, the byte offsets of offsets[0] P^ as [m][r] fp32 (0) and offsets[1] Q' as [cols][r] fp32 (the
+ * next 16-B boundary).  A pure host function. */
+size_t flc_lowrank_wire_layout(int64_t n, int64_t cols, int rank, int64_t* offsets);
+/* bytes of flc_lowrank_encode's workspace (one T = M^T P partial and one fp64 G partial per panel of rows); 0 for bad
+ * arguments */
+size_t flc_lowrank_workspace_size(int64_t n, int64_t cols, int rank);
+/* encode one message: the pass (ONE read of x for P, M^T P and G), the finish (every block folds the G partials
+ * itself in a fixed order: no grid-wide wait, no ticket) and, if out or residual is given, the decode pass.
+ * q: cols * r floats.  record: flc_lowrank_wire_layout bytes, 16-B aligned.  q_next (optional, cols * r floats, may
+ * be q).  out (optional, n floats): the decoded vector.  residual (optional, n floats, may be x itself):
+ * fp32(x_i - decoded_i), the error memory's e' = a - C(a).  ws: flc_lowrank_workspace_size bytes, 256-B aligned.
+ * No RNG, no host synchronisation, no status word: capturable.  FLC_EINVAL (nothing launched): a null x, q or
+ * record, n, cols or rank outside the sets above, a pointer not 16-B aligned, a null, short or misaligned
+ * workspace. */
+int flc_lowrank_encode(const float* x, int64_t n, int64_t cols, int rank, const float* q, void* record, float* q_next,
+                       float* out, float* residual, void* ws, size_t ws_bytes, void* stream);
+/* decode: v = P^[i,0] Q'[j,0], then v = fmaf(P^[i,k], Q'[j,k], v) for k ascending;
+ * out (optional) = accumulate ? fmaf(weight, v, out) : weight * v;  residual (optional, with x; may be x itself)
+ * = fp32(x - v).  The record's values are used as stored (a hand-made record is legal input);
+ * nothing is written past n.  FLC_EINVAL: a null record, neither out nor residual, residual without x, accumulate
+ * without out, a pointer not 16-B aligned, a bad shape. */
+int flc_lowrank_decode(const void* record, int64_t n, int64_t cols, int rank, float weight, int accumulate, float* out,
+                       const float* x, float* residual, void* stream);
+/* The fold of a round's records, a matrix product of inner dimension K = n_records * r on the fp32 MFMA
+ * (v_mfma_f32_32x32x2_f32):  S = sum_c sum_k fp32(w_c P^_c[i,k]) Q'_c[j,k] from +0, records ascending, then k
+ * ascending, two terms per instruction (an odd K ends on a zero operand);  out[i cols + j] = accumulate ? out + S : S
+ * (the stored value added last, in one rounding).  NOT bit-identical to n_records flc_lowrank_decode(accumulate)
+ * calls: the sum is associated differently.  records / weights: HOST arrays; records of one (n, cols, rank), 16-B
+ * aligned device pointers.  Launches chain per 64 records, each adding its 64 records' sum to the stored value.  FLC_EINVAL: null arguments, n_records < 1, a bad shape, out or a
+ * record null or not 16-B aligned. */
+int flc_fold_lowrank_records(const void* const* records, const float* weights, int n_records, int64_t n, int64_t cols,
+                             int rank, int accumulate, float* out, void* stream);
+
 /* ------------------------------------------------------------------ natural compressor
  * (compressors.py:302-325).  Wire: one uint16 per element, 0 = zero, else sign << 15 | (e + 150)
  * for the chosen power of two 2^e, e in [-149, 127]. */
