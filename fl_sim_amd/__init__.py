@@ -17,10 +17,10 @@ there is no CPU fallback.
 import os
 
 from . import _lib
-from .compressors import Compressor, CompressorType, LowRankCompressor, SignCompressor
+from .compressors import Compressor, CompressorType, LowRankCompressor, SignCompressor, SketchCompressor
 
-__all__ = ["Compressor", "CompressorType", "SignCompressor", "LowRankCompressor", "native_library", "load_torch_ops",
-           "__version__"]
+__all__ = ["Compressor", "CompressorType", "SignCompressor", "LowRankCompressor", "SketchCompressor", "native_library",
+           "load_torch_ops", "__version__"]
 __version__ = "0.1.0"
 
 

@@ -131,6 +131,23 @@ SIGNATURES = {
     "flc_fold_lowrank_records": (
         c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p]
     ),
+    "flc_sketch_wire_layout": (c_size_t, [c_int64, c_int, c_int64, c_void_p]),
+    "flc_sketch_splits": (c_int, [c_int64, c_int64]),
+    "flc_sketch_workspace_size": (c_size_t, [c_int64, c_int, c_int64]),
+    "flc_sketch_encode": (
+        c_int, [c_void_p, c_int64, c_int, c_int64, c_uint64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    ),
+    "flc_sketch_estimate": (
+        c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_uint64, c_void_p, c_void_p]
+    ),
+    "flc_sketch_fold": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "flc_sketch_state_step": (
+        c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p]
+    ),
+    "flc_sketch_clear": (
+        c_int, [c_void_p, c_int64, c_int64, c_int, c_int64, c_uint64, c_void_p, c_void_p, c_void_p]
+    ),
+    "flc_sketch_cells": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int64, c_uint64, c_void_p, c_void_p]),
     "flc_count_consumers": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "flc_natural_workspace_size": (c_size_t, [c_int64]),
     "flc_natural_encode": (

@@ -441,10 +441,95 @@ def _fold_lowrank(lrs, alpha: float, delta_parameters, ps, vps, opt: str, lr: fl
     return True
 
 
+class SketchServerState:
+    """FetchSGD's server side of a round of count-sketch records (:func:`_fold_sketch`): ``k`` heavy coordinates kept
+    per round (0: the dense estimate), momentum ``rho`` in the sketch ``u``, and with ``error`` the error sketch
+    ``v``.  With ``rho == 0`` and ``error`` off no table is allocated.  The tables are made on the first round, for
+    that round's (rows, cols) on its device."""
+
+    def __init__(self, k: int = 0, momentum: float = 0.0, error: bool = False):
+        self.k, self.rho, self.error = int(k or 0), float(momentum or 0.0), bool(error)
+        self.u: Optional[torch.Tensor] = None
+        self.v: Optional[torch.Tensor] = None
+
+    @property
+    def stateful(self) -> bool:
+        return self.rho != 0.0 or self.error
+
+    def tables(self, rows: int, cols: int, dev):
+        if self.u is None or self.u.shape != (rows, cols) or self.u.device != dev:
+            self.u = torch.zeros(rows, cols, dtype=torch.float32, device=dev)
+            self.v = torch.zeros(rows, cols, dtype=torch.float32, device=dev) if self.error else None
+        return self.u, self.v
+
+
+def _switch(node, name: str, default):
+    """``name`` looked up on the server, then on its config (as the clients' switches are); absent: ``default``."""
+    v = getattr(node, name, None)
+    if v is None:
+        v = getattr(getattr(node, "config", None), name, None)
+    return default if v is None else v
+
+
+def sketch_server_state(server) -> SketchServerState:
+    """The server's :class:`SketchServerState` from its switches ``sketch_k``, ``sketch_momentum`` (rho, default 0)
+    and ``sketch_error`` (default False), kept on the server while they do not change."""
+    key = (int(_switch(server, "sketch_k", 0)), float(_switch(server, "sketch_momentum", 0.0)),
+           bool(_switch(server, "sketch_error", False)))
+    st = getattr(server, "_sketch_state", None)
+    if st is None or (st.k, st.rho, st.error) != key:
+        st = server._sketch_state = SketchServerState(*key)
+    return st
+
+
+def _fold_sketch(sks, alpha: float, state: Optional[SketchServerState], delta_parameters, ps, vps, opt: str, lr: float,
+                 betas, tau: float) -> bool:
+    """A device-resident FedOpt round of count-sketch records of one (n, rows, cols, seed), FetchSGD's server step:
+    the state step ``u = rho u + S̄, v = v + u`` on the tables (or, stateless, nothing), ONE median-of-rows estimate
+    into a flat scratch, the top ``k`` of it by magnitude, the kept coordinates' cells cleared in ``u`` and ``v``, then
+    the one-launch dense fold of that vector with weight 1 and the optimiser step.  False (nothing launched) when the
+    model or the records are not on one HIP device or the tensors do not hold the records' elements."""
+    d0 = sks[0]
+    state = state or SketchServerState()
+    dev = _model_device(delta_parameters)
+    if dev is None or [p.numel() for p in delta_parameters] != [s.numel() for s in d0.shapes]:
+        return False
+    recs = [d.record for d in sks]
+    if any(r.get_device() != dev for r in recs) or any(not (p.is_cuda and p.get_device() == dev) for p in ps):
+        return False
+    n, rows, cols, seed = d0.n, d0.rows, d0.cols, d0.seed
+    with torch.cuda.device(dev):
+        u = v = None
+        if state.stateful:
+            u, v = state.tables(rows, cols, recs[0].device)
+            codec.sketch_state_step(recs, [alpha] * len(recs), rows, cols, state.rho, u, v)
+            flat = codec.sketch_estimate([v if state.error else u], [1.0], n, rows, cols, seed)
+        else:
+            flat = codec.sketch_estimate(recs, [alpha] * len(recs), n, rows, cols, seed)
+        if 0 < state.k < n:
+            idx, val = codec.topk_encode(flat, state.k, order=codec.ORDER_MAGNITUDE)[:2]
+            if state.stateful:
+                codec.sketch_clear(idx, n, rows, cols, seed, u, v)
+            flat = codec.sparse_decode(idx, val, n)
+        views, off = [], 0
+        for p in delta_parameters:
+            views.append(flat[off:off + p.numel()].view(p.shape))
+            off += p.numel()
+        if _fold(delta_parameters, [views], [1.0], 0, betas[0], theta=ps, v=vps, opt=opt if vps is not None else "avg",
+                 lr=lr, beta2=betas[1], tau=tau):
+            return True
+    for j, dp in enumerate(delta_parameters):  # (a model the one-launch fold does not take) per-tensor launches
+        _weighted_sum_any(dp, [views[j]], [1.0], 0, betas[0])
+        vp = None if vps is None else vps[j]
+        _contig_call(codec.fedopt_step, ps[j], dp, vp, opt if vp is not None else "avg", lr, betas[1], tau)
+    return True
+
+
 def fedopt_update(model_params: Sequence[torch.Tensor], delta_parameters: Sequence[torch.Tensor],
                   v_parameters: Optional[Sequence[torch.Tensor]], messages: Sequence[Mapping], optimizer: str,
-                  lr: float, betas: Sequence[float], tau: float) -> None:
-    """_fedopt.py:196-265 (FedAvg: optimizer="avg", lr=1, betas=(0, 1))."""
+                  lr: float, betas: Sequence[float], tau: float, sketch: Optional[SketchServerState] = None) -> None:
+    """_fedopt.py:196-265 (FedAvg: optimizer="avg", lr=1, betas=(0, 1)).  ``sketch``: the server's state for a round
+    of count-sketch records (:func:`_fold_sketch`); None reads such a round statelessly, its dense estimate."""
     opt = optimizer.lower()
     if opt not in ("avg", "adagrad", "yogi", "adam"):
         raise ValueError(f"Unknown optimizer: {optimizer}")
@@ -469,6 +554,10 @@ def fedopt_update(model_params: Sequence[torch.Tensor], delta_parameters: Sequen
     lrs = compressed.lowrank_round(messages)
     if lrs is not None and _fold_lowrank(lrs, alpha, delta_parameters, _params(model_params), vps, opt, lr, betas, tau):
         return  # Σ α·P^Q'ᵀ as one matrix product into a flat scratch, then the one-launch fold and optimizer step
+    sks = compressed.sketch_round(messages)
+    if sks is not None and _fold_sketch(sks, alpha, sketch, delta_parameters, _params(model_params), vps, opt, lr,
+                                        betas, tau):
+        return  # the tables added (and the server's state stepped), one unsketch, top-k, then the one-launch fold
     # (the parameters as they are for the one-pass fold: its kernels write θ in place, outside autograd)
     if recs is not None and compressed.fold_records(recs, [alpha] * len(recs), delta_parameters, model_params, vps,
                                                     betas[0], opt if vps is not None else "avg", lr, betas[1], tau,
@@ -898,7 +987,7 @@ class FedOptUpdateMixin:
                else [m["delta_parameters"] for m in self._received_messages])
         fedopt_update(list(self.model.parameters()), self.delta_parameters, self.v_parameters,
                       self._received_messages, self.config.optimizer, self.config.lr, self.config.betas,
-                      self.config.tau)
+                      self.config.tau, sketch=sketch_server_state(self))
 
 
 class SCAFFOLDUpdateMixin:

@@ -711,6 +711,135 @@ def fold_lowrank_records(records: Sequence[torch.Tensor], weights: Sequence[floa
     return out
 
 
+# --------------------------------------------------------------------------------------- count-sketch records
+SKETCH_ROWS = (1, 3, 5)
+SKETCH_MIN_COLS, SKETCH_MAX_COLS = 1 << 12, 1 << 20
+SKETCH_MAX_RECORDS = 64  # records per flc_sketch_estimate / flc_sketch_state_step call
+
+
+def sketch_cols(n: int, rows: int = 5) -> int:
+    """The default table width of a count sketch of ``n`` elements: the largest power of two ``<= n / (4 rows)``,
+    clamped to [2^12, 2^20]."""
+    c = SKETCH_MIN_COLS
+    while c < SKETCH_MAX_COLS and 2 * c * 4 * rows <= n:
+        c *= 2
+    return c
+
+
+def sketch_wire_layout(n: int, rows: int, cols: int) -> int:
+    """Bytes of a count-sketch record (flc_sketch_wire_layout): ``S`` as ``[rows][cols]`` fp32 at 0, padded to 256 B."""
+    total = _lib.size("flc_sketch_wire_layout", int(n), int(rows), int(cols), None)
+    if total == 0:
+        raise ValueError(f"bad count-sketch shape n={n}, rows={rows}, cols={cols}")
+    return total
+
+
+def sketch_table(record: torch.Tensor, rows: int, cols: int) -> torch.Tensor:
+    """The ``[rows, cols]`` float32 view of a count-sketch record (a contiguous uint8 HIP tensor, 16-B aligned) or of a
+    float32 table of ``rows * cols`` cells."""
+    if record.device.type != "cuda" or not record.is_contiguous() or record.dtype not in (torch.uint8, torch.float32):
+        raise TypeError("a sketch is a contiguous uint8 or float32 HIP tensor")
+    rec = record.reshape(-1)
+    flat = rec if rec.dtype == torch.float32 else rec[:4 * rows * cols].view(torch.float32)
+    if rows not in SKETCH_ROWS or flat.numel() < rows * cols or rec.data_ptr() % 16 != 0:
+        raise ValueError(f"a count sketch holds {rows} x {cols} fp32 cells, 16-B aligned, rows one of {SKETCH_ROWS}")
+    return flat[:rows * cols].view(rows, cols)
+
+
+def _sketch_args(records, weights, rows, cols):
+    import ctypes
+
+    if len(records) != len(weights) or not records:
+        raise ValueError("one weight per record, at least one record")
+    tabs = [sketch_table(r, rows, cols) for r in records]
+    ptrs = (ctypes.c_void_p * len(tabs))(*[t.data_ptr() for t in tabs])
+    ws = (ctypes.c_float * len(tabs))(*[float(w) for w in weights])
+    return ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(ws, ctypes.c_void_p), tabs
+
+
+def sketch_encode(x: torch.Tensor, rows: int, cols: int, seed: int, record: Optional[torch.Tensor] = None,
+                  estimate: bool = False):
+    """One message as a count-sketch record (flc_sketch_encode), ``x`` read once; ``estimate``: also the estimate of
+    the record itself.  Returns ``(record, estimate or None)``."""
+    x = _dev_f32(x).reshape(-1)
+    n, dev = x.numel(), x.device
+    stride = sketch_wire_layout(n, rows, cols)
+    if record is None:
+        record = torch.empty(stride, dtype=torch.uint8, device=dev)
+    sketch_table(record, rows, cols)  # (the record's checks)
+    out = torch.empty(n, dtype=torch.float32, device=dev) if estimate else None
+    need = _lib.size("flc_sketch_workspace_size", n, rows, cols)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    call("flc_sketch_encode", _p(x), n, rows, cols, int(seed), _p(record), _p(out), _p(ws), need, _stream(dev))
+    return record, out
+
+
+def sketch_fold(records: Sequence[torch.Tensor], weights: Sequence[float], rows: int, cols: int,
+                table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``table = S̄``, the weighted sum of the records' tables (flc_sketch_fold; any number of records)."""
+    ptrs, ws, tabs = _sketch_args(records, weights, rows, cols)
+    if table is None:
+        table = torch.empty(rows, cols, dtype=torch.float32, device=tabs[0].device)
+    call("flc_sketch_fold", ptrs, ws, len(tabs), rows, cols, _p(sketch_table(table, rows, cols)),
+         _stream(table.device))
+    return table
+
+
+def _sketch_folded(records, weights, rows, cols):
+    """A round of more than 64 records as one folded table of weight 1 (the same arithmetic)."""
+    if len(records) > SKETCH_MAX_RECORDS:
+        return [sketch_fold(records, weights, rows, cols)], [1.0]
+    return records, weights
+
+
+def sketch_estimate(records: Sequence[torch.Tensor], weights: Sequence[float], n: int, rows: int, cols: int, seed: int,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[i] = median_j s_j(i) · S̄[j][cell_j(i)]`` of the records' weighted sum (flc_sketch_estimate): the
+    server's unsketch.  Records may be wire records or float32 tables."""
+    records, weights = _sketch_folded(records, weights, rows, cols)
+    ptrs, ws, tabs = _sketch_args(records, weights, rows, cols)
+    dev = tabs[0].device
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or out.device != dev or out.numel() != n or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of n elements on the records' device")
+    call("flc_sketch_estimate", ptrs, ws, len(tabs), n, rows, cols, int(seed), _p(out), _stream(dev))
+    return out
+
+
+def sketch_state_step(records: Sequence[torch.Tensor], weights: Sequence[float], rows: int, cols: int, rho: float,
+                      u: torch.Tensor, v: Optional[torch.Tensor] = None) -> None:
+    """FetchSGD's server state (flc_sketch_state_step): ``u = fmaf(rho, u, S̄)``, ``v = v + u``."""
+    records, weights = _sketch_folded(records, weights, rows, cols)
+    ptrs, ws, tabs = _sketch_args(records, weights, rows, cols)
+    call("flc_sketch_state_step", ptrs, ws, len(tabs), rows, cols, float(rho), _p(sketch_table(u, rows, cols)),
+         _p(None if v is None else sketch_table(v, rows, cols)), _stream(u.device))
+
+
+def _sketch_idx(idx: torch.Tensor) -> torch.Tensor:
+    if idx.dtype != torch.int32 or idx.device.type != "cuda" or not idx.is_contiguous():
+        raise TypeError("idx must be a contiguous int32 HIP tensor")
+    return idx.reshape(-1)
+
+
+def sketch_clear(idx: torch.Tensor, n: int, rows: int, cols: int, seed: int, u: Optional[torch.Tensor],
+                 v: Optional[torch.Tensor] = None) -> None:
+    """Zero the cells of the elements ``idx`` in the tables ``u`` and ``v`` (flc_sketch_clear)."""
+    idx = _sketch_idx(idx)
+    call("flc_sketch_clear", _p(idx), idx.numel(), n, rows, cols, int(seed),
+         _p(None if u is None else sketch_table(u, rows, cols)), _p(None if v is None else sketch_table(v, rows, cols)),
+         _stream(idx.device))
+
+
+def sketch_cells(idx: torch.Tensor, n: int, rows: int, cols: int, seed: int):
+    """Point queries (flc_sketch_cells): ``(cell [k, rows] int64, negative [k, rows] bool)`` of the elements ``idx``."""
+    idx = _sketch_idx(idx)
+    raw = torch.zeros(idx.numel(), rows, dtype=torch.int32, device=idx.device)
+    call("flc_sketch_cells", _p(idx), idx.numel(), n, rows, cols, int(seed), _p(raw), _stream(idx.device))
+    raw = raw.to(torch.int64) & 0xFFFFFFFF
+    return raw & 0x7FFFFFFF, (raw >> 31).bool()
+
+
 def fold_dense_wires(wires: torch.Tensor, slots: Sequence[int], weights: Sequence[float], n: int, fmt: int,
                      levels: int, bits: int, out: Optional[torch.Tensor] = None,
                      accumulate: bool = False) -> torch.Tensor:

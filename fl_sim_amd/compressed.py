@@ -116,7 +116,7 @@ import torch
 from . import _lib, codec
 from ._lib import FLC_NORM_INF, FLC_NORM_L2, FLC_Q_NATURAL_DITHER, FLC_Q_STANDARD_DITHER, FLC_WIRE_NATURAL
 from . import rng as _rng
-from .compressors import Compressor, CompressorType, LowRankCompressor, SignCompressor
+from .compressors import Compressor, CompressorType, LowRankCompressor, SignCompressor, SketchCompressor
 from .feedback import ErrorFeedbackClientMixin, ErrorMemory
 
 
@@ -158,15 +158,22 @@ class CompressedDelta(_abc.Sequence):
     (one scale per bucket, then one bit per element; flc_sign_wire_layout); ``kind == "lowrank"`` (``wire=True`` with
     a :class:`LowRankCompressor`; ``lowrank=(cols, rank)``): the low-rank record (``P^`` then ``Q'``;
     flc_lowrank_wire_layout), which only FedOpt's device fold reads as a record — every other reader takes its decoded
-    vector; ``kind == "dense"``: the decoded flat delta.
+    vector; ``kind == "sketch"`` (``wire=True`` with a :class:`SketchCompressor`; ``sketch=(rows, cols, seed)``): the
+    count-sketch record (flc_sketch_wire_layout), which FedOpt's device fold adds to the round's other sketches without
+    decoding — every other reader takes the median-of-rows estimate of this single record;
+    ``kind == "dense"``: the decoded flat delta.
     Indexing gives tensor ``j`` of the model's shapes (the decoded values, one flat decode on first access), so code
     written for a list of delta tensors reads it unchanged."""
 
     def __init__(self, shapes: Sequence[torch.Size], device: torch.device, n: int, *, record=None, k: int = 0,
                  levels: int = 0, flat: Optional[torch.Tensor] = None, batch: Optional["_Batch"] = None,
                  format: Optional[int] = None, bits: int = 0, sparse: bool = False, bucket: int = 0,
-                 sign: bool = False, lowrank: Optional[Tuple[int, int]] = None):
+                 sign: bool = False, lowrank: Optional[Tuple[int, int]] = None,
+                 sketch: Optional[Tuple[int, int, int]] = None):
         self.cols, self.rank = (int(lowrank[0]), int(lowrank[1])) if lowrank else (0, 0)
+        self.rows, self.seed = 0, 0
+        if sketch:  # (a count-sketch record, flc_sketch_wire_layout(n, rows, cols), hashed with seed)
+            self.rows, self.cols, self.seed = int(sketch[0]), int(sketch[1]), int(sketch[2])
         self.shapes = [torch.Size(s) for s in shapes]
         self.device = device
         self.n = int(n)
@@ -174,7 +181,9 @@ class CompressedDelta(_abc.Sequence):
         self._batch = batch  # (a deferred encode: the record is made by the batch's launch on first access)
         self.format, self.bits = format, int(bits)
         self.bucket = int(bucket)  # a bucket record's bucket size (flc_bucket_wire_layout), else 0
-        if lowrank:  # (a low-rank record, flc_lowrank_wire_layout(n, cols, rank))
+        if sketch:
+            self.kind = "sketch"
+        elif lowrank:  # (a low-rank record, flc_lowrank_wire_layout(n, cols, rank))
             self.kind = "lowrank"
         elif sign:  # (a scaled-sign record, flc_sign_wire_layout(n, bucket): bucket 0 is the whole vector)
             self.kind = "sign"
@@ -200,6 +209,8 @@ class CompressedDelta(_abc.Sequence):
     def codec_key(self) -> tuple:
         """What a round's records must share to be folded together."""
         key = (self.kind, self.n, self.k, self.levels, self.format, self.bits, self.bucket)
+        if self.kind == "sketch":  # (sketches of different hashes do not add)
+            return key + (self.rows, self.cols, self.seed)
         return key + (self.cols, self.rank) if self.kind == "lowrank" else key
 
     def __getstate__(self):
@@ -209,7 +220,7 @@ class CompressedDelta(_abc.Sequence):
             self._batch.run()
         d = self.__dict__.copy()
         d["_batch"] = None
-        if self.kind in ("quant", "natural", "bucket", "sign", "lowrank"):
+        if self.kind in ("quant", "natural", "bucket", "sign", "lowrank", "sketch"):
             d["_flat"] = d["_views"] = None
         return d
 
@@ -218,6 +229,8 @@ class CompressedDelta(_abc.Sequence):
         self.__dict__.setdefault("bucket", 0)  # (a delta pickled before bucket records existed)
         self.__dict__.setdefault("cols", 0)  # (... before low-rank records existed)
         self.__dict__.setdefault("rank", 0)
+        self.__dict__.setdefault("rows", 0)  # (... before count-sketch records existed)
+        self.__dict__.setdefault("seed", 0)
 
     @property
     def nbytes(self) -> int:
@@ -228,7 +241,9 @@ class CompressedDelta(_abc.Sequence):
         """The decoded flat delta (flc_stacked_decode_tiled, flc_sparse_decode_tiled, flc_quant_decode or
         flc_natural_decode of the record, once)."""
         if self._flat is None:
-            if self.kind == "lowrank":
+            if self.kind == "sketch":
+                self._flat = codec.sketch_estimate([self.record], [1.0], self.n, self.rows, self.cols, self.seed)
+            elif self.kind == "lowrank":
                 self._flat = codec.lowrank_decode(self.record, self.n, self.cols, self.rank)
             elif self.kind == "sign":
                 self._flat = codec.sign_decode(self.record, self.n, self.bucket)
@@ -681,6 +696,21 @@ def _lowrank_record(x: torch.Tensor, shapes, n: int, comp: LowRankCompressor, de
     return CompressedDelta(shapes, dev, n, record=rec, lowrank=(comp.cols, comp.rank))
 
 
+def _sketch_wire(compressors: Sequence[Compressor], wire: bool) -> Optional[SketchCompressor]:
+    """The one :class:`SketchCompressor` whose record a ``wire`` message carries, else None."""
+    if wire and len(compressors) == 1 and isinstance(compressors[0], SketchCompressor):
+        return compressors[0]
+    return None
+
+
+def _sketch_record(x: torch.Tensor, shapes, n: int, comp: SketchCompressor, dev) -> CompressedDelta:
+    """The count-sketch record of the flat fp32 vector ``x`` in one flc_sketch_encode."""
+    if n != comp.D:
+        raise ValueError(f"Sketch compressor built for D={comp.D} applied to a message of {n} elements")
+    rec, _ = comp.encode(x)
+    return CompressedDelta(shapes, dev, n, record=rec, sketch=(comp.rows, comp.cols, comp.seed))
+
+
 def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]],
               compressors: Sequence[Compressor], wire: bool = False, sparse: bool = False,
               bucket: int = 0) -> CompressedDelta:
@@ -728,6 +758,9 @@ def _compress(local: List[torch.Tensor], cached: Optional[Sequence[torch.Tensor]
     lr = _lowrank_wire(compressors, wire)
     if lr is not None and out.dtype == torch.float32:  # the low-rank record as the message, nothing decoded
         return _lowrank_record(out, shapes, n, lr, dev)
+    sk = _sketch_wire(compressors, wire)
+    if sk is not None and out.dtype == torch.float32:  # the table as the message, nothing estimated
+        return _sketch_record(out, shapes, n, sk, dev)
     dc = dense_wire_codec(compressors) if wire else None
     B = _bucket_of(compressors, bucket)
     if B and dc is not None and out.dtype == torch.float32:  # a bucket record: one norm per B elements, then the codes
@@ -781,6 +814,9 @@ def _compress_feedback(local: List[torch.Tensor], cached: Optional[Sequence[torc
     then ``e = a − c`` (fl_sim_amd/feedback.py): the K-entry residual of a stacked record (after the batched encode
     when the message is deferred), the K-entry residual of a sparse record likewise (flc_ef_residual_sparse_round),
     the dense one of any other compressor's decoded vector."""
+    if any(isinstance(c, SketchCompressor) for c in compressors):
+        raise ValueError("error_feedback with a SketchCompressor: a count sketch keeps its error in the server's "
+                         "sketch (sketch_error on the server), the clients hold no memory")
     dev = local[0].device if local[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
     shapes = [t.shape for t in local]
     n = sum(t.numel() for t in local)
@@ -1383,6 +1419,12 @@ def lowrank_round(messages: Sequence, key: str = "delta_parameters") -> Optional
     return _round_deltas(messages, key, ("lowrank",))
 
 
+def sketch_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
+    """The messages' compressed deltas when every one is a count-sketch record of one (n, rows, cols, seed), else
+    None.  As :func:`lowrank_round`, only FedOpt's device fold reads these as records."""
+    return _round_deltas(messages, key, ("sketch",))
+
+
 def record_round(messages: Sequence, key: str = "delta_parameters") -> Optional[List[CompressedDelta]]:
     """:func:`stacked_round`, :func:`dense_record_round` or :func:`sparse_round`: a round the record folds take, else
     None."""
@@ -1475,7 +1517,7 @@ def mixed_round(messages: Sequence, key: str = "delta_parameters") -> Optional[L
             return None
         ds.append(d)
     d0 = ds[0]
-    if any(d.n != d0.n for d in ds) or all(d.kind in ("dense", "bucket", "sign", "lowrank") for d in ds):
+    if any(d.n != d0.n for d in ds) or all(d.kind in ("dense", "bucket", "sign", "lowrank", "sketch") for d in ds):
         return None
     if all(d.codec_key == d0.codec_key for d in ds):
         return None
@@ -1493,7 +1535,7 @@ def _mixed_tables(deltas: Sequence[CompressedDelta], dev: torch.device, records=
     for i, d in enumerate(deltas):
         if d.kind == "dense":
             t, desc = d._flat, (_REC_FLAT, 0, 0, 0, 0)
-        elif d.kind in ("bucket", "sign", "lowrank"):  # (not in the mixed fold's descriptor tables: read as its decoded vector)
+        elif d.kind in ("bucket", "sign", "lowrank", "sketch"):  # (not in the mixed fold's descriptor tables: read as its decoded vector)
             t, desc = d.flat(), (_REC_FLAT, 0, 0, 0, 0)
         else:
             t = d.record

@@ -48,7 +48,7 @@ from . import rng as _rng
 from ._lib import FLC_Q_NATURAL_DITHER, FLC_Q_STANDARD_DITHER
 
 __all__ = ["CompressorType", "Compressor", "SignCompressor", "SIGN_COMPRESSOR", "LowRankCompressor",
-           "LOWRANK_COMPRESSOR"]
+           "LOWRANK_COMPRESSOR", "SketchCompressor", "SKETCH_COMPRESSOR"]
 
 
 @unique
@@ -864,3 +864,63 @@ class LowRankCompressor(Compressor):
 
     def _compress_device(self, x: torch.Tensor, host_norm=None) -> torch.Tensor:
         return self.encode(x, decode=True)[1]
+
+
+SKETCH_COMPRESSOR = "SKETCH_COMPRESSOR"  # SketchCompressor.compressorType: outside CompressorType, as SIGN_COMPRESSOR
+
+
+class SketchCompressor(Compressor):
+    """Count Sketch of FetchSGD (Rothchild et al., 2020): the message is a ``rows x cols`` fp32 table that is LINEAR in
+    the vector, so a server adds the clients' tables without decoding them and keeps momentum and error in tables of
+    its own (aggregation.fedopt_update's device path) — clients hold no error memory.  Biased.  ``cols=None``: the
+    largest power of two ``<= D / (4 rows)``, clamped to [2^12, 2^20].  ``seed`` is shared by every client and the
+    server of a run.  ``compressVector`` returns the median-of-rows estimate of the vector's own sketch, cut to its
+    ``K`` largest magnitudes when ``K > 0``.  An extension over the reference: its type is the sentinel
+    ``SKETCH_COMPRESSOR``.  Deterministic: the hash is a function of ``seed`` alone."""
+
+    def __init__(self, D: int, rows: int = 5, cols: Optional[int] = None, K: int = 0, seed: int = 0):
+        super().__init__("SketchCompressor")
+        if int(D) < 1:
+            raise ValueError(f"D must be >= 1 (got {D})")
+        self.D, self.rows = int(D), int(rows)
+        if self.rows not in codec.SKETCH_ROWS:
+            raise ValueError(f"rows must be one of {codec.SKETCH_ROWS} (got {rows})")
+        self.cols = codec.sketch_cols(self.D, self.rows) if cols is None else int(cols)
+        if not (codec.SKETCH_MIN_COLS <= self.cols <= codec.SKETCH_MAX_COLS) or self.cols & (self.cols - 1):
+            raise ValueError(f"cols must be a power of two in [2^12, 2^20] (got {cols})")
+        if not 0 <= int(K) <= self.D:
+            raise ValueError(f"K must be in [0, D] (got {K})")
+        self.K, self.seed = int(K), int(seed)
+
+    compressorType = property(lambda self: SKETCH_COMPRESSOR)
+    is_biased = property(lambda self: True)
+    w = property(lambda self: 0.0)
+    name = property(lambda self: f"Count sketch [D={self.D},r={self.rows},c={self.cols}]")
+    fullName = name
+
+    def send_components(self) -> float:
+        """fp32 components per message: the table."""
+        return float(self.rows * self.cols)
+
+    def encode(self, x: torch.Tensor, estimate: bool = False):
+        """(record, estimate or None) of the flat fp32 device vector ``x`` (codec.sketch_encode)."""
+        rec, out = codec.sketch_encode(x, self.rows, self.cols, self.seed, estimate=estimate)
+        self._finish(self.D, self.send_components())
+        return rec, out
+
+    def compressVector(self, x):
+        """One flc_sketch_encode with ``out`` (device and numpy inputs alike), then the top ``K`` of the estimate by
+        magnitude."""
+        shape, dtype = tuple(x.shape), x.dtype  # (refusals first: nothing is copied or launched for them)
+        if len(shape) != 1 or shape[0] != self.D:
+            raise ValueError(f"Sketch compressor built for D={self.D} applied to a vector of shape {shape}")
+        if str(dtype).endswith("float64"):  # (torch.float64 or numpy's)
+            raise ValueError("the sketch compressor takes float32 vectors")
+        return super().compressVector(x)
+
+    def _compress_device(self, x: torch.Tensor, host_norm=None) -> torch.Tensor:
+        est = self.encode(x, estimate=True)[1]
+        if self.K > 0:
+            idx, val = codec.topk_encode(est, self.K, order=codec.ORDER_MAGNITUDE)[:2]
+            est = codec.sparse_decode(idx, val, self.D)
+        return est

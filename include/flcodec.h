@@ -345,8 +345,70 @@ int flc_lowrank_decode(const void* record, int64_t n, int64_t cols, int rank, fl
 int flc_fold_lowrank_records(const void* const* records, const float* weights, int n_records, int64_t n, int64_t cols,
                              int rank, int accumulate, float* out, void* stream);
 
+/* ------------------------------------------------------------------ count sketch (FetchSGD)
+ * The Count Sketch of FetchSGD (Rothchild et al., ICML 2020) with a tiled hash.  A sketch is LINEAR: the server adds
+ * the clients' records (rows x cols floats) without decoding them, keeps momentum and error in sketches of its own,
+ * and recovers the heavy coordinates once per round by a median-of-rows estimate and a top-k by magnitude.
+ * float32 only; n in [1, 2^31); rows r in {1, 3, 5}; cols c a power of two in [2^12, 2^20]; tile T = 1024,
+ * NT = c / T; a 64-bit seed shared by every client and the server of a run.  Random words: philox_group(group, seed,
+ * counter) -> (x, y, z, w), Philox4x32-10 with counter words (group lo, group hi, counter lo, counter hi), key = seed.
+ * Element i lies in chunk q = i / c, source tile p = (i mod c) / T, offset o = i mod T, global tile g = i / T;
+ * elements at and past n read as +0.
+ *   Tile map (all rows): (x, y) = philox_group(q, seed, 0x100);  A_q = (x | 1) mod NT, B_q = y mod NT;  table tile tau
+ *     of chunk q receives source tile p = (A_q tau + B_q) mod NT (A_q odd: a bijection; NT = 1: p = tau = 0).
+ *   In-tile permutation (row j, tile g): (x, y) = philox_group(g, seed, 0x200 + j);  a = (x | 1) mod T, b = y mod T;
+ *     offset o lands at (a o + b) mod T.
+ *   Sign: s_j(i) = -1 if bit i & 31 of word (i >> 5) & 3 of philox_group(i >> 7, seed, 0x300 + j) is set, else +1.
+ *   Table:    S[j][cell_j(i)] += s_j(i) x_i,  cell_j(i) = T tau + (a o + b) mod T.
+ *   Estimate: x^_i = median_j s_j(i) S[j][cell_j(i)].
+ * Two elements of one chunk never collide; elements of different chunks collide with probability 1 / c per row.
+ * Record (flc_sketch_wire_layout): S as [r][c] fp32 at offsets[0] = 0, padded to 256 B; returns the size, 0 for bad
+ * arguments.  A pure host function.
+ *
+ * Split rule of the encode, by (n, c) alone: Q = ceil(n / c) chunks; a split takes cps = max(8, ceil(Q NT / 1024))
+ * consecutive chunks; flc_sketch_splits returns ceil(Q / cps) (0 for bad arguments).  Each split accumulates
+ * its chunks ascending from +0 in fp32; a cell of the record is the splits' partials added in fp64, splits ascending
+ * from 0.0, rounded once.  No atomics, no grid-wide wait: the record's bytes are a function of
+ * (x, n, rows, cols, seed) only. */
+size_t flc_sketch_wire_layout(int64_t n, int rows, int64_t cols, int64_t* offsets);
+int flc_sketch_splits(int64_t n, int64_t cols);
+/* bytes of flc_sketch_encode's workspace (the splits' partials; 256 with one split, which writes the record itself);
+ * 0 for bad arguments */
+size_t flc_sketch_workspace_size(int64_t n, int rows, int64_t cols);
+/* encode one message: ONE read of x.  record: flc_sketch_wire_layout bytes, 16-B aligned.  out (optional, n floats):
+ * the call ends with the estimate of its own record (weight 1).  ws: flc_sketch_workspace_size bytes, 256-B aligned.
+ * No host synchronisation, no status word: capturable.  FLC_EINVAL (nothing launched): a null x or record, n, rows or
+ * cols outside the sets above, a pointer not 16-B aligned, a null, short or misaligned workspace. */
+int flc_sketch_encode(const float* x, int64_t n, int rows, int64_t cols, uint64_t seed, void* record, float* out,
+                      void* ws, size_t ws_bytes, void* stream);
+/* The weighted sum of a round's tables, per cell:  S-bar = fp32(w_0 S_0), then fmaf(w_c, S_c, S-bar) for records
+ * ascending (flc_weighted_sum's arithmetic with init_mode 1).  records / weights: HOST arrays; records of one
+ * (rows, cols), 16-B aligned device pointers.
+ * flc_sketch_estimate: out[i] = median_j s_j(i) S-bar[j][cell_j(i)] for i < n (the median of three is v_med3_f32, of
+ * five a min / max network; a NaN cell gives an unspecified estimate).  At most 64 records per call: a longer round is
+ * folded first (flc_sketch_fold) and its table estimated as one record of weight 1, which is the same arithmetic.
+ * flc_sketch_fold: table = S-bar; any number of records, launches chained per 64, each continuing the fmaf chain from
+ * the stored value.
+ * flc_sketch_state_step: FetchSGD's server state, elementwise on r c cells:  u = fmaf(rho, u, S-bar);  v = v + u
+ * (v optional).  At most 64 records per call (fold a longer round first).
+ * FLC_EINVAL: null arguments, n_records < 1 (or > 64 where stated), a bad shape, a pointer not 16-B aligned. */
+int flc_sketch_estimate(const void* const* records, const float* weights, int n_records, int64_t n, int rows,
+                        int64_t cols, uint64_t seed, float* out, void* stream);
+int flc_sketch_fold(const void* const* records, const float* weights, int n_records, int rows, int64_t cols,
+                    float* table, void* stream);
+int flc_sketch_state_step(const void* const* records, const float* weights, int n_records, int rows, int64_t cols,
+                          float rho, float* u, float* v, void* stream);
+/* flc_sketch_clear: u[j][cell_j(i)] = v[j][cell_j(i)] = +0 for every i = idx[e], e < k, and row j (either table may be
+ * NULL; an index outside [0, n) is skipped): the error the server has just applied leaves its sketches.
+ * flc_sketch_cells: the same cell function as a point query, cells[e * rows + j] = cell_j(idx[e]) | (s_j < 0) << 31.
+ * idx: k int32 on the device. */
+int flc_sketch_clear(const int32_t* idx, int64_t k, int64_t n, int rows, int64_t cols, uint64_t seed, float* u,
+                     float* v, void* stream);
+int flc_sketch_cells(const int32_t* idx, int64_t k, int64_t n, int rows, int64_t cols, uint64_t seed, uint32_t* cells,
+                     void* stream);
+
 /* ------------------------------------------------------------------ natural compressor
- * (compressors.py:302-325).  Wire: one uint16 per element, 0 = zero, else sign << 15 | (e + 150)
+ * (compressors.py:302-325). Wire: one uint16 per element, 0 = zero, else sign << 15 | (e + 150)
  * for the chosen power of two 2^e, e in [-149, 127]. */
 size_t flc_natural_workspace_size(int64_t n);  /* needed in compat mode only */
 int flc_natural_encode(const float* x, int64_t n, uint64_t seed, uint64_t counter,
