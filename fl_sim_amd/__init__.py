@@ -17,10 +17,11 @@ there is no CPU fallback.
 import os
 
 from . import _lib
+from .codec import ROBUST_MAX_SRC, ROBUST_RULES  # the server switch ``robust``'s values, its limit on a round's messages
 from .compressors import Compressor, CompressorType, LowRankCompressor, SignCompressor, SketchCompressor
 
 __all__ = ["Compressor", "CompressorType", "SignCompressor", "LowRankCompressor", "SketchCompressor", "native_library",
-           "load_torch_ops", "__version__"]
+           "load_torch_ops", "ROBUST_RULES", "ROBUST_MAX_SRC", "__version__"]
 __version__ = "0.1.0"
 
 

@@ -27,6 +27,7 @@ at the boundary, as torch does.
 from __future__ import annotations
 
 import math
+import numbers
 from typing import Iterable, List, Mapping, Optional, Sequence
 
 import torch
@@ -525,14 +526,68 @@ def _fold_sketch(sks, alpha: float, state: Optional[SketchServerState], delta_pa
     return True
 
 
+def robust_rule(rule, trim, n_messages: int):
+    """The checked ``(rule, b)`` of a robust round of ``n_messages`` messages, or None for ``rule`` None (the mean).
+    ``rule``: "median" or "trimmed_mean"; ``trim``: an int is b, the values dropped per side and coordinate; a float f
+    with 0 <= f < 0.5 gives b = int(f * n_messages).  ValueError for anything else, for more than 64 messages and for
+    a b that keeps nothing (2b >= n_messages)."""
+    if rule is None:
+        return None
+    if rule not in codec.ROBUST_RULES:
+        raise ValueError(f"robust must be None or one of {codec.ROBUST_RULES}, not {rule!r}")
+    if not 1 <= n_messages <= codec.ROBUST_MAX_SRC:
+        raise ValueError(f"a robust round takes 1 to {codec.ROBUST_MAX_SRC} messages (the client axis is sorted in "
+                         f"one launch), not {n_messages}")
+    if rule == "median":
+        return rule, 0
+    if isinstance(trim, bool) or not isinstance(trim, numbers.Real):  # (numpy's scalars are Integral / Real too)
+        raise ValueError(f"robust_trim must be an int or a float in [0, 0.5), not {trim!r}")
+    if not isinstance(trim, numbers.Integral):
+        if not 0.0 <= trim < 0.5:
+            raise ValueError(f"robust_trim as a fraction must be in [0, 0.5), not {trim}")
+        trim = float(trim) * n_messages
+    trim = int(trim)
+    if trim < 0 or 2 * trim >= n_messages:
+        raise ValueError(f"robust_trim must satisfy 0 <= 2 * b < {n_messages} messages, not b = {trim}")
+    return rule, trim
+
+
+def _fedopt_robust(model_params, delta_parameters, vps, msgs, opt: str, lr: float, betas, tau: float, rule: str,
+                   b: int) -> None:
+    """FedOptServer.update with the coordinate-wise median or trimmed mean r of the messages' deltas where their mean
+    stood: ``δ = fmaf(1 - β0, r, δ·β0)`` and the optimiser step, one flc_robust_fold launch per pack.  ``msgs``: one
+    list of tensors per message (a compressed message as its decoded list); ``(rule, b)`` as :func:`robust_rule`
+    checked them."""
+    if hoststage.is_host(model_params):
+        groups = [model_params, delta_parameters] + ([vps] if vps is not None else [])
+        n = len(groups)
+        with hoststage.staged(groups, [True] * n, [True] * n, msgs) as (dg, dm):
+            _fedopt_robust(dg[0], dg[1], dg[2] if vps is not None else None, dm, opt, lr, betas, tau, rule, b)
+        return
+    codec.robust_fold(delta_parameters, msgs, rule, b, 1 - betas[0], 0, betas[0], theta=_params(model_params), v=vps,
+                      opt=opt if vps is not None else "avg", lr=lr, beta2=betas[1], tau=tau)
+
+
 def fedopt_update(model_params: Sequence[torch.Tensor], delta_parameters: Sequence[torch.Tensor],
                   v_parameters: Optional[Sequence[torch.Tensor]], messages: Sequence[Mapping], optimizer: str,
-                  lr: float, betas: Sequence[float], tau: float, sketch: Optional[SketchServerState] = None) -> None:
+                  lr: float, betas: Sequence[float], tau: float, sketch: Optional[SketchServerState] = None,
+                  robust=None) -> None:
     """_fedopt.py:196-265 (FedAvg: optimizer="avg", lr=1, betas=(0, 1)).  ``sketch``: the server's state for a round
-    of count-sketch records (:func:`_fold_sketch`); None reads such a round statelessly, its dense estimate."""
+    of count-sketch records (:func:`_fold_sketch`); None reads such a round statelessly, its dense estimate.
+    ``robust``: ``("median", 0)`` or ``("trimmed_mean", b)`` puts that coordinate-wise rule over the messages' deltas
+    where their mean stood (:func:`robust_rule`; at most 64 messages, not with a sketch server that keeps top-k)."""
     opt = optimizer.lower()
     if opt not in ("avg", "adagrad", "yogi", "adam"):
         raise ValueError(f"Unknown optimizer: {optimizer}")
+    if robust is not None:
+        if sketch is not None and (sketch.k > 0 or sketch.stateful):
+            raise ValueError("robust aggregation needs every client's message; a count-sketch server (sketch_k > 0, "
+                             "momentum or error tables) adds the tables and never sees one")
+        rule, b = robust_rule(robust[0], robust[1], len(messages))
+        _fedopt_robust(list(model_params), list(delta_parameters),
+                       None if (v_parameters is None or opt == "avg") else list(v_parameters),
+                       [list(m["delta_parameters"]) for m in messages], opt, lr, betas, tau, rule, b)
+        return
     alpha = (1 - betas[0]) / len(messages) if len(messages) else 0.0
     model_params, delta_parameters = list(model_params), list(delta_parameters)
     vps = None if (v_parameters is None or opt == "avg") else list(v_parameters)
@@ -977,10 +1032,26 @@ class pFedMacUpdateMixin(VRUpdateMixin):  # noqa: N801 (the reference's class na
 
 class FedOptUpdateMixin:
     """Device ``update()`` for the reference's ``FedOptServer`` family (_fedopt.py:196-240), for a server model on a
-    HIP device or in host memory."""
+    HIP device or in host memory.
+
+    Two switches, read on the server and then on its config: ``robust`` (None, "median" or "trimmed_mean") replaces
+    the mean of the round's deltas by that coordinate-wise rule, and ``robust_trim`` (an int b, or a fraction of the
+    round's messages in [0, 0.5)) is the trimmed mean's count dropped per side (:func:`robust_rule`)."""
 
     def update(self) -> None:
         adaptive = self.v_parameters is not None and self.config.optimizer.lower() != "avg"
+        rule = _switch(self, "robust", None)
+        if rule is not None:  # checked before anything is staged or launched
+            rule, b = robust_rule(rule, _switch(self, "robust_trim", 0), len(self._received_messages))
+            if int(_switch(self, "sketch_k", 0)) > 0:
+                raise ValueError("robust and sketch_k > 0 do not combine: the sketch server adds the clients' tables "
+                                 "and never sees one client's message")
+            msgs = [list(m["delta_parameters"]) for m in self._received_messages]  # (compressed: decoded here, once)
+            vps = list(self.v_parameters) if adaptive else None
+            _adopt([list(self.model.parameters()), self.delta_parameters, vps], msgs)
+            _fedopt_robust(list(self.model.parameters()), list(self.delta_parameters), vps, msgs,
+                           self.config.optimizer.lower(), self.config.lr, self.config.betas, self.config.tau, rule, b)
+            return
         recs = compressed.record_round(self._received_messages)  # (compressed messages: the fold reads the records)
         _adopt([list(self.model.parameters()), self.delta_parameters, self.v_parameters if adaptive else None],
                [[d.record] for d in recs] if recs is not None

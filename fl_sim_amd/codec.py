@@ -1872,6 +1872,64 @@ def model_fold(dsts: Sequence[torch.Tensor], srcs: Sequence[Sequence[torch.Tenso
          float(tau), torch.cuda.current_stream(dev).cuda_stream)
 
 
+ROBUST_MAX_SRC = _lib.FLC_ROBUST_MAX_SRC
+ROBUST_RULES = tuple(_lib.FLC_ROBUST)
+
+
+def robust_fold(dsts: Sequence[torch.Tensor], srcs: Sequence[Sequence[torch.Tensor]], rule: str, trim: int = 0,
+                scale: float = 1.0, init_mode: int = 1, beta: float = 0.0,
+                theta: Optional[Sequence[torch.Tensor]] = None, v: Optional[Sequence[torch.Tensor]] = None,
+                opt: str = "avg", lr: float = 1.0, beta2: float = 0.0, tau: float = 0.0) -> None:
+    """The coordinate-wise median (``rule`` "median") or trimmed mean ("trimmed_mean", ``trim`` values dropped per
+    side) of a whole model's messages (flc_robust_fold): per tensor t and element, ``r`` = the rule over
+    ``srcs[m][t]`` in IEEE totalOrder (a NaN sorts to an end), ``dsts[t] = fmaf(scale, r, init(dsts[t]))`` and, with
+    ``theta``, ``fedopt_step(theta[t], dsts[t], v[t], opt, lr, beta2, tau)`` in the same pass.  ``srcs[m]`` is message
+    m's list of tensors, 1 to 64 messages; a message tensor elsewhere is moved to the dsts' device."""
+    import ctypes
+
+    nt, ns = len(dsts), len(srcs)
+    if rule not in _lib.FLC_ROBUST:
+        raise ValueError(f"robust_fold: rule must be one of {ROBUST_RULES}, not {rule!r}")
+    if not 1 <= ns <= ROBUST_MAX_SRC:
+        raise ValueError(f"robust_fold takes 1 to {ROBUST_MAX_SRC} messages, not {ns}")
+    trim = int(trim) if rule == "trimmed_mean" else 0
+    if trim < 0 or 2 * trim >= ns:
+        raise ValueError(f"robust_fold: 0 <= 2 * trim < {ns} messages, not trim {trim}")
+    if opt not in _lib.FLC_OPT:
+        raise ValueError(f"Unknown optimizer: {opt}")
+    if theta is not None and opt != "avg" and v is None:
+        raise ValueError("robust_fold: v is required for an adaptive optimizer")
+    if nt == 0:
+        return
+    f32, dev = torch.float32, dsts[0].get_device()
+    sizes = [t.numel() for t in dsts]
+
+    def ptrs(ts, what, move=False):
+        if len(ts) != nt:
+            raise ValueError(f"{what}: one tensor per model tensor")
+        out = []
+        for t, n in zip(ts, sizes):
+            if move and not (t.is_cuda and t.get_device() == dev):
+                t = t.detach().to(f"cuda:{dev}")
+                keep.append(t)
+            if not (t.is_cuda and t.dtype is f32 and t.is_contiguous() and t.get_device() == dev and t.numel() == n):
+                raise TypeError(f"{what} tensors must be contiguous fp32 HIP tensors of the model's sizes on one device")
+            out.append(t.data_ptr())
+        return out
+
+    keep: list = []  # (moved message tensors, alive until the launch is queued on their stream)
+    P = ctypes.c_void_p
+    vp = lambda a: ctypes.cast(a, P)  # noqa: E731
+    dp = ptrs(dsts, "model")
+    sp = [q for m in srcs for q in ptrs(m, "message", move=True)]
+    with torch.cuda.device(dev):
+        call("flc_robust_fold", vp((P * nt)(*dp)), vp((P * len(sp))(*sp)), ns, vp((ctypes.c_int64 * nt)(*sizes)), nt,
+             _lib.FLC_ROBUST[rule], trim, float(scale), int(init_mode), float(beta),
+             None if theta is None else vp((P * nt)(*ptrs(theta, "theta"))),
+             None if (v is None or theta is None) else vp((P * nt)(*ptrs(v, "v"))), _lib.FLC_OPT[opt], float(lr),
+             float(beta2), float(tau), torch.cuda.current_stream(dev).cuda_stream)
+
+
 def fedopt_step(theta: torch.Tensor, delta: torch.Tensor, v: Optional[torch.Tensor], opt: str, lr: float,
                 beta2: float, tau: float) -> None:
     dt = theta.dtype

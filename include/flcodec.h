@@ -1054,6 +1054,31 @@ int flc_weighted_sum(const float* const* srcs, const float* weights, int n_src, 
 int flc_model_fold(float* const* dst, const float* const* srcs, const float* weights, int n_src, const int64_t* sizes,
                    int n_tensors, int init_mode, float beta, float* const* theta, float* const* v, int opt, double lr,
                    double beta2, double tau, void* stream);
+/* Robust aggregation of a whole model: per coordinate, the median or the trimmed mean of the n_src messages' values
+ * (Yin et al. 2018) where flc_model_fold takes their weighted mean, with the same store and step.
+ *   Order.  x_0 .. x_{C-1} (C = n_src, 1 <= C <= FLC_ROBUST_MAX_SRC) are ordered by IEEE-754 totalOrder, that is by
+ *     the signed 32-bit key k = bits ^ ((bits >> 31) & 0x7fffffff):  -NaN < -inf < .. < -0 < +0 < .. < +inf < +NaN.
+ *     s_0 <= .. <= s_{C-1} is that order.  A NaN is a value like any other: it sorts to an end and is trimmed as an
+ *     outlier is, and every result below is defined for every input.
+ *   FLC_ROBUST_MEDIAN (trim is checked as below and otherwise unused).  C odd: r = s_{(C-1)/2}, a selection, bit for bit.  C even:
+ *     r = 0.5f * s_{C/2-1} + 0.5f * s_{C/2}: two fp32 products and one fp32 add, not contracted.
+ *   FLC_ROBUST_TRIMMED, trim = b per side, 0 <= 2b < C.  r = (s_b + .. + s_{C-1-b}) / float(C - 2b): the kept values
+ *     alone are summed, in fp32, in ASCENDING order ((..(s_b + s_{b+1}) + ..) + s_{C-1-b}; one kept value is itself),
+ *     then one IEEE fp32 division.  b = 0 is the plain mean (in ascending, not message, order).
+ *   Store and step, as flc_model_fold:  a = fmaf(scale, r, init(dst)) with init_mode 0 (dst * beta), 1 (+0) or
+ *     2 (dst);  dst = a;  with theta != NULL, flc_fedopt_step's step on (theta, a, v), bit-identical to that call.
+ * The result depends on (C, b, rule) and the values only: a rerun gives the same bytes (no atomics).  Host arrays of
+ * device pointers, srcs[m * n_tensors + t]; a launch holds about 256 source pointers, so 32 tensors up to 8 messages,
+ * 16 up to 16, 8 up to 32 and 4 up to 64, further tensors in further launches (tensor order).  The client axis is not
+ * chained across launches: n_src > 64 is refused.  v may be NULL for opt = avg.  FLC_EINVAL, nothing launched: an
+ * unknown rule; n_src outside [1, 64]; trim < 0 or 2 * trim >= n_src; init_mode outside 0..2; with theta an unknown
+ * opt, or an adaptive opt without v; a negative size; a null pointer of a non-empty tensor. */
+#define FLC_ROBUST_MEDIAN 0
+#define FLC_ROBUST_TRIMMED 1
+#define FLC_ROBUST_MAX_SRC 64
+int flc_robust_fold(float* const* dst, const float* const* srcs, int n_src, const int64_t* sizes, int n_tensors,
+                    int rule, int trim, float scale, int init_mode, float beta, float* const* theta, float* const* v,
+                    int opt, double lr, double beta2, double tau, void* stream);
 /* avg_parameters (nodes.py:1134-1163) and update_gradients (nodes.py:1165-1180) of one round in ONE launch — what
  * the variance-reduced servers run back to back (fedprox/_fedprox.py:163-167, fedpd/_fedpd.py:197-202,
  * proxskip/_proxskip.py:212-216, pfedmac/_pfedmac.py:158-162):
